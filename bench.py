@@ -21,19 +21,32 @@ north_star tolerance) or "fp32" (exact-fp32 MFMA).  Every line states its own me
 
 ``--config train``: BASELINE configs[4], one training step on a synthetic 256^3 crop (see train_measure).
 
-The default N = 1 line (what the driver runs) carries three measurements from ONE process: ``value`` = the fp16 eval
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline figure needs: set-up, W warm-up steps, K
+timed steps (no per-launch instrumentation), the outputs when ``--dump-outputs DIR`` is given, and the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, config).  Everything else it measures is behind ``--full``.
+
+``--full``: the N = 1 line carries three measurements from ONE process: ``value`` = the fp16 eval
 path (BASELINE's dtype), ``also.split`` (and ``also.mix8``, its variant with fp8 correction products in the 3x3x3 convs)
 = the same volume at the precision that meets north_star's 1e-3 tolerance
 (value, ms_per_step, roofline, parity_vs_fp32_mode measured live) and ``also.train_bf16`` = configs[4] (ms_per_step,
-Mvoxels/s trained, roofline); ``--no-also`` prints the first alone.  ``box`` = a bare-MFMA-loop probe of this device:
-boxes differ by ~6 % under matrix load, figures from two boxes compare only beside it.
+Mvoxels/s trained, roofline); ``--no-also`` prints the first alone.  The timed steps carry HIP events around every conv
+and stage launch (``roofline``, ``roofline_gate`` / ``_ccl`` / ``_assign``), and the line adds the CPU baseline
+(``--no-cpu-baseline`` skips it) and ``box`` = a bare-MFMA-loop probe of this device: boxes differ by ~6 % under matrix
+load, figures from two boxes compare only beside it.
+
+``--dump-outputs DIR``: after the timed steps, what the last step computed is written as DIR/<name>.npy (float64 for
+integer arrays, float32 otherwise; a fixed, seeded sample of DUMP_SAMPLE elements of anything larger, under 40 MB
+in all), so that two builds can be compared output for output on identical seeded inputs.  Eval: the arrays
+``ShardedVolume.run`` returns (instance_mask, labels, skeleton, vec4), n_instances, the voxel count of every instance id
+and the network's output of the first tile batch (recomputed on the same launch geometry: the kernels are
+deterministic).  Train: the losses and the updated parameters.  Ranks other than 0 write rank<r>_<name>.npy.
 
 ``--streams N`` (default 1): N tile batches in flight on N HIP streams.  ``--streams 2 --tile-batch 32`` measured +1.3 %
 over one stream of 64-tile batches (the conv kernels fill the register file, so only launch tails overlap).  Overlapping
 launches make per-launch durations meaningless -- rocprofv3's and the bench's own -- so with more than one stream
-``roofline`` (and the stage rooflines) are measured in ONE extra single-stream step after the warm-up, outside the timed
-region (``roofline.timed_over`` says so); the default stays one stream so that the driver's line and a rocprofv3 run of
-the same command time the same launches.
+``--full``'s ``roofline`` (and the stage rooflines) are measured in ONE extra single-stream step after the warm-up, outside
+the timed region (``roofline.timed_over`` says so); the default stays one stream so that the driver's line and a rocprofv3
+run of the same command time the same launches.
 
 Synthetic data: uint8-range random image, random-init network of the named shape
 (DIMS [32,64,128,64,32], DEPTHS [2,2,2,2,2]).  A random-init net never crosses the 0.8
@@ -63,6 +76,7 @@ import torch.distributed as dist  # noqa: E402
 SCALE = (60, 60, 12)  # cfg.SKOOTS.VECTOR_SCALING default, skoots/config.py:144
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 MFMA_PEAK_TFLOPS = 2500.0  # dense fp16 / bf16 matrix peak
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: elements kept per array (a fixed, seeded sample of anything larger)
 
 
 def workload_shape(n_gpus: int):
@@ -352,6 +366,41 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def dump_array(out_dir, name, t, rank=0, sample=DUMP_SAMPLE):
+    """``t`` as out_dir/<name>.npy: float64 for 32/64-bit integers (exact), float32 otherwise; larger than ``sample``
+    elements -> the flattened array at ``sample`` indices drawn from a fixed seed (the same indices on every run)."""
+    import numpy as np
+    t = torch.as_tensor(t).detach()
+    if t.numel() > sample:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, t.numel(), (sample,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    exact = t.dtype in (torch.int32, torch.int64)
+    np.save(os.path.join(out_dir, (f"rank{rank}_" if rank else "") + name + ".npy"),
+            t.to(torch.float64 if exact else torch.float32).cpu().numpy())
+
+
+def dump_eval_outputs(out_dir, res, model, image, sv, mean, std, rank, world):
+    """What the last timed step of the eval path computed (see the module docstring), under 40 MB in all."""
+    from skoots_amd.parallel import tile_plan
+    sample = DUMP_SAMPLE // world
+    inst = res["instance_mask"]
+    for name in ("instance_mask", "labels", "skeleton", "vec4"):
+        dump_array(out_dir, name, res[name], rank, sample)
+    dump_array(out_dir, "n_instances", torch.tensor([int(res["n_instances"])], dtype=torch.int64), rank)
+    dump_array(out_dir, "instance_voxels_per_id", torch.bincount(inst.reshape(-1)), rank, sample)
+    # the network output of the run's first tile batch, recomputed with the same arguments on the same model context
+    plan, eff = tile_plan(sv.shape, (300, 300, 20), (50, 50, 5), world, halo=sv.halo)
+    reach, ov = (3, 3, 1), (50, 50, 5)
+    lo = [max(0, o - r) for o, r in zip(ov, reach)]
+    hi = [min(s, s - o + r) for s, o, r in zip(eff, ov, reach)]
+    wlo = sv.window[0]
+    batch = [(x, y, z - wlo) for (x, y, z) in plan[rank][:sv.tile_batch_used]]
+    out5 = model.forward_tiles(image, batch, eff, mean, std, out_box=(lo, hi))
+    dump_array(out_dir, "network_out_first_batch", out5[:, :, lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]], rank, sample)
+    torch.cuda.synchronize(image.device)
+
+
 # ---------------------------------------------------------------------------------------------------
 # launcher: --gpus N without torchrun
 # ---------------------------------------------------------------------------------------------------
@@ -472,9 +521,9 @@ def conv_c1_measure(dev, iters=5, warmup=2, tile=(512, 512, 128)):
 
 
 def eval_main(args, rank, world, local):
-    """The headline line.  At N = 1 the same process then times, on the same resident volume, the precision that
-    meets north_star's 1e-3 tolerance (``also.split``) and one training leg (``also.train_bf16``, configs[4]) --
-    the driver's command prints one line and that line carries all three (``--no-also`` skips them)."""
+    """The headline line.  With ``--full`` at N = 1 the same process then times, on the same resident volume, the
+    precision that meets north_star's 1e-3 tolerance (``also.split``) and one training leg (``also.train_bf16``,
+    configs[4]) -- one line carries all three (``--no-also`` skips them)."""
     ndev = torch.cuda.device_count()
     if ndev < 1:
         raise SystemExit("bench.py needs an MI355X: there is no CPU path")
@@ -533,10 +582,11 @@ def eval_main(args, rank, world, local):
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    probe = box_probe(dev) if rank == 0 else None
+    probe = box_probe(dev) if rank == 0 and args.full else None
 
-    def measure(precision, steps, warmup, streams):
-        """W untimed + K timed steps of the whole path at ``precision``; returns rank 0's line (None elsewhere)."""
+    def measure(precision, steps, warmup, streams, dump_dir=None):
+        """W untimed + K timed steps of the whole path at ``precision``; returns rank 0's line (None elsewhere).
+        ``dump_dir``: write what the last timed step computed there (--dump-outputs)."""
         model.precision = precision
 
         def step(prof=None, sprof=None, nstreams=1):
@@ -547,13 +597,14 @@ def eval_main(args, rank, world, local):
         # Two tile batches in flight overlap their launches, which makes a per-launch duration meaningless: with
         # streams > 1 the `roofline` figures come from ONE extra single-stream step with the per-launch HIP events on --
         # every conv launch has the device to itself there -- run after the warm-up and outside the timed region.
-        prof, sprof = unet.ConvProfile(), KernelProfile()
+        # A plain run times the steps without the per-launch HIP events: the rooflines they feed are --full's.
+        prof, sprof = (unet.ConvProfile(), KernelProfile()) if args.full else (None, None)
         res = None
         for i in range(warmup):
             res = step(None, None, streams)
             log(f"warm-up step done: {sv.timings}")
         roof_steps, roof_src = steps, "timed steps"
-        if streams > 1:
+        if streams > 1 and args.full:
             res = step(prof, sprof, 1)
             roof_steps, roof_src = 1, "extra single-stream step after the warm-up, untimed"
         sv.timings.clear()
@@ -575,6 +626,9 @@ def eval_main(args, rank, world, local):
                  "alloc_retries": int(mstat1.get("num_alloc_retries", 0) - mstat0.get("num_alloc_retries", 0)),
                  "reserved_gib": round(mstat1.get("reserved_bytes.all.current", 0) / 2 ** 30, 1)}
         log(f"[{precision}] timed {steps} steps in {dt:.3f} s; per step {per_step_ms[:8]} ms; allocator {alloc}")
+        if dump_dir:
+            dump_eval_outputs(dump_dir, res, model, image, sv, mean, std, rank, world)
+            log(f"[{precision}] outputs of the last timed step written to {dump_dir}")
         comm_stats = sv.comm.stats()
         tiles = sv.tiles_this_rank
         if world > 1:
@@ -596,18 +650,6 @@ def eval_main(args, rank, world, local):
         if rank == 0:
             ms = dt / steps * 1e3
             voxels = X * Y * Z
-            conv_ms, conv_flops, conv_launches = prof.totals()
-            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-            executed = prof.executed_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-            traffic, traffic_src = conv_hbm_traffic(args.tile_batch)
-            per_layer = {}
-            for e0, e1, fl, name in prof.named():
-                d = per_layer.setdefault(name, [0.0, 0.0, 0])
-                d[0] += e0.elapsed_time(e1)
-                d[1] += fl
-                d[2] += 1
-            layers = {k: {"tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1), "avg_launch_ms": round(v[0] / v[2], 4)}
-                      for k, v in per_layer.items() if v[0] > 0}
             line = {
                 "metric": "Mvoxels/s end-to-end (3D U-Net fwd + instance assign)",
                 "value": round(voxels / (dt / steps) / 1e6, 3), "unit": "Mvoxels/s",
@@ -624,26 +666,40 @@ def eval_main(args, rank, world, local):
                            "inject_layout": "none" if inject_vol is None else ("strided windows" if args.strided_inject else "contiguous per-tile blocks"),
                            "stage_ms": {k: round(v / steps * 1e3, 2) for k, v in sv.timings.items()},
                            "step_ms_min_max": [min(per_step_ms), max(per_step_ms)], "allocator_in_timed_steps": alloc},
-                "roofline": {"bound": "mfma", "kernel": "conv3_px_kernel (enc0.1, dec0.1: the kernel with the most time) + conv3_upf_kernel (dec0.0, dec1.0) "
-                                                          "+ conv3_kernel<64|128> (enc1.x, dec1.1, mid.x): all 3x3x3 MFMA conv launches" if precision == "fp16" else
-                                                          "conv3_m16_kernel / conv3_kernel / conv3_upf_kernel, split variants (all 3x3x3 MFMA conv launches)",
-                             "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                             "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic if precision == "fp16" else None,
-                             # the two decoder convs over [skip, upsample(x)] run with the upsample folded into the weights
-                             # (8 of 27 taps for the upsampled channels): the pipe executes fewer FLOPs than the algorithm counts
-                             "executed": round(executed, 2), "frac_executed": round(executed / MFMA_PEAK_TFLOPS, 4),
-                             "traffic_unit": f"bytes per launch of {args.tile_batch} tiles (PMC, profiles/{traffic_src})",
-                             "launches": conv_launches, "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
-                             "timed_over": f"{roof_steps} {roof_src} (HIP events around every conv launch, one stream)",
-                             "flops_counted": "achieved: algorithmic 2*Cin*Cout*27 per output voxel, the conv as the reference states it "
-                                              "(split mode issues 3x that on the MFMA pipe); executed: what the launches issue (fp16 mode: "
-                                              "dec0.0 / dec1.0 fold the nearest-upsample into the weights, 35 of 54 tap-chunks); "
-                                              "dec0.1's launches also contain the GroupNorm + SiLU of their input (fused, fp16 mode)",
-                             "layers": layers},
             }
+        if rank == 0 and args.full:
+            conv_ms, conv_flops, conv_launches = prof.totals()
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            executed = prof.executed_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            traffic, traffic_src = conv_hbm_traffic(args.tile_batch)
+            per_layer = {}
+            for e0, e1, fl, name in prof.named():
+                d = per_layer.setdefault(name, [0.0, 0.0, 0])
+                d[0] += e0.elapsed_time(e1)
+                d[1] += fl
+                d[2] += 1
+            layers = {k: {"tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1), "avg_launch_ms": round(v[0] / v[2], 4)}
+                      for k, v in per_layer.items() if v[0] > 0}
+            line["roofline"] = {"bound": "mfma", "kernel": "conv3_px_kernel (enc0.1, dec0.1: the kernel with the most time) + conv3_upf_kernel (dec0.0, dec1.0) "
+                                                             "+ conv3_kernel<64|128> (enc1.x, dec1.1, mid.x): all 3x3x3 MFMA conv launches" if precision == "fp16" else
+                                                             "conv3_m16_kernel / conv3_kernel / conv3_upf_kernel, split variants (all 3x3x3 MFMA conv launches)",
+                                "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic if precision == "fp16" else None,
+                                # the two decoder convs over [skip, upsample(x)] run with the upsample folded into the weights
+                                # (8 of 27 taps for the upsampled channels): the pipe executes fewer FLOPs than the algorithm counts
+                                "executed": round(executed, 2), "frac_executed": round(executed / MFMA_PEAK_TFLOPS, 4),
+                                "traffic_unit": f"bytes per launch of {args.tile_batch} tiles (PMC, profiles/{traffic_src})",
+                                "launches": conv_launches, "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
+                                "timed_over": f"{roof_steps} {roof_src} (HIP events around every conv launch, one stream)",
+                                "flops_counted": "achieved: algorithmic 2*Cin*Cout*27 per output voxel, the conv as the reference states it "
+                                                 "(split mode issues 3x that on the MFMA pipe); executed: what the launches issue (fp16 mode: "
+                                                 "dec0.0 / dec1.0 fold the nearest-upsample into the weights, 35 of 54 tap-chunks); "
+                                                 "dec0.1's launches also contain the GroupNorm + SiLU of their input (fused, fp16 mode)",
+                                "layers": layers}
             if precision == "fp32":  # the MFMA conv profile only instruments the fp16 / split kernels
                 line["roofline"] = None
             line.update(stage_rooflines(sprof))
+        if rank == 0:
             if world > 1:
                 line["multi_gpu"] = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(),
                                      "tiles_per_rank": tiles, "slab_planes": [b - a for a, b in sv.slabs],
@@ -652,7 +708,7 @@ def eval_main(args, rank, world, local):
                                                                  "ms_max_over_ranks": round(v.get("ms_max_over_ranks", v["ms"]) / steps, 3),
                                                                  "calls": v["calls"] // steps}
                                                              for k, v in comm_stats.items()}}
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             # every rank runs it (same launches everywhere keeps the ranks in step); rank 0 reports
             plan, eff = tile_plan(shape, (300, 300, 20), (50, 50, 5), world)
             mine = plan[rank][:8]
@@ -663,9 +719,10 @@ def eval_main(args, rank, world, local):
                 line["parity_vs_fp32_mode"] = par
         return line
 
-    line = measure(args.precision, args.steps, args.warmup, args.streams)
+    line = measure(args.precision, args.steps, args.warmup, args.streams, dump_dir=args.dump_outputs)
     also = {}
-    if world == 1 and not args.no_also and args.precision == "fp16":
+    extra_legs = args.full and world == 1 and not args.no_also and args.precision == "fp16"
+    if extra_legs:
         # the precision that meets north_star's tolerance, same volume, same process
         sp = measure("split", args.also_steps, 1, args.streams)
         also["split"] = {k: sp[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "dtype", "parity_vs_fp32_mode")
@@ -690,12 +747,12 @@ def eval_main(args, rank, world, local):
                                             "product + one block-scaled fp8 instruction stream that takes 10/9 (K = 128) or 1 (K = 64, "
                                             "folded taps) fp16-pass times")
         also["mix8"]["step_ms_min_max"] = mx["config"]["step_ms_min_max"]
-    if rank == 0:
+    if rank == 0 and args.full:
         line["box"] = probe
         if not args.no_cpu_baseline and world == 1:
             log("timing the CPU restatement (bounded sample)")
             line["cpu_baseline"] = cpu_baseline(args.cpu_budget)
-    if world == 1 and not args.no_also and args.precision == "fp16":
+    if extra_legs:
         del sv, model, image, inject_vol
         tile_cache.clear()
         blocks = None
@@ -703,7 +760,7 @@ def eval_main(args, rank, world, local):
         also["conv_c1"] = conv_c1_measure(dev)
         targs = argparse.Namespace(**vars(args))
         targs.precision, targs.steps, targs.warmup, targs.no_cpu_baseline = "bf16", args.also_train_steps, 2, True
-        targs.shape = args.also_train_shape
+        targs.shape, targs.dump_outputs = args.also_train_shape, None
         tr = train_measure(targs, rank, world, dev)
         also["train_bf16"] = {k: tr[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "roofline")}
         also["train_bf16"]["config"] = tr["config"]
@@ -798,7 +855,7 @@ def train_measure(args, rank, world, dev):
     for _ in range(args.warmup):
         losses = step(images, masks, skele, baked)
     barrier()
-    prof = KernelProfile()
+    prof = KernelProfile() if args.full else None   # per-launch HIP events: the roofline is --full's
     model._L.profile = prof if model.fast16 else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -806,6 +863,9 @@ def train_measure(args, rank, world, dev):
     barrier()
     dt = time.perf_counter() - t0
     model._L.profile = None
+    if args.dump_outputs:   # what the last step computed: its losses and the parameters it updated
+        dump_array(args.dump_outputs, "losses", losses, rank)
+        dump_array(args.dump_outputs, "params", model.flat_param, rank, DUMP_SAMPLE // world)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -824,7 +884,7 @@ def train_measure(args, rank, world, dev):
                            "precision": args.precision, "steps_per_s": round(args.steps / dt * world, 4),
                            "losses": [round(float(v), 6) for v in losses.cpu()],
                            "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)}}
-        tot = prof.totals()
+        tot = prof.totals() if args.full else None
         if tot:
             kms = sum(v[0] for v in tot.values())
             kfl = sum(v[1] for v in tot.values())
@@ -836,7 +896,7 @@ def train_measure(args, rank, world, dev):
                                 "launches": sum(v[2] for v in tot.values()),
                                 "ms_per_step": {k: round(v[0] / args.steps, 3) for k, v in tot.items()},
                                 "tflops": {k: round(v[1] / (v[0] * 1e-3) / 1e12, 1) for k, v in tot.items() if v[0] > 0}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             log("timing the CPU restatement of the training step (bounded sample)")
             line["cpu_baseline"] = train_cpu_baseline(budget_s=args.cpu_budget)
     return line
@@ -871,11 +931,20 @@ def main():
     ap.add_argument("--also-train-shape", type=str, default="", help="X,Y,Z of the training leg's crop (default 256,256,256)")
     ap.add_argument("--launcher-dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=8.0, help="seconds of stage-1 CPU work in the cpu_baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-launch rooflines, parity against the fp32 mode, the box "
+                         "probe, the CPU baseline and (eval, N = 1, fp16) the `also` legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (seeded samples of large arrays)")
     args = ap.parse_args()
     if args.precision is None:
         args.precision = "fp16" if args.config == "eval" else "bf16"
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:

@@ -1,11 +1,13 @@
 """The driver's contract with bench.py, checked on the GPU box on a reduced volume: ONE JSON line with the metric of
-BASELINE.json, the roofline of the dominant kernel measured live, the per-stage HBM rooflines, the measured parity of
-the benched precision and the CPU baseline; and the training leg (configs[4]) on a reduced crop."""
+BASELINE.json; with --full also the roofline of the dominant kernel measured live, the per-stage HBM rooflines, the
+measured parity of the benched precision and the CPU baseline, and the training leg (configs[4]) on a reduced crop; a
+plain run carries the headline figure alone and dumps what its last step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +26,7 @@ def _run(*argv):
 
 @pytest.mark.parametrize("precision", ["fp16", "split"])
 def test_eval_line_contract(precision):
-    d = _run("--steps", "1", "--warmup", "1", "--shape", "512,512,64", "--precision", precision, "--cpu-budget", "1",
+    d = _run("--full", "--steps", "1", "--warmup", "1", "--shape", "512,512,64", "--precision", precision, "--cpu-budget", "1",
              "--also-steps", "1", "--also-train-steps", "2", "--also-train-shape", "64,64,64")
     assert d["metric"].startswith("Mvoxels/s end-to-end") and d["unit"] == "Mvoxels/s" and d["n_gpus"] == 1
     assert d["steps"] == 1 and d["warmup"] == 1 and d["higher_is_better"] is True and d["vs_baseline"] is None
@@ -68,6 +70,33 @@ def test_eval_line_contract(precision):
     assert d["config"]["inject_layout"] == "contiguous per-tile blocks"
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline figure alone -- no per-launch rooflines, parity, box probe, CPU baseline or `also`
+    legs -- with exactly --steps timed steps, and --dump-outputs writes what its last step computed: float32 / float64
+    arrays, well under 64 MB, identical for another number of steps on the same seeded inputs."""
+    dumps = []
+    for steps in (1, 2):
+        out = tmp_path / f"steps{steps}"
+        d = _run("--steps", str(steps), "--warmup", "1", "--shape", "512,512,64", "--dump-outputs", str(out))
+        assert d["metric"].startswith("Mvoxels/s end-to-end") and d["unit"] == "Mvoxels/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f16" and d["steps"] == steps and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 512 * 512 * 64 / d["ms_per_step"] / 1e3) < 0.01 * d["value"]
+        assert not {"roofline", "roofline_gate", "roofline_ccl", "roofline_assign", "parity_vs_fp32_mode", "box", "cpu_baseline",
+                    "also"} & set(d)
+        arrays = {p.stem: np.load(p) for p in sorted(out.glob("*.npy"))}
+        assert {"instance_mask", "labels", "skeleton", "vec4", "n_instances", "instance_voxels_per_id",
+                "network_out_first_batch"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) < 64 * 2 ** 20
+        k = int(arrays["n_instances"][0])
+        assert k == d["config"]["instances"] > 0 and arrays["instance_mask"].max() <= k
+        assert arrays["instance_voxels_per_id"].size == k + 1 and arrays["instance_voxels_per_id"].sum() == 512 * 512 * 64
+        assert np.isfinite(arrays["network_out_first_batch"]).all() and np.abs(arrays["network_out_first_batch"]).max() > 0
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+
+
 def test_eval_line_two_ranks_gloo_rehearsal():
     """`python bench.py --gpus 2` without a launcher, rehearsed on the one-GPU box: two rank processes share the device and
     exchange through gloo (SKOOTS_DIST_BACKEND=gloo).  Rank 0 prints ONE line for the 2-rank job: the Z-sharded pipeline
@@ -92,16 +121,21 @@ def test_eval_line_two_ranks_gloo_rehearsal():
 def test_eval_line_two_streams_keeps_a_roofline():
     """--streams 2: the timed steps overlap two tile batches; the per-launch roofline then comes from the single-stream
     warm-up steps and says so."""
-    d = _run("--steps", "1", "--warmup", "2", "--shape", "512,512,64", "--streams", "2", "--tile-batch", "32", "--no-also", "--no-cpu-baseline")
+    d = _run("--full", "--steps", "1", "--warmup", "2", "--shape", "512,512,64", "--streams", "2", "--tile-batch", "32", "--no-also",
+             "--no-cpu-baseline")
     r = d["roofline"]
     assert d["config"]["streams"] == 2 and "warm-up" in r["timed_over"] and r["launches"] > 0 and 0.02 < r["frac"] < 1.0
     assert d["roofline_assign"]["launches"] >= 1 and d["config"]["instances"] > 0
 
 
-def test_train_line_contract():
-    d = _run("--config", "train", "--steps", "2", "--warmup", "1", "--shape", "64,64,64", "--cpu-budget", "1")
+def test_train_line_contract(tmp_path):
+    d = _run("--full", "--config", "train", "--steps", "2", "--warmup", "1", "--shape", "64,64,64", "--cpu-budget", "1",
+             "--dump-outputs", str(tmp_path))
     assert d["dtype"] == "bf16" and d["config"]["precision"] == "bf16" and d["n_gpus"] == 1 and d["value"] > 0
     assert d["roofline"]["bound"] == "mfma" and d["roofline"]["launches"] > 0 and d["roofline"]["achieved"] > 0
     assert set(d["roofline"]["ms_per_step"]) == {"conv_fwd_dgrad", "conv_wgrad"}
     assert all(0 < v < 3 for v in d["config"]["losses"][:3])
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
+    losses = np.load(tmp_path / "losses.npy")
+    assert np.allclose(losses, d["config"]["losses"], rtol=1e-5, atol=1e-6)
+    assert np.load(tmp_path / "params.npy").dtype == np.float32
