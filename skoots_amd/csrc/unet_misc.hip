@@ -77,6 +77,7 @@ __global__ void __launch_bounds__(256) stem_norm_kernel(StemArgs a) {
 static int stem_rows(int Yt, int Zt) {
     int r = (40 * 1024) / (3 * (Zt + 2) * (int)sizeof(t16)) - 2;
     if (r > 150) r = 150;
+    if (r < 1) r = 1;   // very deep tiles: one row (the caller's LDS check refuses what does not fit)
 #ifdef SK_TUNING
     if (const char* e = getenv("SK_STEM_ROWS")) {
         const int v = atoi(e);
@@ -84,6 +85,7 @@ static int stem_rows(int Yt, int Zt) {
     }
 #endif
     if (r > Yt) r = Yt;
+    if (r < 1) return 1;   // Yt < 1: refused by the callers' extent checks
     // even split of Yt
     int n = (Yt + r - 1) / r;
     r = (Yt + n - 1) / n;
@@ -122,7 +124,7 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
     // stage the three padded x planes' rows [y0, y0 + rows + 2): contiguous (rows+2)*pz halves each.  Eight loads per
     // lane are issued before the first LDS store (a plain copy loop chains load -> store, one latency per 256 dwords).
     const int seg_halves = (a.rows + 2) * pz;          // LDS pitch per plane (halves, even)
-    const int seg_dw = (rows + 2) * pz / 2;               // dwords to copy (pz is even: Zt % 4 == 0)
+    const int seg_dw = (rows + 2) * pz / 2;               // dwords to copy (pz is even: Zt % 2 == 0, check_stem_tile)
     {
         const unsigned int* src[3];
 #pragma unroll
@@ -627,6 +629,14 @@ int sk_conv3d_stem_num_blocks(int X, int Y, int Z) {
 
 static size_t stem_lds_bytes(int Yt, int Zt) { return (size_t)3 * (stem_rows(Yt, Zt) + 2) * (Zt + 2) * sizeof(t16); }
 
+// Tile extents every stem_kernel launch needs: positive, Zt even (the staging copy moves dwords of a pitch Zt + 2) and
+// the three staged planes within 60 KiB of LDS.  Checked before ANY launch, so a refused call has written nothing.
+static int check_stem_tile(int Xt, int Yt, int Zt, const char* who) {
+    SK_CHECK_ARG(Xt >= 1 && Yt >= 1 && Zt >= 1, "%s: bad tile extents (%d,%d,%d)", who, Xt, Yt, Zt);
+    SK_CHECK_ARG(Zt % 2 == 0 && stem_lds_bytes(Yt, Zt) <= 60 * 1024, "%s: tile depth %d unsupported", who, Zt);
+    return SK_OK;
+}
+
 size_t sk_conv3d_stem_workspace_bytes(int B, int Xt, int Yt, int Zt) {
     return (size_t)B * (Xt + 2) * (Yt + 2) * (Zt + 2) * sizeof(t16);
 }
@@ -638,6 +648,7 @@ static int fill_stem_args(StemArgs& a, const void* image, int X, int Y, int Z, c
     SK_CHECK_ARG(cout == 32, "sk_conv3d_stem: cout must be 32");
     SK_CHECK_ARG(B >= 1 && B <= kStemMaxB, "sk_conv3d_stem: batch must be in [1,%d]", kStemMaxB);
     SK_CHECK_ARG(stdv != 0.0f, "sk_conv3d_stem: std must be non-zero");
+    if (int rc = check_stem_tile(Xt, Yt, Zt, "sk_conv3d_stem")) return rc;
     SK_CHECK_ARG(workspace_bytes >= sk_conv3d_stem_workspace_bytes(B, Xt, Yt, Zt),
                  "sk_conv3d_stem: workspace too small");
     a.image = (const t16*)image;
@@ -679,7 +690,6 @@ int sk_conv3d_stem(const void* image, int X, int Y, int Z, const int32_t* origin
     a.partial = gn_partial;
     dim3 g1(Xt + 2, B);
     stem_norm_kernel<<<g1, 256, 0, (hipStream_t)stream>>>(a);
-    SK_CHECK_ARG(Zt % 2 == 0 && stem_lds_bytes(Yt, Zt) <= 60 * 1024, "sk_conv3d_stem: tile depth %d unsupported", Zt);
     if (stem_lds_bytes(Yt, Zt) > 40 * 1024)
         SK_CHECK_HIP(hipFuncSetAttribute((const void*)stem_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)stem_lds_bytes(Yt, Zt)));
@@ -703,7 +713,6 @@ int sk_conv3d_stem_raw(const void* image, int X, int Y, int Z, const int32_t* or
     a.out = (t16*)out_raw;
     dim3 g1(Xt + 2, B);
     stem_norm_kernel<<<g1, 256, 0, (hipStream_t)stream>>>(a);
-    SK_CHECK_ARG(Zt % 2 == 0 && stem_lds_bytes(Yt, Zt) <= 60 * 1024, "sk_conv3d_stem_raw: tile depth %d unsupported", Zt);
     if (stem_lds_bytes(Yt, Zt) > 40 * 1024)
         SK_CHECK_HIP(hipFuncSetAttribute((const void*)stem_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)stem_lds_bytes(Yt, Zt)));
@@ -716,6 +725,7 @@ static int stem_apply_impl(int B, int Xt, int Yt, int Zt, const float* weight, c
                            const float* affine, void* out, int cout, const void* workspace, void* stream, bool split, bool mix8 = false) {
     SK_CHECK_ARG(weight && bias && affine && out && workspace, "sk_conv3d_stem_apply: NULL pointer");
     SK_CHECK_ARG(cout == 32 && B >= 1 && B <= kStemMaxB, "sk_conv3d_stem_apply: bad cout / batch");
+    if (int rc = check_stem_tile(Xt, Yt, Zt, "sk_conv3d_stem_apply")) return rc;
     StemArgs a{};
     a.B = B;
     a.Xt = Xt;
