@@ -447,6 +447,47 @@ int sk_train_tversky(const float* predicted, const float* ground_truth, int B, i
                      float alpha, float beta, float eps, float* loss, float* workspace,
                      void* stream);
 
+/* Soft skeleton (train/loss.py:269-310, soft_skeletonize): img, skel (B, X, Y, Z) fp32, every axis
+ * extent >= 1, 0 <= iter <= SK_CLDICE_MAX_ITER.  e_0 = img, e_{k+1} = min(min(p_x, p_y), p_z) with
+ * p_a the 3-wide min along axis a, open_k = 3x3x3 max of e_{k+1} (out-of-range neighbours ignored),
+ * d_k = relu(e_k - open_k); skel = d_0, then skel += relu(d_k - skel * d_k) for k = 1..iter.
+ * Bit-identical to the reference in fp32.  workspace: sk_train_soft_skeleton_workspace_floats(...). */
+#define SK_CLDICE_MAX_ITER 16
+int sk_train_soft_skeleton(const float* img, float* skel, int B, int X, int Y, int Z, int iter,
+                           float* workspace, void* stream);
+int64_t sk_train_soft_skeleton_workspace_floats(int B, int X, int Y, int Z);
+
+/* soft_dice_cldice(iter, alpha, smooth)(pred, gt) (train/loss.py:344-391): pred, gt (B, X, Y, Z)
+ * fp32.  loss (DEVICE, 1 float) = (1 - alpha) dice + alpha cl_dice, dice = 1 - (2 sum p g + 1) /
+ * (sum g + sum p + 1) (smooth fixed at 1, as the reference calls it), cl_dice = 1 - 2 tprec tsens /
+ * (tprec + tsens), tprec = (sum S_p g + smooth) / (sum S_p + smooth), tsens = (sum S_t p + smooth) /
+ * (sum S_t + smooth), S = the soft skeletons; every sum runs over the whole batch.  dpred (B, X, Y, Z)
+ * = d loss / d pred (torch autograd's routing: max-pool ties to the first maximum in x, y, z scan
+ * order, torch.min ties split in halves, relu' = 0 at 0; no gradient into gt), or NULL for the value
+ * only; it must not alias pred or gt.  Deterministic (no atomics).  Arguments as sk_train_soft_skeleton;
+ * alpha and smooth finite.  workspace: sk_train_soft_dice_cldice_workspace_floats(B, X, Y, Z, iter). */
+int sk_train_soft_dice_cldice(const float* pred, const float* gt, int B, int X, int Y, int Z, int iter,
+                              float alpha, float smooth, float* loss, float* dpred, float* workspace,
+                              void* stream);
+int64_t sk_train_soft_dice_cldice_workspace_floats(int B, int X, int Y, int Z, int iter);
+
+/* A soft-clDice term of the fused step (sk_train_loss's layout: logits (B, X*Y*Z, 5), target
+ * (B, X*Y*Z), baked (B, 3, X*Y*Z), host vector_scale / sigma).  term 0 = embed, 1 = probability,
+ * 2 = skeleton.  sk_train_cldice_term_field: prob (B, X*Y*Z) = the term's probability field
+ * (sk_train_loss's embedding probability, sigmoid(logits[..., 4]), sigmoid(logits[..., 3])) and
+ * gt = (target > 0); baked may be NULL for terms 1, 2.  sk_train_cldice_chain, after sk_train_loss
+ * (run with this term's weight 0): dlogits += weight * dprob * d prob / d logits (through
+ * E = index + tanh(l) scale for term 0, p (1 - p) for 1, 2), losses[term] = term_loss[0] and
+ * losses[3] += weight * term_loss[0]; dlogits and dprob both NULL = losses only. */
+int sk_train_cldice_term_field(const float* logits, const float* target, const float* baked, int B,
+                               int X, int Y, int Z, const float* vector_scale_host,
+                               const float* sigma_host, int term, float* prob, float* gt,
+                               void* stream);
+int sk_train_cldice_chain(const float* logits, const float* baked, int B, int X, int Y, int Z,
+                          const float* vector_scale_host, const float* sigma_host, int term,
+                          float weight, const float* dprob, const float* term_loss, float* losses,
+                          float* dlogits, void* stream);
+
 /* Data gradient of a conv layer from dy (B, ox, oy, oz, cout) and the layer's own weight
  * (cout, cin_total, k, k, k), read transposed / tap-flipped in place.
  *   ksize 1, 3: dx (B, ox, oy, oz, cin_n) = gradient w.r.t. input channels [cin_lo, cin_lo+cin_n)

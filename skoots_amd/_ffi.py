@@ -117,6 +117,12 @@ _SIGS = {
     "sk_train_tversky": (i32, [vp, vp, i32, i64, C.c_float, C.c_float, C.c_float, vp, vp, vp]),
     "sk_train_loss_workspace_floats": (i64, [i32, i64]),
     "sk_train_loss_num_blocks": (i32, [i64]),
+    "sk_train_soft_skeleton": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "sk_train_soft_skeleton_workspace_floats": (i64, [i32, i32, i32, i32]),
+    "sk_train_soft_dice_cldice": (i32, [vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp]),
+    "sk_train_soft_dice_cldice_workspace_floats": (i64, [i32, i32, i32, i32, i32]),
+    "sk_train_cldice_term_field": (i32, [vp, vp, vp, i32, i32, i32, i32, fp, fp, i32, vp, vp, vp]),
+    "sk_train_cldice_chain": (i32, [vp, vp, i32, i32, i32, i32, fp, fp, i32, C.c_float, vp, vp, vp, vp, vp]),
     "sk_train_conv_dgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "sk_train_conv_wgrad": (i32, [C.POINTER(ConvSrc), i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "sk_train_conv_wgrad_workspace_floats": (i64, [i32, i32, i32, i32, i32, i32, i32]),

@@ -562,33 +562,69 @@ class TrainUNet:
         self._keep = []
 
 
+def _loss_term(spec):
+    """A term's loss: a ``tversky`` / ``soft_dice_cldice`` object, or an (alpha, beta, eps) tuple meaning tversky.
+    Returns ("tversky", [alpha, beta, eps]) or ("soft_cldice", the object)."""
+    from .loss import soft_dice_cldice, tversky
+    if isinstance(spec, soft_dice_cldice):
+        return "soft_cldice", spec
+    if isinstance(spec, tversky):
+        return "tversky", [spec.alpha, spec.beta, spec.eps]
+    a, b, e = spec
+    return "tversky", [float(a), float(b), float(e)]
+
+
 def fused_loss(logits: Tensor, masks: Tensor, skele_masks: Tensor, baked: Tensor, sigma: Sequence[float],
                vector_scale: Sequence[float] = (60, 60, 12),
                loss_params=((0.25, 0.75, 1e-8), (0.5, 0.5, 1e-8), (0.5, 1.5, 1e-8)),
                weights: Sequence[float] = (1.0, 1.0, 1.0), need_grad: bool = True):
-    """The three Tversky terms of the step (engine.py:465-493) and d(total)/d(logits) in two passes over
-    the logits.  logits (B, X, Y, Z, 5) = head outputs before tanh / sigmoid; masks, skele_masks
-    (B, 1, X, Y, Z) (> 0 = foreground); baked (B, 3, X, Y, Z); ``loss_params`` = (alpha, beta, eps) of the
-    embedding, probability and skeleton term.  Returns (losses[4] = embed, prob, skeleton, total; dlogits)."""
+    """The three loss terms of the step (engine.py:465-493) and d(total)/d(logits).  logits (B, X, Y, Z, 5) = head
+    outputs before tanh / sigmoid; masks, skele_masks (B, 1, X, Y, Z) (> 0 = foreground); baked (B, 3, X, Y, Z);
+    ``loss_params`` = the embedding, probability and skeleton term's loss: an (alpha, beta, eps) tuple or a
+    ``tversky`` object (Tversky; the three Tversky terms and their gradient take two passes over the logits) or a
+    ``soft_dice_cldice`` object (its probability field -- the embedding probability, sigmoid(logits[..., 4]) or
+    sigmoid(logits[..., 3]) -- through the soft-clDice kernels, the gradient chained into the logits).
+    Returns (losses[4] = embed, prob, skeleton, total; dlogits)."""
     _ffi.require_gpu(logits, "logits")
     B, X, Y, Z, five = logits.shape
     if five != 5 or logits.dtype != torch.float32:
         raise ValueError("logits must be fp32 (B, X, Y, Z, 5)")
+    terms = [_loss_term(t) for t in loss_params]
     n = X * Y * Z
     dev = logits.device
     m = masks.reshape(B, n).to(dev, torch.float32).contiguous()
     sk = skele_masks.reshape(B, n).to(dev, torch.float32).contiguous()
     bk = baked.reshape(B, 3, n).to(dev, torch.float32).contiguous()
     params: List[float] = []
-    for (a, b, e), wt in zip(loss_params, weights):
-        params += [float(a), float(b), float(e), float(wt)]
+    for (kind, p), wt in zip(terms, weights):
+        # a soft-clDice term weighs 0 in the Tversky kernels: its value and gradient are added below
+        params += (p + [float(wt)]) if kind == "tversky" else [0.5, 0.5, 1.0, 0.0]
     losses = torch.empty(16, dtype=torch.float32, device=dev)
     dl = torch.empty_like(logits) if need_grad else None
     ws = torch.empty(int(_ffi.lib.sk_train_loss_workspace_floats(B, n)), dtype=torch.float32, device=dev)
+    scale_h = _ffi.float_array([float(v) for v in vector_scale])
+    sigma_h = _ffi.float_array([float(s) for s in sigma])
+    st = _ffi.stream_ptr(dev)
     _ffi.check(_ffi.lib.sk_train_loss(_ffi.ptr(logits), _ffi.ptr(m), _ffi.ptr(sk), _ffi.ptr(bk), B, X, Y, Z,
-                                      _ffi.float_array([float(v) for v in vector_scale]),
-                                      _ffi.float_array([float(s) for s in sigma]), _ffi.float_array(params),
-                                      _ffi.ptr(losses), _ffi.ptr(dl), _ffi.ptr(ws), _ffi.stream_ptr(dev)))
+                                      scale_h, sigma_h, _ffi.float_array(params),
+                                      _ffi.ptr(losses), _ffi.ptr(dl), _ffi.ptr(ws), st))
+    for term, ((kind, fn), wt) in enumerate(zip(terms, weights)):
+        if kind != "soft_cldice":
+            continue
+        prob = torch.empty((B, n), dtype=torch.float32, device=dev)
+        gt = torch.empty_like(prob)
+        _ffi.check(_ffi.lib.sk_train_cldice_term_field(_ffi.ptr(logits), _ffi.ptr(sk if term == 2 else m), _ffi.ptr(bk),
+                                                       B, X, Y, Z, scale_h, sigma_h, term, _ffi.ptr(prob), _ffi.ptr(gt),
+                                                       st))
+        term_loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dprob = torch.empty_like(prob) if need_grad else None
+        cws = torch.empty(int(_ffi.lib.sk_train_soft_dice_cldice_workspace_floats(B, X, Y, Z, min(max(fn.iter, 0), 16))),
+                          dtype=torch.float32, device=dev)
+        _ffi.check(_ffi.lib.sk_train_soft_dice_cldice(_ffi.ptr(prob), _ffi.ptr(gt), B, X, Y, Z, fn.iter, fn.alpha,
+                                                      fn.smooth, _ffi.ptr(term_loss), _ffi.ptr(dprob), _ffi.ptr(cws), st))
+        _ffi.check(_ffi.lib.sk_train_cldice_chain(_ffi.ptr(logits), _ffi.ptr(bk), B, X, Y, Z, scale_h, sigma_h, term,
+                                                  float(wt), _ffi.ptr(dprob), _ffi.ptr(term_loss), _ffi.ptr(losses),
+                                                  _ffi.ptr(dl), st))
     return losses[:4], dl
 
 
@@ -597,7 +633,9 @@ class TrainStep:
 
     Defaults are the reference's (skoots/config.py:49-64,87,96-101,144): AdamW lr 5e-4, weight decay
     1e-6, betas (0.9, 0.999), eps 1e-8; Tversky (alpha, beta, eps) = embed (0.25, 0.75, 1e-8), probability
-    (0.5, 0.5, 1e-8), skeleton (0.5, 1.5, 1e-8); relative weights 1; vector scaling (60, 60, 12)."""
+    (0.5, 0.5, 1e-8), skeleton (0.5, 1.5, 1e-8); relative weights 1; vector scaling (60, 60, 12).  Each of
+    ``loss_embed`` / ``loss_prob`` / ``loss_skele`` is an (alpha, beta, eps) tuple (Tversky) or a loss object,
+    ``tversky(...)`` or ``soft_dice_cldice(...)`` (e.g. ``loss.loss_from_cfg(cfg.TRAIN.LOSS_SKELETON, ...)``)."""
 
     def __init__(self, model: TrainUNet, lr: float = 5e-4, weight_decay: float = 1e-6, betas=(0.9, 0.999),
                  eps: float = 1e-8, vector_scale=(60, 60, 12),
@@ -608,7 +646,7 @@ class TrainStep:
         self.process_group = process_group
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
         self.vector_scale = [float(v) for v in vector_scale]
-        self.loss_params = [list(map(float, loss_embed)), list(map(float, loss_prob)), list(map(float, loss_skele))]
+        self.loss_params = [_loss_term(t)[1] for t in (loss_embed, loss_prob, loss_skele)]
         self.weights = [float(w) for w in weights]
         self.exp_avg = torch.zeros_like(model.flat_param)
         self.exp_avg_sq = torch.zeros_like(model.flat_param)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the training step of BASELINE.json configs[4]: random-init U-Net, synthetic 256^3 crop, batch 1.
 
-    python tools/bench_train.py [--shape 256 256 256] [--steps 3] [--warmup 1]
+    python tools/bench_train.py [--shape 256 256 256] [--steps 3] [--warmup 1] [--loss-skeleton soft_cldice]
 
 Prints one JSON line: steps/s plus the split into forward / loss / backward / optimizer (HIP events on
 the launch stream).  Not the driver's bench (bench.py measures the inference metric); this is the
@@ -23,14 +23,16 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--precision", choices=["fp32", "mixed", "bf16"], default="fp32")
+    ap.add_argument("--loss-skeleton", choices=["tversky", "soft_cldice"], default="tversky",
+                    help="the skeleton term's loss (TRAIN.LOSS_SKELETON) with the reference's default keywords")
     args = ap.parse_args()
-    from skoots_amd.train import TrainStep, TrainUNet
+    from skoots_amd.train import TrainStep, TrainUNet, soft_dice_cldice
     from skoots_amd.unet import random_state_dict
     dev = torch.device("cuda:0")
     X, Y, Z = args.shape
     B = args.batch
     model = TrainUNet(random_state_dict(), dev, precision=args.precision)
-    step = TrainStep(model)
+    step = TrainStep(model) if args.loss_skeleton == "tversky" else TrainStep(model, loss_skele=soft_dice_cldice())
     gen = torch.Generator(device=dev).manual_seed(1)
     images = torch.randn((B, 1, X, Y, Z), device=dev, generator=gen)
     gx = torch.arange(X, device=dev).view(X, 1, 1)
@@ -74,7 +76,9 @@ def main():
     phases = [sum(e[i].elapsed_time(e[i + 1]) for e in rec) / len(rec) for i in range(4)]
     print(json.dumps({"metric": "train_steps_per_s", "value": round(1000.0 / ms, 4), "unit": "steps/s",
                       "ms_per_step": round(ms, 2), "dtype": {"fp32": "f32", "mixed": "f16 operands / f32 accumulate + master", "bf16": "bf16 operands / f32 accumulate + master"}[args.precision], "data": "synthetic",
-                      "config": {"workload": f"{X}x{Y}x{Z} crop, batch {B}, random-init U-Net, 3 Tversky terms, AdamW"},
+                      "config": {"workload": f"{X}x{Y}x{Z} crop, batch {B}, random-init U-Net, "
+                                           + ("3 Tversky terms" if args.loss_skeleton == "tversky" else
+                                              "2 Tversky terms + soft clDice skeleton term (iter_ 3)") + ", AdamW"},
                       "phase_ms": {"forward": round(phases[0], 2), "loss": round(phases[1], 2),
                                    "backward": round(phases[2], 2), "optimizer": round(phases[3], 2)},
                       "losses": [round(float(v), 6) for v in losses.cpu()],
