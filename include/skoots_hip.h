@@ -612,6 +612,48 @@ int sk_average_baked_skeletons(const float* baked, float* out, int C, int X, int
                                void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Training-crop augmentation (skoots/train/merged_transform.py:402-762, TransformFromCfg).
+ *
+ * sk_aug_resample: one gather over the crop-2 output (w2, h2, d2) that composes, for each output voxel, the flips,
+ * the crop-2 origin (in the crop-1 window of extents (w1, h1, d1)), the per-z-slice inverse affine (torchvision's
+ * rescaled theta: theta[0..2] = the grid's x row, [3..5] its y row; nearest, align_corners False, 0 outside the
+ * slice), the elastic map (field (1, 3, field_d, field_h, field_w) fp32 on the device, interpolated trilinearly to
+ * (w1, h1, d1) on the fly and scaled by magnitude = (z, y, x); nearest, align_corners True, 0 outside) and the
+ * crop-1 origin in the source (1, src_x, src_y, src_z).  image uint8 / fp16 / fp32 (SK_U8 / SK_F16 / SK_F32), masks
+ * uint8 / int16 / int32 (SK_U8 / SK_I16 / SK_I32), both contiguous; out_image fp32 and out_masks int32, (w2, h2, d2)
+ * contiguous.  invert (255 - v) and brightness (clamp(v + brightness_val, 0, 255)) are applied in the same pass,
+ * which also leaves the per-z partial sums of out_image / 255 in the workspace (sk_aug_workspace_bytes).
+ *
+ * sk_aug_intensity (two launches, in place on out_image, same workspace): contrast blend + clamp with one mean per
+ * z-slice (contrast != 0), + noise * noise_gamma (noise (w2, h2, d2) fp32 or NULL), then (v - mean) / std where
+ * own_mean / own_std ask for the image's mean / unbiased std instead of the given values.  Reductions run in a fixed
+ * order without atomics.
+ *
+ * sk_skeleton_to_mask: out (X, Y, Z) fp32 = 1 at trunc(point + offset) for every point (n_points, 3) fp32 and every
+ * row of the offset table (n_offsets, 3) int32 that lands inside, 0 elsewhere.  Every check runs before any write. */
+typedef struct {
+    int src_x, src_y, src_z;
+    int c1_x0, c1_y0, c1_z0, w1, h1, d1;
+    int c2_x0, c2_y0, c2_z0, w2, h2, d2;
+    int flip_x, flip_y, flip_z;
+    int affine;
+    float theta[6];
+    int elastic, field_d, field_h, field_w;
+    float magnitude[3];
+    int invert, brightness;
+    float brightness_val;
+} sk_aug_params;
+size_t sk_aug_workspace_bytes(int w2, int h2, int d2);
+int sk_aug_resample(const sk_aug_params* params, const void* image, int image_dtype, const void* masks,
+                    int masks_dtype, const float* field, float* out_image, int32_t* out_masks, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int sk_aug_intensity(float* image, int w2, int h2, int d2, int contrast, float contrast_val, const float* noise,
+                     float noise_gamma, int own_mean, float mean, int own_std, float std_value, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int sk_skeleton_to_mask(const float* points, int64_t n_points, const int32_t* offsets, int n_offsets, int X, int Y,
+                        int Z, float* out, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Validation metrics (skoots/validate/lib.py:190-229 mask_iou): iou (N, M) fp32 of the N
  * ground-truth and M predicted instances, intersection / union of voxel counts, 0 for pairs that do not touch.
  * gt, pred (n) int32; lut_gt (max_gt + 1) / lut_pred (max_pred + 1) int32 map an id to its 1-based row / column

@@ -44,6 +44,15 @@ class ConvSrc(C.Structure):
     _fields_ = [("data", vp), ("affine", vp), ("c", i32), ("upsample", i32)]
 
 
+class AugParams(C.Structure):
+    """sk_aug_params (include/skoots_hip.h)."""
+    _fields_ = [(n, i32) for n in ("src_x", "src_y", "src_z", "c1_x0", "c1_y0", "c1_z0", "w1", "h1", "d1",
+                                   "c2_x0", "c2_y0", "c2_z0", "w2", "h2", "d2", "flip_x", "flip_y", "flip_z",
+                                   "affine")] + \
+               [("theta", f32 * 6)] + [(n, i32) for n in ("elastic", "field_d", "field_h", "field_w")] + \
+               [("magnitude", f32 * 3), ("invert", i32), ("brightness", i32), ("brightness_val", f32)]
+
+
 _SIGS = {
     "sk_last_error": (C.c_char_p, []),
     "sk_abi_version": (i32, []),
@@ -149,6 +158,10 @@ _SIGS = {
     "sk_train_stem_wgrad_f16": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "sk_bake_skeleton": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, fp, vp, vp, vp]),
     "sk_average_baked_skeletons": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "sk_aug_workspace_bytes": (sz, [i32, i32, i32]),
+    "sk_aug_resample": (i32, [C.POINTER(AugParams), vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "sk_aug_intensity": (i32, [vp, i32, i32, i32, i32, f32, vp, f32, i32, f32, i32, f32, vp, sz, vp]),
+    "sk_skeleton_to_mask": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, vp]),
     "sk_mask_iou_workspace_bytes": (sz, [i32, i32]),
     "sk_mask_iou": (i32, [vp, vp, i64, vp, i32, i32, vp, i32, i32, vp, vp, sz, vp]),
     "sk_train_adamw": (i32, [vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]),

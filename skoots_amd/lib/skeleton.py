@@ -1,7 +1,12 @@
-"""``skoots.lib.skeleton.index_skeleton_by_embed`` on the MI355X
-(reference: skoots/lib/skeleton.py:656-695)."""
+"""``skoots.lib.skeleton`` on the MI355X: index_skeleton_by_embed (reference: skoots/lib/skeleton.py:656-695),
+bake_skeleton / average_baked_skeletons (:18-48, :448-528) and skeleton_to_mask (:531-593 with
+skoots/lib/utils.py:422-438)."""
 from __future__ import annotations
 
+from functools import lru_cache
+from typing import Dict, Tuple
+
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -82,3 +87,51 @@ def bake_skeleton(masks: Tensor, skeletons, anisotropy=(1.0, 1.0, 1.0), average:
     if average:
         baked = average_baked_skeletons(baked.unsqueeze(0)).squeeze(0)
     return (baked, dist) if return_distance else baked
+
+
+def _disk(radius: int) -> np.ndarray:
+    """skimage.morphology.disk(radius): x^2 + y^2 <= r^2 over [-r, r]^2, uint8."""
+    r = np.arange(-radius, radius + 1)
+    xx, yy = np.meshgrid(r, r)
+    return (xx ** 2 + yy ** 2 <= radius ** 2).astype(np.uint8)
+
+
+@lru_cache()
+def get_cached_disk_coords(device, radius: int = 7, flank_radius: int = 3) -> Tensor:
+    """Offsets (3, K) int64 of the skeleton-mask stamp (skoots/lib/utils.py:422-438): a disk of ``radius`` in the
+    point's z-slice and disks of ``flank_radius`` in the slices above and below, in torch.nonzero order.  x and y
+    are shifted by ``radius // 2``, not by ``radius``, exactly as the reference does (DESIGN.md section 11)."""
+    center = _disk(radius)
+    flank = _disk(flank_radius)
+    pad = (center.shape[0] - flank.shape[0]) // 2
+    flank = np.pad(flank, ((pad, pad), (pad, pad)))
+    nz = np.argwhere(np.stack((flank, center, flank), axis=-1))   # row-major, as torch.nonzero
+    nz[:, 2] -= 1
+    nz[:, :2] -= radius // 2
+    return torch.from_numpy(nz.astype(np.int64)).to(device).T
+
+
+@lru_cache()
+def _disk_offsets_i32(device, radius: int, flank_radius: int) -> Tensor:
+    return get_cached_disk_coords(device, radius, flank_radius).T.to(torch.int32).contiguous()
+
+
+def skeleton_to_mask(skeletons: Dict[int, Tensor], shape: Tuple[int, int, int], device=None, radius: int = 7,
+                     flank_radius: int = 3) -> Tensor:
+    """(1, X, Y, Z) fp32 {0, 1} mask: 1 at trunc(point + offset) for every skeleton point and every offset of
+    ``get_cached_disk_coords(radius, flank_radius)`` that lands inside ``shape`` (skoots/lib/skeleton.py:531-593).
+    Points are taken as fp32.  A ``-1`` key or an empty dict gives zeros.  One HIP launch over all points."""
+    X, Y, Z = (int(s) for s in shape)
+    if device is None:
+        device = next(iter(skeletons.values())).device if skeletons and -1 not in skeletons else "cuda"
+    device = torch.device(device)
+    out = torch.zeros((1, X, Y, Z), dtype=torch.float32, device=device)
+    _ffi.require_gpu(out, "skeleton mask")
+    if -1 in skeletons or not skeletons:
+        return out
+    pts = torch.cat([torch.as_tensor(v).reshape(-1, 3).to(device, torch.float32) for v in skeletons.values()])
+    pts = pts.contiguous()
+    offs = _disk_offsets_i32(device, int(radius), int(flank_radius))
+    _ffi.check(_ffi.lib.sk_skeleton_to_mask(_ffi.ptr(pts), pts.shape[0], _ffi.ptr(offs), offs.shape[0], X, Y, Z,
+                                            _ffi.ptr(out), _ffi.stream_ptr(device)))
+    return out

@@ -2,3 +2,4 @@
 from .engine import TrainUNet, TrainStep, fused_loss, sync_gradients, train_step  # noqa: F401
 from .loss import LOSS_FUNCTIONS, loss_from_cfg, soft_dice_cldice, soft_skeletonize, tversky  # noqa: F401
 from .sigma import Sigma, init_sigma  # noqa: F401
+from .transforms import AugmentPlan, TransformFromCfg, draw_plan, skeleton_colate  # noqa: F401
