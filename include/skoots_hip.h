@@ -663,6 +663,32 @@ int sk_mask_iou(const int32_t* gt, const int32_t* pred, int64_t n, const int32_t
                 const int32_t* lut_pred, int max_pred, int M, float* iou, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* Dice and soft-clDice matrices (ABI 6; skoots/validate/lib.py:232-315 mask_dice / mask_soft_cldice, the metrics of
+ * skoots/validate/__main__.py).  Volumes are (1, X, Y, Z) int32 with z fastest, at most 2^31 - 1 voxels; iters in
+ * [0, 12] (the reference's soft_cldice uses 3).
+ *
+ * sk_label_soft_skeleton2d: skel (X, Y, Z) uint8 = 1 where a voxel lies on its own instance's soft skeleton
+ * (train/loss.py:295-310 on `labels == id`, 4-D branch): per (Y, Z) slice, D(u) = own-label cross-erosion depth
+ * capped at iters + 1 (in-slice 4-neighbours; out-of-slice neighbours are ignored), and u is on the skeleton iff
+ * labels(u) > 0 and no voxel of its in-slice 3x3 window has its label and D >= min(D(u), iters) + 1.
+ *
+ * sk_mask_metrics: whichever of iou / dice / cldice (N, M) fp32 is non-NULL, rows / columns as in sk_mask_iou (same
+ * luts).  One pass builds three int32 contingency tables: voxel counts, pred-skeleton counts at x >= 1 and
+ * gt-skeleton counts at x >= 1.  A pair with no common voxel (any x) is 0 in every matrix.  Otherwise
+ *   iou    = float(|A & B|) / float(|A | B|)
+ *   dice   = float(2 |A & B|) / float(|A| + |B|)
+ *   cldice = 1 - (2 (tprec tsens)) / (tprec + tsens)   (the loss, as the reference stores it), with
+ *            tprec = (float(S_p) + 1) / (float(T_p) + 1), tsens = (float(S_g) + 1) / (float(T_g) + 1);
+ *            S_p = pred-b skeleton voxels inside gt a, T_p = pred-b skeleton voxels, S_g / T_g the same for gt a,
+ *            all over x >= 1.  Bit-exact to the reference while every T is below 2^24.
+ * cldice = NULL skips the skeleton.  workspace: sk_mask_metrics_workspace_bytes(N, M); it needs
+ * (N + 1) (M + 1) <= 2^31 - 1.  Every argument is checked before the first write. */
+int sk_label_soft_skeleton2d(const int32_t* labels, int X, int Y, int Z, int iters, uint8_t* skel, void* stream);
+size_t sk_mask_metrics_workspace_bytes(int N, int M);
+int sk_mask_metrics(const int32_t* gt, const int32_t* pred, int X, int Y, int Z, const int32_t* lut_gt, int max_gt,
+                    int N, const int32_t* lut_pred, int max_pred, int M, int iters, float* iou, float* dice,
+                    float* cldice, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */

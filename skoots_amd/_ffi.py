@@ -164,6 +164,9 @@ _SIGS = {
     "sk_skeleton_to_mask": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, vp]),
     "sk_mask_iou_workspace_bytes": (sz, [i32, i32]),
     "sk_mask_iou": (i32, [vp, vp, i64, vp, i32, i32, vp, i32, i32, vp, vp, sz, vp]),
+    "sk_label_soft_skeleton2d": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "sk_mask_metrics_workspace_bytes": (sz, [i32, i32]),
+    "sk_mask_metrics": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "sk_train_adamw": (i32, [vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]),
 }
 
