@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -94,6 +95,428 @@ constexpr int kUpFrags8 = 64;    // of an upsampled chunk: [class 4][ty 2][cout 
 #include "conv3d_up_kernel.inc"
 #undef SK_UPF_NAME
 #undef SK_UPF_MIX8
+
+// ------------------------------------------------------------------------------------------
+// conv3_upf_px_kernel (round 5): the fp16 folded conv of ONE skip chunk and ONE upsampled chunk into 32 channels (dec0.0)
+// with conv3_px_kernel's plane streaming.  conv3_upf_kernel streams its weights: per step of four output planes a wave
+// issues ~106 vector-memory instructions for 560 MFMAs, 74 of them weight fragments from L2 (the folded set of a parity
+// class is 32 fragments per wave, 128 KiB per workgroup: too large to stay).  Here a workgroup computes ONE cout half
+// (grid = 2 x npatch x x-chunks x B, the two halves of a region adjacent in the XCD-aware order: the second one's planes
+// come from L2), and then every weight stays:
+//   * the wave's 16 folded fragments (class (py, pz) = w, this cout half: [tytz 4][px 2][tx 2]) in registers;
+//   * the 27 skip fragments of the cout half: tap rows 0 .. RES-1 in registers, the others in LDS (one copy per
+//     workgroup, loaded once) -- no weight load in the step loop;
+//   * a step consumes fine planes A = 2i, B = 2i + 1 and low-resolution plane i: the fine planes reach output planes
+//     A-1 .. B+1 through their x taps, and plane i's four folded (px, tx) taps land in output planes 2i-1 .. 2i+2 -- the
+//     SAME four rolling accumulator planes (4 planes x 2 voxel halves x 1 cout half = 32 registers); A-1 and A complete;
+//   * the ring: 4 fine slots + 2 low-resolution slots; the next step's planes (2 fine, 1 low-resolution) are requested at
+//     the START of the step, into the slots the step before read; one barrier per step;
+//   * uniform pair steps: an x-chunk of n planes runs n/2 + 2 steps from fine plane xa - 2; the planes outside
+//     [xa - 1, xb] (which reach no stored output plane) and outside the tile are staged as zeros (out-of-range LDS-DMA);
+//   * per step and wave 108 skip MFMAs (9 tap rows x 12) + 32 upsampled (4 tap rows x 8); the next row's LDS reads are
+//     pinned into the first MFMA gaps of the row before (conv3_px_kernel's finding).
+// x-chunks: kUpxChunks consecutive chunks of make_upf_plan per workgroup (fewer half-idle end steps and prologues); the
+// GroupNorm partials are still reduced and written per chunk of the plan -- the rows sk_conv3d_upfold_num_blocks reports,
+// in conv3_upf_kernel's summation order -- so the finalize pass and its order do not change.
+// Summation order of a voxel: by input plane (fine planes and low-resolution planes interleaved), not by tap row: fp32
+// rounding differs from conv3_upf_kernel's; bit-exact on integer operands.
+constexpr int kUpxChunks = 4;
+constexpr int kUpxResRows = 3;   // skip tap rows held in registers (36 VGPRs); the other 6 rows (18 KiB) in LDS
+constexpr int kUpxPosP = 176;    // the planes it is built for: Zl 10 (the production tile's level 0; also Zl 8) --
+constexpr int kUpxPosL = 64;     // make_upf_plan's nposp / nposl there
+
+template <int NPOSP, int NPOSL>
+constexpr size_t upx_lds_bytes() {
+    return (size_t)4 * (NPOSP + sk::kZeroPos) * kPosBytes + (size_t)2 * (NPOSL + sk::kZeroPos) * kPosBytes +
+           (size_t)(9 - kUpxResRows) * 3 * 1024 + (size_t)kUpxChunks * 4 * 8 * sizeof(float);
+}
+
+template <int NPOSP, int NPOSL>
+__global__ void __launch_bounds__(256, 2) conv3_upf_px_kernel(UpfArgs a) {
+    constexpr int RES = kUpxResRows;
+    constexpr int FS = (NPOSP + sk::kZeroPos) * kPosBytes;   // a fine plane slot (compile-time: slot offsets are immediates)
+    constexpr int LS = (NPOSL + sk::kZeroPos) * kPosBytes;   // a low-resolution plane slot
+    constexpr int kLow = 4 * FS;                             // the two low-resolution slots
+    constexpr int kWl = kLow + 2 * LS;                       // skip tap rows RES .. 8 of the cout half
+    constexpr int kRed = kWl + (9 - RES) * 3 * 1024;         // GroupNorm partials [plan chunk][wave][quad][2]
+    constexpr int zf = NPOSP * kPosBytes, zl = NPOSL * kPosBytes;   // the zero windows, behind the staged positions
+    constexpr int NDMA = NPOSP / 16, NDMAL = NPOSL / 16;
+    static_assert(!SK_ZERO_WINDOW || (zf % 256 == 0 && zl % 256 == 0), "a zero window must cover the 64 banks once");
+    static_assert(NDMA <= 4 * kMaxDma && NDMAL <= 4 * kMaxDmaL, "LDS-DMA pieces per plane");
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int py = w >> 1, pz = w & 1;   // parity class of this wave's output voxels
+    const int c16 = lane & 15, g = lane >> 4;
+
+    int blk = blockIdx.x;   // XCD-aware order (conv3d.hip); the two cout halves of a region are neighbours in it
+    {
+        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
+        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
+    }
+    const int h = blk & 1;   // cout half
+    blk >>= 1;
+    const int patch = blk % a.npatch;
+    blk /= a.npatch;
+    const int nxc2 = (a.nxc + kUpxChunks - 1) / kUpxChunks;
+    const int xc2 = blk % nxc2;
+    const int b = blk / nxc2;
+    const int nblk = a.npatch * a.nxc;
+
+    const int Zl = a.Zl, Zt = a.Zt;
+    const int yl0 = patch * a.K;
+    const int nseg = a.K * Zl;
+
+    // per-lane column flags and the store voxel: conv3_upf_kernel's
+    unsigned vflags = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int m = 16 * j + c16;
+        const int r = m / Zl, c = m - r * Zl;
+        vflags |= (unsigned)(pz == 0 && c == 0) << j;
+        vflags |= (unsigned)(pz == 1 && c == Zl - 1) << (8 + j);
+        vflags |= (unsigned)(m < nseg && yl0 + r < a.Yl) << (16 + j);
+    }
+    auto zlo = [&](int j) { return (vflags >> j) & 1u; };
+    auto zhi = [&](int j) { return (vflags >> (8 + j)) & 1u; };
+    auto vvalid = [&](int j) { return (vflags >> (16 + j)) & 1u; };
+    int ovox;
+    {
+        const int m = c16 + 16 * (g & 1);
+        const int r = m / Zl, c = m - r * Zl;
+        ovox = (m < nseg && yl0 + r < a.Yl) ? (2 * (yl0 + r) + py) * Zt + 2 * c + pz : -1;
+    }
+
+    // ---- LDS-DMA bookkeeping (conv3_upf_kernel's de-interleaved fine planes, low-resolution planes as they are) -------
+    const int d_cs = ((lane & 3) ^ (((lane >> 4) & 1) << 1)) * 16;
+    int d_vox[kMaxDma], d_low[kMaxDmaL];   // BYTE offsets of this lane's pieces in a plane, -1: outside the tile
+#pragma unroll
+    for (int k = 0; k < kMaxDma; ++k) {
+        const int t = w + 4 * k;
+        const int q = (64 * t + lane) >> 2;
+        const int sub = q / a.SUBP, rem = q - sub * a.SUBP - 1;
+        const int ylr = rem >= 0 ? rem / Zl : 0, zl_ = rem - ylr * Zl;
+        const int yp = sub >> 1, zp = sub & 1;
+        const int y = 2 * (yl0 - yp + ylr) + yp, z = 2 * zl_ + zp;
+        const bool ok = t < NDMA && sub < 4 && rem >= 0 && ylr <= a.K && y >= 0 && y < a.Yt;
+        d_vox[k] = ok ? (y * Zt + z) * kPosBytes + d_cs : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxDmaL; ++k) {
+        const int t = w + 4 * k;
+        const int q = (64 * t + lane) >> 2;
+        const int rem = q - 1;
+        const int ylr = rem >= 0 ? rem / Zl : 0, zl_ = rem - ylr * Zl;
+        const int yl = yl0 - 1 + ylr;
+        const bool ok = t < NDMAL && rem >= 0 && ylr < a.K + 2 && yl >= 0 && yl < a.Yl;
+        d_low[k] = ok ? (yl * Zl + zl_) * kPosBytes + d_cs : -1;
+    }
+
+    const int xa = xc2 * kUpxChunks * a.XC;
+    const int xb = min(xa + kUpxChunks * a.XC, a.Xt);
+    const int Xl = a.Xt >> 1;
+    const int nsteps = (xb - xa) / 2 + 2;   // step s: fine planes xa - 2 + 2s, xa - 1 + 2s, low-resolution plane xa/2 - 1 + s
+    const long long out_plane = (long long)a.Yt * Zt * a.out_vs;
+    char* outb = a.out + (long long)b * a.Xt * out_plane;
+    const char* skipb = a.skip + (long long)b * a.skip_batch;
+    const char* upb = a.up + (long long)b * a.up_batch;
+
+    // fine plane f (x = xa - 2 + f) into slot f & 3, low-resolution plane s into slot s & 1
+    auto issue_fine = [&](int f, int slot) {
+        const int x = xa - 2 + f;
+        const bool xok = x >= xa - 1 && x <= xb && x >= 0 && x < a.Xt;
+        const int xs = min(max(x, 0), a.Xt - 1);
+        const __amdgpu_buffer_rsrc_t rsrc = sk::make_rsrc(skipb + (long long)xs * a.skip_plane, (unsigned)a.skip_plane);
+        char* lbase = lds + slot * FS;
+#pragma unroll
+        for (int k = 0; k < kMaxDma; ++k) {
+            const int t = w + 4 * k;
+            if (t < NDMA) {
+                const unsigned voff = (xok && d_vox[k] >= 0) ? (unsigned)d_vox[k] : sk::kOob;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lbase + t * 1024), 16, voff, 0, 0, 0);
+            }
+        }
+    };
+    auto issue_low = [&](int s, int slot) {
+        const int xl = (xa >> 1) - 1 + s;
+        const bool xok = xl >= 0 && xl < Xl;
+        const int xs = min(max(xl, 0), Xl - 1);
+        const __amdgpu_buffer_rsrc_t rsrc = sk::make_rsrc(upb + (long long)xs * a.up_plane, (unsigned)a.up_plane);
+        char* lbase = lds + kLow + slot * LS;
+#pragma unroll
+        for (int k = 0; k < kMaxDmaL; ++k) {
+            const int t = w + 4 * k;
+            if (t < NDMAL) {
+                const unsigned voff = (xok && d_low[k] >= 0) ? (unsigned)d_low[k] : sk::kOob;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lbase + t * 1024), 16, voff, 0, 0, 0);
+            }
+        }
+    };
+
+    // ---- weights: loaded once --------------------------------------------------------------------------------------
+    // skip fragment (tap row r, cout half h, x tap d): ((r * 2 + h) * 3 + d) KiB; folded fragment of (class w, tap row tytz,
+    // cout half h, px, tx): kSkipFrags + w * 32 + tytz * 8 + h * 4 + px * 2 + tx
+    const __amdgpu_buffer_rsrc_t wrsrc = sk::make_rsrc(a.wpk, (unsigned)((kSkipFrags + kUpFrags) * 1024));
+    auto wload = [&](int frag) {
+        return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, frag * 1024, 0));
+    };
+    half8 wres[RES][3];
+#pragma unroll
+    for (int r = 0; r < RES; ++r)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) wres[r][d] = wload((r * 2 + h) * 3 + d);
+    half8 wup[4][2][2];   // [tytz][px][tx]
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int px = 0; px < 2; ++px)
+#pragma unroll
+            for (int tx = 0; tx < 2; ++tx) wup[t][px][tx] = wload(kSkipFrags + w * 32 + t * 8 + h * 4 + px * 2 + tx);
+    for (int i = tid; i < (9 - RES) * 3 * 64; i += 256) {
+        const int r = RES + i / 192, e = i % 192;
+        *reinterpret_cast<uint4*>(lds + kWl + i * 16) = *reinterpret_cast<const uint4*>(a.wpk + (r * 2 + h) * 3 * 1024 + e * 16);
+    }
+    if (tid < 6 * 4 * sk::kZeroPos) {
+        const int sl = tid / (4 * sk::kZeroPos), e = tid % (4 * sk::kZeroPos);
+        char* zp = sl < 4 ? lds + sl * FS + zf : lds + kLow + (sl - 4) * LS + zl;
+        *reinterpret_cast<uint4*>(zp + e * 16) = make_uint4(0, 0, 0, 0);
+    }
+    issue_fine(0, 0);
+    issue_fine(1, 1);
+    issue_low(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // ---- accumulators and tap addresses --------------------------------------------------------------------------------
+    // element r of [j]: cout 16 h + 4 g + r, column 16 j + c16 of the wave's segment
+    const f32x4 bias4 = *reinterpret_cast<const f32x4*>(a.bias + 16 * h + 4 * g);
+    f32x4 P0[2], P1[2], Q0[2], Q1[2];
+    auto reset = [&](f32x4 (&o)[2]) { o[0] = o[1] = bias4; };
+    reset(P0);
+    reset(P1);
+    reset(Q0);
+    reset(Q1);
+    float gsum = 0.0f, gsq = 0.0f;
+
+    // fine plane, tap row dydz of the wave's class (conv3_upf_kernel's load_body)
+    auto saddr = [&](int dydz, int j) {
+        const int dy = dydz / 3 - 1, dz = dydz % 3 - 1;
+        const int Y = py + dy, Z = pz + dz;
+        const int tapoff = ((Y & 1) * 2 + (Z & 1)) * a.SUBP + 1 + (Y >= 1 ? Zl : 0) + (Z >> 1);
+        const int q = c16 + tapoff;
+        int addr = (q * 4 + (g ^ (((q >> 2) & 1) << 1))) * 16 + 1024 * j;
+        if (dz < 0) addr = zlo(j) ? sk::zero_of(zf, addr) : addr;
+        if (dz > 0) addr = zhi(j) ? sk::zero_of(zf, addr) : addr;
+        return addr;
+    };
+    // low-resolution plane, folded tap row tytz (conv3_upf_kernel's load_low)
+    auto laddr = [&](int tytz, int j) {
+        const int sy = (tytz >> 1) + py - 1, sz = (tytz & 1) + pz - 1;
+        const int q = c16 + 1 + (1 + sy) * Zl + sz;
+        int addr = (q * 4 + (g ^ (((q >> 2) & 1) << 1))) * 16 + 1024 * j;
+        addr = (sz < 0 && zlo(j)) ? sk::zero_of(zl, addr) : addr;
+        addr = (sz > 0 && zhi(j)) ? sk::zero_of(zl, addr) : addr;
+        return addr;
+    };
+
+    // A step over fine planes A (slot sA), B = A + 1 (slot sA + 1) and low-resolution plane A / 2 (slot sL).  oA1 / oA / oB /
+    // oB1: the accumulators of output planes A-1, A, B, B+1.
+    auto pair_step = [&](auto SA, auto SL, f32x4 (&oA1)[2], f32x4 (&oA)[2], f32x4 (&oB)[2], f32x4 (&oB1)[2]) {
+        const char* pa = lds + decltype(SA)::value * FS;
+        const char* pb = pa + FS;
+        const char* pl = lds + kLow + decltype(SL)::value * LS;
+        const char* wl = lds + kWl + lane * 16;
+        half8 bq[2][2][2];   // [buffer][plane][j]: the B fragments of a skip tap row, one row ahead
+        half8 wq[2][3];      // [buffer][d]: the weight fragments of a skip tap row, one row ahead
+        half8 bl[2][2];      // [buffer][j]: the B fragments of a folded tap row
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int ad = saddr(0, j);
+            bq[0][0][j] = *reinterpret_cast<const half8*>(pa + ad);
+            bq[0][1][j] = *reinterpret_cast<const half8*>(pb + ad);
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) wq[0][d] = wres[0][d];
+        // skip: 9 tap rows of 12 MFMAs; the reads of row r + 1 (its weights when they live in LDS, then its four B fragments;
+        // after row 8 the B fragments of the first folded row) in the first MFMA gaps of row r, in consumption order
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+            const half8(&W)[3] = wq[r & 1];
+            const int nr = r + 1;
+            const bool wread = nr < 9 && nr >= RES;
+            if (nr < 9 && !wread) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) wq[nr & 1][d] = wres[nr][d];
+            }
+            auto next_read = [&](int k) {
+                if (nr == 9) {   // B fragments of folded row 0
+                    bl[0][k] = *reinterpret_cast<const half8*>(pl + laddr(0, k));
+                    return;
+                }
+                const char* wp = wl + (nr - RES) * 3 * 1024;
+                int kk = k;   // W0, A0, B0, W1, W2, A1, B1
+                if (!wread) kk = (k == 0 ? 1 : k == 1 ? 2 : k == 2 ? 5 : 6);
+                switch (kk) {
+                    case 0: wq[nr & 1][0] = *reinterpret_cast<const half8*>(wp); break;
+                    case 1: bq[nr & 1][0][0] = *reinterpret_cast<const half8*>(pa + saddr(nr, 0)); break;
+                    case 2: bq[nr & 1][1][0] = *reinterpret_cast<const half8*>(pb + saddr(nr, 0)); break;
+                    case 3: wq[nr & 1][1] = *reinterpret_cast<const half8*>(wp + 1024); break;
+                    case 4: wq[nr & 1][2] = *reinterpret_cast<const half8*>(wp + 2048); break;
+                    case 5: bq[nr & 1][0][1] = *reinterpret_cast<const half8*>(pa + saddr(nr, 1)); break;
+                    default: bq[nr & 1][1][1] = *reinterpret_cast<const half8*>(pb + saddr(nr, 1)); break;
+                }
+            };
+            const int nreads = nr == 9 ? 2 : (wread ? 7 : 4);
+#pragma unroll
+            for (int m = 0; m < 12; ++m) {
+                const int j = m / 6;
+                const half8 fa = bq[r & 1][0][j], fb = bq[r & 1][1][j];
+                switch (m % 6) {   // tap d of a weight row multiplies x_in = x_out + d - 1
+                    case 0: oB[j] = SK_MFMA_16x16x32_T16(W[0], fa, oB[j], 0, 0, 0); break;
+                    case 1: oB1[j] = SK_MFMA_16x16x32_T16(W[0], fb, oB1[j], 0, 0, 0); break;
+                    case 2: oA[j] = SK_MFMA_16x16x32_T16(W[1], fa, oA[j], 0, 0, 0); break;
+                    case 3: oA1[j] = SK_MFMA_16x16x32_T16(W[2], fa, oA1[j], 0, 0, 0); break;
+                    case 4: oB[j] = SK_MFMA_16x16x32_T16(W[1], fb, oB[j], 0, 0, 0); break;
+                    default: oA[j] = SK_MFMA_16x16x32_T16(W[2], fb, oA[j], 0, 0, 0); break;
+                }
+                if (m < nreads) next_read(m);
+                if (m <= nreads) __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // upsampled: 4 folded tap rows of 8 MFMAs.  Output plane A-1 (px 1) reads this plane through tx 1, A (px 0) through
+        // tx 1, B (px 1) through tx 0, B+1 (px 0) through tx 0.
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int nreads = t < 3 ? 2 : 0;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int j = m / 4;
+                const half8 f = bl[t & 1][j];
+                switch (m % 4) {
+                    case 0: oA1[j] = SK_MFMA_16x16x32_T16(wup[t][1][1], f, oA1[j], 0, 0, 0); break;
+                    case 1: oA[j] = SK_MFMA_16x16x32_T16(wup[t][0][1], f, oA[j], 0, 0, 0); break;
+                    case 2: oB[j] = SK_MFMA_16x16x32_T16(wup[t][1][0], f, oB[j], 0, 0, 0); break;
+                    default: oB1[j] = SK_MFMA_16x16x32_T16(wup[t][0][0], f, oB1[j], 0, 0, 0); break;
+                }
+                if (m < nreads) bl[(t + 1) & 1][m] = *reinterpret_cast<const half8*>(pl + laddr(t + 1, m));
+                if (m <= nreads) __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
+    // ---- epilogue: raw fp16 store of a finished plane + its GroupNorm sums (conv3_upf_kernel's, one cout half) ----------
+    // Always two stores per step (a plane outside [xa, xb) stores to an out-of-range offset: dropped): the counted wait
+    // below relies on it.
+    auto finish_plane = [&](f32x4 (&o)[2], int x) {
+        const bool st = x >= xa && x < xb;   // wave-uniform
+        const int xs = min(max(x, 0), a.Xt - 1);
+        const __amdgpu_buffer_rsrc_t rout = sk::make_rsrc(outb + (long long)xs * out_plane, (unsigned)out_plane);
+        unsigned d[2][2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const f32x4 r = o[j];
+            const half4 hv = {(t16)r[0], (t16)r[1], (t16)r[2], (t16)r[3]};
+            const uint2 u = __builtin_bit_cast(uint2, hv);
+            d[j][0] = u.x;
+            d[j][1] = u.y;
+            const bool in = st && vvalid(j);
+            const t16x2 z2 = {(t16)0.0f, (t16)0.0f}, one2 = {(t16)1.0f, (t16)1.0f};
+            const t16x2 lo2 = in ? t16x2{hv[0], hv[1]} : z2, hi2 = in ? t16x2{hv[2], hv[3]} : z2;
+            gsum = SK_DOT2_T16(lo2, one2, gsum);
+            gsum = SK_DOT2_T16(hi2, one2, gsum);
+            gsq = SK_DOT2_T16(lo2, lo2, gsq);
+            gsq = SK_DOT2_T16(hi2, hi2, gsq);
+        }
+        const auto s0 = __builtin_amdgcn_permlane16_swap(d[0][0], d[1][0], false, false);
+        const auto s1 = __builtin_amdgcn_permlane16_swap(d[0][1], d[1][1], false, false);
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 lv = {s0[0], s1[0], s0[1], s1[1]};   // channels 16 h + 8 (g >> 1) .. +7 of column c16 + 16 (g & 1)
+        const unsigned off = (unsigned)(ovox * a.out_vs + a.cout_off * 2 + 32 * h + 16 * (g >> 1));
+        __builtin_amdgcn_raw_buffer_store_b128(lv, rout, (st && ovox >= 0) ? off : sk::kOob, 0, 0);
+    };
+    // GroupNorm partials of plan chunk u: this wave's share, reduced over the 16 lanes of a quad (conv3_upf_kernel's order)
+    float* red = reinterpret_cast<float*>(lds + kRed);
+    auto flush = [&](int u) {
+        float s = gsum, ss = gsq;
+#pragma unroll
+        for (int m = 8; m > 0; m >>= 1) {
+            s += __shfl_xor(s, m);
+            ss += __shfl_xor(ss, m);
+        }
+        if (c16 == 0) {
+            red[((u * 4 + w) * 4 + g) * 2 + 0] = s;
+            red[((u * 4 + w) * 4 + g) * 2 + 1] = ss;
+        }
+        gsum = gsq = 0.0f;
+    };
+    int xnext = xa + a.XC, unext = 0;   // the next boundary between two plan chunks, the chunk it closes
+    auto end_step = [&](int s, f32x4 (&oA1)[2], f32x4 (&oA)[2]) {
+        const int xA = xa - 2 + 2 * s;
+        finish_plane(oA1, xA - 1);
+        if (xA == xnext && xA < xb) {
+            flush(unext);
+            ++unext;
+            xnext += a.XC;
+        }
+        finish_plane(oA, xA);
+        reset(oA1);
+        reset(oA);
+        // vmcnt retires in order: the step's LDS-DMA (older than its two stores) has landed
+        asm volatile("s_waitcnt vmcnt(2)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    };
+
+    typedef std::integral_constant<int, 0> S0_;
+    typedef std::integral_constant<int, 1> S1_;
+    typedef std::integral_constant<int, 2> S2_;
+    // Steps alternate between two fixed role assignments: even steps read fine slots (0, 1) and low slot 0 with (P0, P1, Q0,
+    // Q1) = output planes (A-1, A, B, B+1); odd steps fine slots (2, 3), low slot 1, the pairs P / Q swapped.
+    int s = 0;
+    auto even_step = [&]() {
+        if (s + 1 < nsteps) {
+            issue_fine(2 * s + 2, 2);
+            issue_fine(2 * s + 3, 3);
+            issue_low(s + 1, 1);
+        }
+        pair_step(S0_{}, S0_{}, P0, P1, Q0, Q1);
+        end_step(s, P0, P1);
+        ++s;
+    };
+    auto odd_step = [&]() {
+        if (s + 1 < nsteps) {
+            issue_fine(2 * s + 2, 0);
+            issue_fine(2 * s + 3, 1);
+            issue_low(s + 1, 0);
+        }
+        pair_step(S2_{}, S1_{}, Q0, Q1, P0, P1);
+        end_step(s, Q0, Q1);
+        ++s;
+    };
+    while (s + 1 < nsteps) {
+        even_step();
+        odd_step();
+    }
+    if (s < nsteps) even_step();
+    flush(unext);
+
+    // ---- one partial row per plan chunk: the four waves' shares in wave order ---------------------------------------------
+    if (a.partial) {
+        __syncthreads();
+        if (tid < kUpxChunks * 8) {
+            const int u = tid >> 3, k = tid & 7;
+            const int xo = xc2 * kUpxChunks + u;
+            if (xo < a.nxc) {
+                float t = 0.0f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t += red[(u * 4 + q) * 8 + k];
+                a.partial[((long long)b * nblk + xo * a.npatch + patch) * a.pstride + a.poff + 8 * h + k] = t;
+            }
+        }
+    }
+}
 
 struct UpfPlan {
     int K, SUBP, nposp, nposl, npatch, XC, nxc;
@@ -317,6 +740,21 @@ static int upfold_impl(const void* skip, int c_skip, const void* up, int c_up, c
 #ifdef SK_TIMING
     a.dbg = sk::timing_buffer();
 #endif
+    a.out_vs = cout * 2 * lanes;
+    a.pstride = (cout / 4) * 2;
+    if (!split && !mix8 && a.ns == 1 && a.nu == 1 && cout == 32 && p.nposp == kUpxPosP && p.nposl == kUpxPosL) {
+        // the plane-streaming form (conv3_upf_px_kernel): one cout half per workgroup, kUpxChunks plan chunks along x
+        auto kern = conv3_upf_px_kernel<kUpxPosP, kUpxPosL>;
+        constexpr size_t lds = upx_lds_bytes<kUpxPosP, kUpxPosL>();
+        static_assert(lds <= 80 * 1024, "two workgroups per CU");
+        SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const unsigned grid = (unsigned)(2 * p.npatch * ((p.nxc + kUpxChunks - 1) / kUpxChunks) * B);
+        a.cout_off = 0;
+        a.poff = 0;
+        kern<<<grid, 256, lds, stream>>>(a);
+        SK_CHECK_LAUNCH();
+        return SK_OK;
+    }
     const bool wlds = !split && a.ns == 1 && p.lds + 12288 <= 80 * 1024;   // two tap rows of the single skip chunk in LDS
     auto kern = mix8 ? conv3_upf_mix8_kernel<4, false, true>
                      : (split ? conv3_upf_kernel<4, false, true> : (wlds ? conv3_upf_kernel<4, true, false> : conv3_upf_kernel<4, false, false>));
@@ -335,8 +773,6 @@ static int upfold_impl(const void* skip, int c_skip, const void* up, int c_up, c
     const unsigned grid = (unsigned)(p.npatch * p.nxc * B);
     // 32 output channels per launch (COUT 64: two launches over the same inputs -- twice the staging, but on the
     // 16x16x32 matrix instruction and at 70 instead of 108 tap-chunks; measured against conv3_kernel<64> in DESIGN.md)
-    a.out_vs = cout * 2 * lanes;
-    a.pstride = (cout / 4) * 2;
     for (int cg = 0; cg < cout / 32; ++cg) {
         a.cout_off = 32 * cg;
         a.poff = 16 * cg;
