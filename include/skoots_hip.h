@@ -654,6 +654,29 @@ int sk_skeleton_to_mask(const float* points, int64_t n_points, const int32_t* of
                         int Z, float* out, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Training skeletons (skoots/train/generate_skeletons.py:65-157 calculate_skeletons, whose per-object
+ * skimage.morphology.skeletonize(crop, method="lee") is scikit-image 0.18.3's Lee thinning): the thinning of every
+ * object in its own crop, one workgroup per object, bit for bit the sequential algorithm.
+ *
+ * boxes_host[6 i .. 6 i + 5] = (x0, y0, z0, x1, y1, z1): object i (id ids[i]) is thinned in the binary crop
+ * labels[x0:x1, y0:y1, z0:z1] == ids[i]; labels (X, Y, Z) int32.  An object whose padded crop fits the kernel's LDS
+ * (24 bytes per 32-voxel word of the padded crop, 152 KiB at most) is thinned there, a larger one in the workspace.
+ *
+ * sk_skeletonize_workspace_bytes: bytes of workspace (16-byte aligned) for these boxes; 0 if a box is empty.
+ * sk_skeletonize: counts[i] = skeleton voxels of object i, stats[2 i] = passes, stats[2 i + 1] = the most re-check
+ * rounds of one sub-iteration; *error = 0, or bit 0 (a round bound hit) / bit 1 (the pass bound hit).  The skeletons
+ * stay in the workspace for sk_skeletonize_emit.  Synchronises `stream` (the crop table is copied from the host).
+ * sk_skeletonize_emit: points[offsets[i] ..] = the skeleton voxels of object i in raster order of its crop, as int32
+ * crop coordinates (x, y, z); offsets (n + 1) int32 is the exclusive prefix sum of counts; no row at or beyond
+ * n_points is written. */
+size_t sk_skeletonize_workspace_bytes(const int32_t* boxes_host, int n);
+int sk_skeletonize(const int32_t* labels, int X, int Y, int Z, const int32_t* ids, const int32_t* boxes_host, int n,
+                   void* workspace, size_t workspace_bytes, int32_t* counts, int32_t* stats, int32_t* error,
+                   void* stream);
+int sk_skeletonize_emit(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
+                        const int32_t* offsets, int64_t n_points, int32_t* points, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Validation metrics (skoots/validate/lib.py:190-229 mask_iou): iou (N, M) fp32 of the N
  * ground-truth and M predicted instances, intersection / union of voxel counts, 0 for pairs that do not touch.
  * gt, pred (n) int32; lut_gt (max_gt + 1) / lut_pred (max_pred + 1) int32 map an id to its 1-based row / column

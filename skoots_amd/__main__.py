@@ -1,23 +1,49 @@
 """``python -m skoots_amd --image P --pretrained-checkpoint C [--log 0-4]``: the eval flags of
-the reference CLI (skoots/__main__.py:19-46, 78-98).  Training / conversion flags are out of scope."""
+the reference CLI (skoots/__main__.py:19-46, 78-98), and ``--skeletonize-train-data PATH [--mask-filter .labels]
+[--anisotropyXY a] [--anisotropyZ b]`` (skoots/__main__.py:49-68, 101-106).  ``--convert`` is out of scope."""
 import argparse
 import glob
 import logging
 import os
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="SKOOTS (MI355X)", description="skoots parameters")
     eval_args = parser.add_argument_group("eval arguments")
-    eval_args.add_argument("--image", type=str, required=True, help="path to image (or a directory of *.tif)")
+    eval_args.add_argument("--image", type=str,
+                           help="path to image (or a directory of *.tif); required unless --skeletonize-train-data")
     eval_args.add_argument("--pretrained-checkpoint", type=str, help="path to a pretrained skoots model")
     eval_args.add_argument("--use-cached", action="store_true",
                            help="skips model evaluation and loads previously evaluated arrays")
     eval_args.add_argument("--log", type=int, default=3,
                            help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
-    args = parser.parse_args()
+    accessory_args = parser.add_argument_group("scripting arguments")
+    accessory_args.add_argument("--skeletonize-train-data",
+                                help="calculate skeletons of training data (a label TIFF or a directory of them)")
+    accessory_args.add_argument("--mask-filter", default=".labels", help="filter of mask file")
+    accessory_args.add_argument("--anisotropyXY", type=float, default=1.0, help="resample factor of x and y")
+    accessory_args.add_argument("--anisotropyZ", type=float, default=1.0, help="resample factor of z")
+    return parser
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.skeletonize_train_data is None and args.image is None:
+        parser.error("the following arguments are required: --image")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     levels = [logging.DEBUG, logging.INFO, logging.WARNING, logging.ERROR, logging.CRITICAL]
     logging.basicConfig(level=levels[args.log], format="[%(asctime)s] skoots-eval [%(levelname)s]: %(message)s")
+    if args.skeletonize_train_data is not None:
+        from skoots_amd.train.generate_skeletons import create_gt_skeletons
+        scale = (args.anisotropyXY, args.anisotropyXY, args.anisotropyZ)
+        print("skeletonizing...")
+        create_gt_skeletons(args.skeletonize_train_data, args.mask_filter, scale)
+        return
     assert args.pretrained_checkpoint is not None, (
         "Cannot evaluate SKOOTS wihtout pretrained model. --pretrained_checkpoint must not be None")
     from skoots_amd.lib.eval import eval as sk_eval

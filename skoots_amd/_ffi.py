@@ -168,6 +168,9 @@ _SIGS = {
     "sk_mask_metrics_workspace_bytes": (sz, [i32, i32]),
     "sk_mask_metrics": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "sk_train_adamw": (i32, [vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]),
+    "sk_skeletonize_workspace_bytes": (sz, [ip, i32]),
+    "sk_skeletonize": (i32, [vp, i32, i32, i32, vp, ip, i32, vp, sz, vp, vp, vp, vp]),
+    "sk_skeletonize_emit": (i32, [ip, i32, vp, sz, vp, i64, vp, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

@@ -1,0 +1,455 @@
+// Lee (1994) 3-D thinning of training masks, one workgroup per object.
+//
+// Replaces the per-object skimage.morphology.skeletonize(crop, method="lee") call of
+// skoots/train/generate_skeletons.py:65-157 (calculate_skeletons), whose thinning lives in scikit-image 0.18.3's
+// skimage/morphology/_skeletonize_3d_cy.  The result is that of the sequential algorithm, bit for bit:
+//
+//   repeat until six border directions in a row delete nothing:
+//     for d in (y-1, y+1, z+1, z-1, x+1, x-1):
+//       C = foreground voxels p (raster order) whose neighbour p + d is background, that are not endpoints (exactly
+//           one foreground 26-neighbour), are Euler invariant and are simple, all judged on the image as it is now;
+//       for p in C (raster order): if p is still simple on the CURRENT image, delete p.
+//
+// Parallel re-check.  A candidate's re-check reads only its 26 neighbours; of those only candidates that come earlier
+// in raster order can have changed, and they lie among its 13 raster-preceding neighbours.  So a candidate may be
+// decided as soon as none of those is still pending ("ready"); two ready candidates are never 26-neighbours, so one
+// round decides all ready candidates at once and reproduces the sequential result.  The earliest pending candidate is
+// always ready: rounds <= candidates, and a pass that does not end the loop deletes a voxel: passes <= voxels + 1.
+// Both bounds are enforced; a kernel that hits one sets a bit of the error word and stops that object.
+//
+// Storage.  The crop, padded by one background voxel on every side, is a bit plane: word ((x * PY + y) * WZ + wz)
+// holds the voxels z = 32 wz .. 32 wz + 31 of row (x, y), WZ = ceil(PZ / 32).  Next to it a plane of pending
+// candidates, the list of words that hold pending candidates (two, for this round and the next) and the list of
+// (word, ready bits) pairs of the round: 6 words per plane word.  An object whose 24 * W bytes fit kLdsBytes keeps all
+// of it in LDS; a larger one keeps it in a global workspace (same code, a device-scope fence at every barrier).
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kLdsBytes = 152 * 1024;  // dynamic LDS of the thinning kernel at most: 24 bytes per plane word
+constexpr int kPlanes = 6;             // img, pending, list 0, list 1, ready words, ready bits
+
+struct SkelObj {   // one object: crop origin, crop extent, where its planes live
+    int x0, y0, z0;
+    int cx, cy, cz;
+    int lds;        // 1: working planes in LDS, result copied to `off`; 0: all six planes at `off`
+    int pad;
+    long long off;  // word offset of the object's planes in the workspace (after the table)
+};
+
+// 27-bit neighbourhood code: bit 9 (dx + 1) + 3 (dy + 1) + (dz + 1)
+constexpr uint32_t nb(int dx, int dy, int dz) { return 1u << (9 * (dx + 1) + 3 * (dy + 1) + (dz + 1)); }
+constexpr uint32_t kFull = 0x7FFFFFFu;
+constexpr uint32_t kCentre = 1u << 13;
+constexpr uint32_t kK0 = 0x1249249u;  // dz = -1
+constexpr uint32_t kK2 = kK0 << 2;    // dz = +1
+constexpr uint32_t kJ0 = 0x01C0E07u;  // dy = -1
+constexpr uint32_t kJ2 = kJ0 << 6;    // dy = +1
+
+// The cells of the centre cube that other voxels share: 6 faces (1 voxel each), 12 edges (3), 8 vertices (7).
+struct CubeCells {
+    uint32_t face[6], edge[12], vert[8];
+};
+constexpr CubeCells make_cube_cells() {
+    CubeCells c{};
+    int f = 0, e = 0, v = 0;
+    for (int s = -1; s <= 1; s += 2) {
+        c.face[f++] = nb(s, 0, 0);
+        c.face[f++] = nb(0, s, 0);
+        c.face[f++] = nb(0, 0, s);
+    }
+    for (int a = -1; a <= 1; a += 2)
+        for (int b = -1; b <= 1; b += 2) {
+            c.edge[e++] = nb(a, 0, 0) | nb(0, b, 0) | nb(a, b, 0);
+            c.edge[e++] = nb(a, 0, 0) | nb(0, 0, b) | nb(a, 0, b);
+            c.edge[e++] = nb(0, a, 0) | nb(0, 0, b) | nb(0, a, b);
+        }
+    for (int a = -1; a <= 1; a += 2)
+        for (int b = -1; b <= 1; b += 2)
+            for (int d = -1; d <= 1; d += 2)
+                c.vert[v++] = nb(a, 0, 0) | nb(0, b, 0) | nb(0, 0, d) | nb(a, b, 0) | nb(a, 0, d) | nb(0, b, d) |
+                              nb(a, b, d);
+    return c;
+}
+
+// Removing the centre leaves the Euler characteristic of the neighbourhood (foreground voxels as closed unit cubes)
+// unchanged: chi drops by V - E + F - 1 over the centre cube's cells that no other foreground voxel covers.
+__device__ __forceinline__ bool euler_invariant(uint32_t n) {
+    constexpr CubeCells c = make_cube_cells();
+    int d = -1;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) d += (n & c.face[i]) == 0;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) d -= (n & c.edge[i]) == 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) d += (n & c.vert[i]) == 0;
+    return d == 0;
+}
+
+__device__ __forceinline__ uint32_t dilate26(uint32_t m) {
+    m = (m | ((m << 1) & ~kK0) | ((m >> 1) & ~kK2)) & kFull;  // bits shifted past 26 must not come back
+    m = (m | ((m << 3) & ~kJ0) | ((m >> 3) & ~kJ2)) & kFull;
+    return (m | (m << 9) | (m >> 9)) & kFull;
+}
+
+// The foreground 26-neighbours (centre excluded) form at most one 26-connected component.
+__device__ __forceinline__ bool is_simple(uint32_t n) {
+    const uint32_t fg = n & kFull & ~kCentre;
+    if (!fg) return true;
+    uint32_t comp = fg & (0u - fg);
+    for (int i = 0; i < 26; ++i) {  // a component of <= 26 voxels stops growing within 26 steps
+        const uint32_t grown = dilate26(comp) & fg;
+        if (grown == comp) break;
+        comp = grown;
+    }
+    return comp == fg;
+}
+
+// Row (x, y) around word wz as 34 bits: bit 0 = voxel 32 wz - 1, bit b + 1 = voxel 32 wz + b, bit 33 = 32 wz + 32.
+__device__ __forceinline__ uint64_t row_bits(const uint32_t* plane, int row, int wz, int WZ) {
+    const uint32_t mid = plane[row + wz];
+    const uint32_t lo = wz > 0 ? plane[row + wz - 1] : 0u;
+    const uint32_t hi = wz + 1 < WZ ? plane[row + wz + 1] : 0u;
+    return ((uint64_t)mid << 1) | (lo >> 31) | ((uint64_t)(hi & 1u) << 33);
+}
+
+// v[3 (dx + 1) + (dy + 1)] = row_bits of row (x + dx, y + dy): neighbourhood of bit b of the centre word
+__device__ __forceinline__ uint32_t gather27(const uint64_t (&v)[9], int b) {
+    uint32_t n = 0;
+#pragma unroll
+    for (int r = 0; r < 9; ++r) n |= (uint32_t)((v[r] >> b) & 7u) << (3 * r);
+    return n;
+}
+
+template <bool kLds>
+__device__ __forceinline__ void wg_barrier() {
+    if (!kLds) __threadfence();  // the planes and lists live in global memory: make this wave's stores visible
+    __syncthreads();
+}
+
+struct Counters {
+    int n[2];        // entries of list 0 / list 1
+    int nready[2];   // entries of the ready list, by round parity
+    int ncand;       // candidates of the sub-iteration
+    int changed;     // the sub-iteration deleted a voxel
+    int total;       // skeleton voxels at the end
+};
+
+template <bool kLds>
+__device__ void thin_object(const int* __restrict__ labels, int X, int Y, int Z, int id, const SkelObj& o,
+                            uint32_t* planes, int W, uint32_t* result, int* count, int* stats, int* error,
+                            Counters& s) {
+    const int PY = o.cy + 2, PZ = o.cz + 2, WZ = (PZ + 31) >> 5;
+    uint32_t* img = planes;
+    uint32_t* pend = planes + W;
+    int* list0 = (int*)(planes + 2 * W);
+    int* list1 = (int*)(planes + 3 * W);
+    int* rword = (int*)(planes + 4 * W);
+    uint32_t* rbits = planes + 5 * W;
+    const int tid = threadIdx.x;
+
+    // binary crop [x0, x0 + cx) x [y0, y0 + cy) x [z0, z0 + cz) of `labels == id`, padded
+    for (int w = tid; w < W; w += kThreads) {
+        const int wz = w % WZ, t = w / WZ, y = t % PY, x = t / PY;
+        uint32_t bits = 0;
+        if (x >= 1 && x <= o.cx && y >= 1 && y <= o.cy) {
+            const int* src = labels + ((long long)(o.x0 + x - 1) * Y + (o.y0 + y - 1)) * Z + o.z0;
+            const int zlo = max(32 * wz, 1), zhi = min(32 * wz + 31, o.cz);
+            for (int z = zlo; z <= zhi; ++z) bits |= (uint32_t)(src[z - 1] == id) << (z - 32 * wz);
+        }
+        img[w] = bits;
+        pend[w] = 0u;
+    }
+    const int pass_limit = o.cx * o.cy * o.cz + 1;
+    int passes = 0, max_rounds = 0, failed = 0;
+    for (;;) {
+        if (passes >= pass_limit) {
+            failed = 2;
+            break;
+        }
+        ++passes;
+        int unchanged = 0;
+        for (int dir = 0; dir < 6 && !failed; ++dir) {
+            wg_barrier<kLds>();
+            if (tid == 0) {
+                s.n[0] = s.n[1] = 0;
+                s.nready[0] = s.nready[1] = 0;
+                s.ncand = 0;
+                s.changed = 0;
+            }
+            wg_barrier<kLds>();
+            // candidates, judged on the image at the start of the sub-iteration
+            // border directions in skimage's order 4, 3, 2, 1, 5, 6: y-1, y+1, z+1, z-1, x+1, x-1
+            const int dx = dir == 4 ? 1 : dir == 5 ? -1 : 0;
+            const int dy = dir == 0 ? -1 : dir == 1 ? 1 : 0;
+            const int dz = dir == 2 ? 1 : dir == 3 ? -1 : 0;
+            for (int w = tid; w < W; w += kThreads) {
+                const uint32_t cur = img[w];
+                if (!cur) continue;  // pad rows are all zero
+                const int wz = w % WZ, t = w / WZ, y = t % PY, x = t / PY;
+                uint64_t v[9];
+#pragma unroll
+                for (int r = 0; r < 9; ++r) v[r] = row_bits(img, ((x + r / 3 - 1) * PY + (y + r % 3 - 1)) * WZ, wz, WZ);
+                const uint64_t nrow = dx < 0 ? v[1] : dx > 0 ? v[7] : dy < 0 ? v[3] : dy > 0 ? v[5] : v[4];
+                const uint32_t across = (uint32_t)(nrow >> (1 + dz));  // voxel p + d of every bit
+                uint32_t border = cur & ~across;
+                uint32_t cand = 0;
+                while (border) {
+                    const int b = __builtin_ctz(border);
+                    border &= border - 1;
+                    const uint32_t n = gather27(v, b);
+                    if (__builtin_popcount(n & ~kCentre) == 1) continue;  // endpoint
+                    if (!euler_invariant(n) || !is_simple(n)) continue;
+                    cand |= 1u << b;
+                }
+                if (cand) {
+                    pend[w] = cand;
+                    list0[atomicAdd(&s.n[0], 1)] = w;
+                    atomicAdd(&s.ncand, __builtin_popcount(cand));
+                }
+            }
+            wg_barrier<kLds>();
+            int nlist = s.n[0];
+            const int ncand = s.ncand;
+            int round = 0;
+            while (nlist > 0) {
+                if (round >= ncand) {  // impossible: every round decides the earliest pending candidate
+                    failed = 1;
+                    break;
+                }
+                const int cur = round & 1, nxt = cur ^ 1;
+                const int* from = cur ? list1 : list0;
+                int* to = cur ? list0 : list1;
+                // ready = pending candidates none of whose 13 raster-preceding neighbours is pending
+                for (int i = tid; i < nlist; i += kThreads) {
+                    const int w = from[i];
+                    const uint32_t p = pend[w];
+                    const int wz = w % WZ, t = w / WZ, y = t % PY, x = t / PY;
+                    uint64_t blocked64 = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {  // rows (x-1, y-1), (x-1, y), (x-1, y+1), (x, y-1): z-1, z, z+1
+                        const int rx = r < 3 ? x - 1 : x, ry = r < 3 ? y + r - 1 : y - 1;
+                        const uint64_t q = row_bits(pend, (rx * PY + ry) * WZ, wz, WZ);
+                        blocked64 |= q | (q >> 1) | (q >> 2);
+                    }
+                    blocked64 |= row_bits(pend, (x * PY + y) * WZ, wz, WZ);  // (x, y, z-1)
+                    const uint32_t ready = p & ~(uint32_t)blocked64;
+                    if (ready) {
+                        const int j = atomicAdd(&s.nready[cur], 1);
+                        rword[j] = w;
+                        rbits[j] = ready;
+                    }
+                    if (p & ~ready) to[atomicAdd(&s.n[nxt], 1)] = w;
+                }
+                wg_barrier<kLds>();
+                const int nready = s.nready[cur];
+                const int nlist_next = s.n[nxt];
+                if (tid == 0) {  // read last round (before its second barrier); written again next round
+                    s.nready[nxt] = 0;
+                    s.n[cur] = 0;
+                }
+                // decide the ready candidates on the current image; none of them is a neighbour of another
+                for (int j = tid; j < nready; j += kThreads) {
+                    const int w = rword[j];
+                    const uint32_t ready = rbits[j];
+                    const int wz = w % WZ, t = w / WZ, y = t % PY, x = t / PY;
+                    uint64_t v[9];
+#pragma unroll
+                    for (int r = 0; r < 9; ++r)
+                        v[r] = row_bits(img, ((x + r / 3 - 1) * PY + (y + r % 3 - 1)) * WZ, wz, WZ);
+                    uint32_t del = 0, rb = ready;
+                    while (rb) {
+                        const int b = __builtin_ctz(rb);
+                        rb &= rb - 1;
+                        if (is_simple(gather27(v, b))) del |= 1u << b;
+                    }
+                    if (del) {
+                        img[w] = img[w] & ~del;  // the only writer of word w this round
+                        s.changed = 1;
+                    }
+                    pend[w] = pend[w] & ~ready;
+                }
+                wg_barrier<kLds>();
+                nlist = nlist_next;
+                ++round;
+            }
+            max_rounds = max(max_rounds, round);
+            if (failed) break;
+            wg_barrier<kLds>();
+            unchanged += s.changed == 0;
+        }
+        if (failed || unchanged == 6) break;
+    }
+    wg_barrier<kLds>();
+    if (tid == 0) s.total = 0;
+    wg_barrier<kLds>();
+    int mine = 0;
+    for (int w = tid; w < W; w += kThreads) {
+        const uint32_t bits = img[w];
+        if (kLds) result[w] = bits;
+        mine += __builtin_popcount(bits);
+    }
+    if (mine) atomicAdd(&s.total, mine);
+    wg_barrier<kLds>();
+    if (tid == 0) {
+        *count = s.total;
+        stats[0] = passes;
+        stats[1] = max_rounds;
+        if (failed) atomicOr(error, failed);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) thin_kernel(const int* __restrict__ labels, int X, int Y, int Z,
+                                                        const int* __restrict__ ids, const SkelObj* __restrict__ objs,
+                                                        uint32_t* __restrict__ work, int* __restrict__ counts,
+                                                        int* __restrict__ stats, int* __restrict__ error) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_planes[];
+    __shared__ Counters s;
+    const int i = blockIdx.x;
+    const SkelObj o = objs[i];
+    const int W = (o.cx + 2) * (o.cy + 2) * ((o.cz + 2 + 31) >> 5);
+    uint32_t* mine = work + o.off;
+    if (o.lds)
+        thin_object<true>(labels, X, Y, Z, ids[i], o, lds_planes, W, mine, counts + i, stats + 2 * i, error, s);
+    else
+        thin_object<false>(labels, X, Y, Z, ids[i], o, mine, W, mine, counts + i, stats + 2 * i, error, s);
+}
+
+// Skeleton voxels of object i, in raster order, as crop coordinates (x, y, z) at rows offsets[i] ..
+__global__ void __launch_bounds__(kThreads) emit_kernel(const SkelObj* __restrict__ objs, const uint32_t* __restrict__ work,
+                                                        const int* __restrict__ offsets, long long n_points,
+                                                        int* __restrict__ points) {
+    __shared__ int scan[kThreads];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const SkelObj o = objs[i];
+    const int PY = o.cy + 2, WZ = (o.cz + 2 + 31) >> 5;
+    const int W = (o.cx + 2) * PY * WZ;
+    const uint32_t* img = work + o.off;
+    const long long first = offsets[i], last = min((long long)offsets[i + 1], n_points);
+    long long base = first;
+    for (int w0 = 0; w0 < W; w0 += kThreads) {
+        const int w = w0 + tid;
+        uint32_t bits = w < W ? img[w] : 0u;
+        const int c = __builtin_popcount(bits);
+        scan[tid] = c;
+        __syncthreads();
+        for (int step = 1; step < kThreads; step <<= 1) {  // inclusive scan
+            const int add = tid >= step ? scan[tid - step] : 0;
+            __syncthreads();
+            scan[tid] += add;
+            __syncthreads();
+        }
+        const int total = scan[kThreads - 1];
+        long long p = base + scan[tid] - c;
+        if (bits) {
+            const int wz = w % WZ, t = w / WZ, y = t % PY, x = t / PY;
+            while (bits) {
+                const int b = __builtin_ctz(bits);
+                bits &= bits - 1;
+                if (p >= first && p < last) {
+                    points[3 * p] = x - 1;
+                    points[3 * p + 1] = y - 1;
+                    points[3 * p + 2] = 32 * wz + b - 1;
+                }
+                ++p;
+            }
+        }
+        base += total;
+        __syncthreads();  // scan[] is rewritten by the next chunk
+    }
+}
+
+struct Layout {
+    std::vector<SkelObj> objs;
+    size_t table_bytes = 0;
+    long long words = 0;
+    int lds_bytes = 0;
+};
+
+// Validates the boxes and places every object: LDS when its six planes fit kLdsBytes, else the global workspace.
+static int plan(const int32_t* boxes_host, int n, int X, int Y, int Z, Layout& L) {
+    L.objs.resize(n);
+    L.table_bytes = ((size_t)n * sizeof(SkelObj) + 255) & ~(size_t)255;
+    long long words = 0;
+    int lds = 0;
+    for (int i = 0; i < n; ++i) {
+        const int32_t* b = boxes_host + 6 * i;
+        SK_CHECK_ARG(b[0] >= 0 && b[1] >= 0 && b[2] >= 0 && b[3] > b[0] && b[4] > b[1] && b[5] > b[2] &&
+                         (X <= 0 || (b[3] <= X && b[4] <= Y && b[5] <= Z)),
+                     "sk_skeletonize: box %d (%d, %d, %d)..(%d, %d, %d) is empty or outside the volume", i, b[0],
+                     b[1], b[2], b[3], b[4], b[5]);
+        SkelObj& o = L.objs[i];
+        o.x0 = b[0], o.y0 = b[1], o.z0 = b[2];
+        o.cx = b[3] - b[0], o.cy = b[4] - b[1], o.cz = b[5] - b[2];
+        o.pad = 0;
+        const long long w = (long long)(o.cx + 2) * (o.cy + 2) * ((o.cz + 2 + 31) >> 5);
+        SK_CHECK_ARG(w * kPlanes < (1LL << 31) && (long long)o.cx * o.cy * o.cz < (1LL << 30),
+                     "sk_skeletonize: crop %d of %d x %d x %d voxels is too large", i, o.cx, o.cy, o.cz);
+        o.lds = w * kPlanes * 4 <= kLdsBytes;
+        o.off = words;
+        words += o.lds ? w : w * kPlanes;
+        if (o.lds) lds = std::max(lds, (int)(w * kPlanes * 4));
+    }
+    L.words = words;
+    L.lds_bytes = lds;
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sk_skeletonize_workspace_bytes(const int32_t* boxes_host, int n) {
+    Layout L;
+    if (n <= 0 || !boxes_host || plan(boxes_host, n, 0, 0, 0, L) != SK_OK) return 0;
+    return L.table_bytes + (size_t)L.words * 4;
+}
+
+int sk_skeletonize(const int32_t* labels, int X, int Y, int Z, const int32_t* ids, const int32_t* boxes_host, int n,
+                   void* workspace, size_t workspace_bytes, int32_t* counts, int32_t* stats, int32_t* error,
+                   void* stream) {
+    SK_CHECK_ARG(labels && ids && boxes_host && workspace && counts && stats && error && X > 0 && Y > 0 && Z > 0 && n > 0,
+                 "sk_skeletonize: bad arguments");
+    Layout L;
+    const int rc = plan(boxes_host, n, X, Y, Z, L);
+    if (rc != SK_OK) return rc;
+    SK_CHECK_ARG(workspace_bytes >= L.table_bytes + (size_t)L.words * 4,
+                 "sk_skeletonize: workspace of %zu bytes, %zu needed", workspace_bytes,
+                 L.table_bytes + (size_t)L.words * 4);
+    SK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "sk_skeletonize: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // the table goes through pageable memory: wait for the copy before L.objs goes away
+    SK_CHECK_HIP(hipMemcpyAsync(workspace, L.objs.data(), (size_t)n * sizeof(SkelObj), hipMemcpyHostToDevice, s));
+    SK_CHECK_HIP(hipMemsetAsync(error, 0, sizeof(int32_t), s));
+    if (L.lds_bytes > 0)
+        SK_CHECK_HIP(hipFuncSetAttribute((const void*)thin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         L.lds_bytes));
+    thin_kernel<<<n, kThreads, L.lds_bytes, s>>>(labels, X, Y, Z, ids, (const SkelObj*)workspace,
+                                                 (uint32_t*)((char*)workspace + L.table_bytes), counts, stats, error);
+    SK_CHECK_LAUNCH();
+    SK_CHECK_HIP(hipStreamSynchronize(s));
+    return SK_OK;
+}
+
+int sk_skeletonize_emit(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
+                        const int32_t* offsets, int64_t n_points, int32_t* points, void* stream) {
+    SK_CHECK_ARG(boxes_host && workspace && offsets && n > 0 && n_points >= 0 && (points || n_points == 0),
+                 "sk_skeletonize_emit: bad arguments");
+    Layout L;
+    const int rc = plan(boxes_host, n, 0, 0, 0, L);
+    if (rc != SK_OK) return rc;
+    SK_CHECK_ARG(workspace_bytes >= L.table_bytes + (size_t)L.words * 4,
+                 "sk_skeletonize_emit: workspace of %zu bytes, %zu needed", workspace_bytes,
+                 L.table_bytes + (size_t)L.words * 4);
+    emit_kernel<<<n, kThreads, 0, (hipStream_t)stream>>>((const SkelObj*)workspace,
+                                                         (const uint32_t*)((const char*)workspace + L.table_bytes),
+                                                         offsets, n_points, points);
+    SK_CHECK_LAUNCH();
+    return SK_OK;
+}
+
+}  // extern "C"

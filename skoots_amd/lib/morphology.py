@@ -1,7 +1,12 @@
 """``skoots.lib.morphology`` dilations on the MI355X
-(reference: skoots/lib/morphology.py:155-175 ``binary_dilation``, :178-199 ``binary_dilation_2d``)."""
+(reference: skoots/lib/morphology.py:155-175 ``binary_dilation``, :178-199 ``binary_dilation_2d``), and the Lee
+thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skeletonize``, ``thin_objects``)."""
 from __future__ import annotations
 
+import ctypes as C
+from typing import Tuple
+
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -31,3 +36,70 @@ def binary_dilation(image: Tensor) -> Tensor:
 def binary_dilation_2d(image: Tensor) -> Tensor:
     """3x3x1 max filter with zero padding on a (B, C, X, Y, Z) tensor."""
     return _max_filter(image, (1, 1, 0))
+
+
+THIN_ERRORS = {1: "a re-check round bound was hit", 2: "the pass bound was hit"}
+
+
+def thin_objects(labels: Tensor, ids, boxes) -> Tuple[Tensor, np.ndarray, np.ndarray]:
+    """Lee thinning of every object in its own crop, in one launch (one workgroup per object).
+
+    labels (X, Y, Z) int32 on the GPU; ids: n object ids; boxes (n, 6) ints (x0, y0, z0, x1, y1, z1): object i is
+    thinned in the binary crop ``labels[x0:x1, y0:y1, z0:z1] == ids[i]`` (voxels of other ids are background).
+    Returns (points, counts, stats): points (sum(counts), 3) int32 on the GPU, the skeleton voxels of object 0, 1, ...
+    in raster order of their crop as crop coordinates; counts (n,) int64; stats (n, 2) = passes and the most
+    re-check rounds of one sub-iteration (the kernel's counters)."""
+    if labels.ndim != 3:
+        raise ValueError("labels must be (X, Y, Z)")
+    _ffi.require_gpu(labels, "labels")
+    if labels.dtype != torch.int32:
+        raise ValueError("labels must be int32")
+    dev = labels.device
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 6))
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.zeros((0, 3), dtype=torch.int32, device=dev), np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
+    ids_d = torch.as_tensor(np.asarray(ids, dtype=np.int32).reshape(-1), device=dev)
+    if ids_d.numel() != n:
+        raise ValueError("one id per box")
+    boxes_p = boxes.ctypes.data_as(_ffi.ip)
+    nbytes = _ffi.lib.sk_skeletonize_workspace_bytes(boxes_p, n)
+    if nbytes == 0:
+        raise ValueError("every box must be non-empty: " + _ffi.last_error())
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    stats = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    X, Y, Z = labels.shape
+    stream = _ffi.stream_ptr(dev)
+    _ffi.check(_ffi.lib.sk_skeletonize(_ffi.ptr(labels), X, Y, Z, _ffi.ptr(ids_d), boxes_p, n, _ffi.ptr(work),
+                                       C.c_size_t(nbytes), _ffi.ptr(counts), _ffi.ptr(stats), _ffi.ptr(err), stream))
+    code = int(err.item())
+    if code:
+        msg = "; ".join(v for k, v in THIN_ERRORS.items() if code & k)
+        raise _ffi.SkootsHipError(f"sk_skeletonize: {msg} (error word {code})")
+    offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total = int(offsets[-1].item())
+    points = torch.empty((total, 3), dtype=torch.int32, device=dev)
+    _ffi.check(_ffi.lib.sk_skeletonize_emit(boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes), _ffi.ptr(offsets), total,
+                                            _ffi.ptr(points), stream))
+    return points, counts.cpu().numpy().astype(np.int64), stats.cpu().numpy().astype(np.int64)
+
+
+def skeletonize(image: Tensor) -> Tensor:
+    """Lee thinning of one 3-D binary volume on the GPU: ``skimage.morphology.skeletonize(image, method="lee") != 0``
+    (scikit-image 0.18.3), as a bool tensor of the same shape.  Non-zero voxels are foreground."""
+    if image.ndim != 3:
+        raise ValueError("image must be a 3-D volume")
+    _ffi.require_gpu(image, "image")
+    labels = (image != 0).to(torch.int32).contiguous()
+    X, Y, Z = labels.shape
+    out = torch.zeros((X, Y, Z), dtype=torch.bool, device=image.device)
+    if labels.numel() == 0:
+        return out
+    points, _, _ = thin_objects(labels, [1], [(0, 0, 0, X, Y, Z)])
+    if points.shape[0]:
+        p = points.long()
+        out[p[:, 0], p[:, 1], p[:, 2]] = True
+    return out
