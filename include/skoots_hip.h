@@ -713,6 +713,18 @@ int sk_mask_metrics(const int32_t* gt, const int32_t* pred, int X, int Y, int Z,
                     float* cldice, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Training command: dataset statistics
+ * ------------------------------------------------------------------------ */
+
+/* Adds the histogram of the n bytes at x into the 256 counters hist256 (the caller zeroes them; a second call adds
+ * into the same counters).  Replaces the per-volume host loops of skoots/train/dataloader.py:246-310 (dataset.sum,
+ * subtract_square_sum) for a volume that lives on the device: the sum is sum_v v h[v], exactly, and
+ * sum (x - other)^2 = sum_v h[v] (v - other)^2 for any `other`.  x may have any alignment; n in [0, 2^40]; hist256 is
+ * 8-byte aligned.  Integer atomics: exact and identical from run to run.  Every argument is checked before the
+ * first write. */
+int sk_u8_histogram(const uint8_t* x, int64_t n, unsigned long long* hist256, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

@@ -171,6 +171,7 @@ _SIGS = {
     "sk_skeletonize_workspace_bytes": (sz, [ip, i32]),
     "sk_skeletonize": (i32, [vp, i32, i32, i32, vp, ip, i32, vp, sz, vp, vp, vp, vp]),
     "sk_skeletonize_emit": (i32, [ip, i32, vp, sz, vp, i64, vp, vp]),
+    "sk_u8_histogram": (i32, [vp, i64, vp, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

@@ -28,6 +28,7 @@ from .. import _ffi
 from ..profile import ASSIGN_BYTES_PER_VOXEL, GATE_BYTES_PER_VOXEL, maybe_span
 from . import cropper
 from .flood_fill import label_skeleton
+from .tiff import read_image as _read_image  # noqa: F401  (shared with skoots_amd.train.dataloader)
 from .vector_to_embedding import step_scales
 
 TILE = (300, 300, 20)          # eval.py:126
@@ -233,19 +234,6 @@ def eval_volume(image: Tensor, model, scale, mean=None, std=None, n: int = FOLLO
 # ----------------------------------------------------------------------------------------
 # File-level entry point: same signature and side effects as skoots.lib.eval.eval
 # ----------------------------------------------------------------------------------------
-def _read_image(path: str) -> np.ndarray:
-    """[Z, X, Y(, C)] array from a multi-page TIFF (Pillow) or a .npy file (eval.py:61)."""
-    if path.endswith(".npy"):
-        return np.load(path)
-    from PIL import Image
-    pages = []
-    with Image.open(path) as im:
-        for i in range(getattr(im, "n_frames", 1)):
-            im.seek(i)
-            pages.append(np.array(im))
-    return np.stack(pages, axis=0)
-
-
 def _write_mask_tif(path: str, mask_zxy: np.ndarray) -> None:
     """(Z, X, Y) integer stack -> multi-page TIFF, zlib/deflate compressed (eval.py:309-310)."""
     from PIL import Image

@@ -369,6 +369,12 @@ class TrainUNet:
                             want32=(i == len(self.dec0) - 1 and not self._heads_fast(self.heads)))
         return self._block(self.heads, [(a, 0)], L0)
 
+    def release(self) -> None:
+        """Drop what the last forward kept for a backward (a forward that is not followed by one: validation)."""
+        self._tape = []
+        self._half = {}
+        self._keep = []
+
     def backward(self, dlogits: Tensor) -> None:
         """Walk the recorded layers in reverse; gradients of every parameter land in ``flat_grad``."""
         if not self._tape:
@@ -635,7 +641,10 @@ class TrainStep:
     1e-6, betas (0.9, 0.999), eps 1e-8; Tversky (alpha, beta, eps) = embed (0.25, 0.75, 1e-8), probability
     (0.5, 0.5, 1e-8), skeleton (0.5, 1.5, 1e-8); relative weights 1; vector scaling (60, 60, 12).  Each of
     ``loss_embed`` / ``loss_prob`` / ``loss_skele`` is an (alpha, beta, eps) tuple (Tversky) or a loss object,
-    ``tversky(...)`` or ``soft_dice_cldice(...)`` (e.g. ``loss.loss_from_cfg(cfg.TRAIN.LOSS_SKELETON, ...)``)."""
+    ``tversky(...)`` or ``soft_dice_cldice(...)`` (e.g. ``loss.loss_from_cfg(cfg.TRAIN.LOSS_SKELETON, ...)``).
+
+    ``lr`` is a plain attribute read by every optimizer step: the training loop sets it at the start of each epoch
+    (skoots_amd/train/trainer.py)."""
 
     def __init__(self, model: TrainUNet, lr: float = 5e-4, weight_decay: float = 1e-6, betas=(0.9, 0.999),
                  eps: float = 1e-8, vector_scale=(60, 60, 12),
@@ -678,6 +687,20 @@ class TrainStep:
         if self.process_group is not False:
             self.sync_gradients()
         self.optimizer_step()
+        return losses
+
+    @torch.no_grad()
+    def evaluate(self, images: Tensor, masks: Tensor, skele_masks: Tensor, baked: Tensor,
+                 sigma: Sequence[float] = (20.0, 20.0, 20.0), weights: Optional[Sequence[float]] = None) -> Tensor:
+        """The validation pass of one batch (engine.py:559-595): forward and losses only -- no gradient, no optimizer
+        step -- then what the forward kept for a backward is released.  Returns (embed, prob, skeleton, total) on the
+        device.  As in the reference (engine.py:571), the SKELETON term is computed with the PROBABILITY term's loss
+        function."""
+        logits = self.model.forward(images)
+        params = [self.loss_params[0], self.loss_params[1], self.loss_params[1]]
+        losses, _ = fused_loss(logits, masks, skele_masks, baked, sigma, self.vector_scale, params,
+                               self.weights if weights is None else weights, need_grad=False)
+        self.model.release()
         return losses
 
     # -- checkpoint (the payload the reference documents: cfg, model_state_dict, optimizer_state_dict) ------
