@@ -725,6 +725,28 @@ int sk_mask_metrics(const int32_t* gt, const int32_t* pred, int X, int Y, int Z,
 int sk_u8_histogram(const uint8_t* x, int64_t n, unsigned long long* hist256, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * eval() outputs: deflate encoder for the zarr chunks and the TIFF pages
+ * ------------------------------------------------------------------------ */
+
+/* Compresses n_streams inputs of stream_bytes bytes each (src: contiguous, any alignment) into n_streams complete
+ * zlib streams (RFC 1950: 78 01, RFC 1951 blocks, Adler-32 big-endian), written back to back into dst: stream i is
+ * dst[dst_offsets[i] .. dst_offsets[i + 1]); dst_offsets has n_streams + 1 entries (device, 8-byte aligned).  Replaces
+ * zlib.compress(chunk, 1) on the host (the reference leaves its arrays to zarr / skimage, eval.py:101-111, 309-310).
+ * dst must hold n_streams * sk_deflate_bound(stream_bytes) bytes: the worst case of one stream, in which every 16 KiB
+ * piece is a stored block (n + 8 <= bound(n) <= n + n / 1024 + 64).  A zero-length stream is the 8-byte empty stream.
+ * elem_bytes (1, 2 or 4) is a hint: the match distances tried are 1 and k * elem_bytes, k = 1..64; the format does
+ * not change with it.  all_zero (device, n_streams bytes) may be NULL; when given, all_zero[i] = 1 says that input i
+ * held only zero bytes, and such a stream is left out of dst (dst_offsets[i + 1] == dst_offsets[i]): the zarr writer
+ * does not store fill-value chunks.  The bytes depend on the input alone: the same on every run, for every n_streams.
+ * workspace: sk_deflate_workspace_bytes(n_streams, stream_bytes), 16-byte aligned.  sk_deflate_bound and
+ * sk_deflate_workspace_bytes are host functions that touch no device.  Every argument is checked before the first
+ * write. */
+size_t sk_deflate_bound(int64_t stream_bytes);
+size_t sk_deflate_workspace_bytes(int n_streams, int64_t stream_bytes);
+int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes, uint8_t* dst,
+                       int64_t* dst_offsets, uint8_t* all_zero, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

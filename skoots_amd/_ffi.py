@@ -172,6 +172,9 @@ _SIGS = {
     "sk_skeletonize": (i32, [vp, i32, i32, i32, vp, ip, i32, vp, sz, vp, vp, vp, vp]),
     "sk_skeletonize_emit": (i32, [ip, i32, vp, sz, vp, i64, vp, vp]),
     "sk_u8_histogram": (i32, [vp, i64, vp, vp]),
+    "sk_deflate_bound": (sz, [i64]),
+    "sk_deflate_workspace_bytes": (sz, [i32, i64]),
+    "sk_deflate_streams": (i32, [vp, i32, i64, i32, vp, vp, vp, vp, sz, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

@@ -257,8 +257,9 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     matrix instruction (same tolerance, ~20 % faster); "fp32" = exact-fp32 matrix instructions (:class:`skoots_amd.unet.HipUNet`).
 
     Writes next to the image, with the reference's names: ``<base>_skoots_skeleton`` (1,X,Y,Z) u1
-    and ``<base>_skoots_vectors`` (3,X,Y,Z) f2 as ``.zarr`` directory stores (zarr v2 layout, uncompressed,
-    written by ``zarr_store``: the zarr package itself is not in this image),
+    and ``<base>_skoots_vectors`` (3,X,Y,Z) f2 as ``.zarr`` directory stores (zarr v2 layout, zlib codec,
+    written by ``zarr_store.save_device``: the zarr package itself is not in this image; chunks and TIFF pages are
+    deflated on the device, ``lib/deflate.py``),
     ``<base>_skoots_benchmark.txt`` and ``<base>_instance_mask.tif`` (Z,X,Y), and prints DONE.
 
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
@@ -291,7 +292,7 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
 
     logging.info("Constructing SKOOTS model")
     model = unet.cfg_to_model(cfg, device, checkpoint["model_state_dict"], precision=precision)
-    from . import zarr_store
+    from . import tiff, zarr_store
     skel_path, vec_path = base + "_skoots_skeleton.zarr", base + "_skoots_vectors.zarr"  # eval.py:102-103
 
     benchmark_start = time.time()
@@ -314,8 +315,8 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     torch.cuda.synchronize(device)
     dt = time.time() - benchmark_start
 
-    zarr_store.save(skel_path, skeleton.cpu().numpy()[np.newaxis])
-    zarr_store.save(vec_path, vectors.cpu().numpy())
+    zarr_store.save_device(skel_path, skeleton.unsqueeze(0))  # deflated on the device: only compressed bytes leave it
+    zarr_store.save_device(vec_path, vectors)
     logging.info("writing benchmark information")
     with open(base + "_skoots_benchmark.txt", "w") as f:  # eval.py:286-295
         f.write("SKOOTS Segmentation Benchmark:\n")
@@ -325,6 +326,6 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
                 f"{torch.cuda.max_memory_allocated(device)})\n\n")
     print("DONE")
     logging.info(f"saving to tif file at {base}_instance_mask.tif")
-    _write_mask_tif(base + "_instance_mask.tif", inst.cpu().numpy().transpose(2, 0, 1))
+    tiff.write_label_stack(base + "_instance_mask.tif", inst.permute(2, 0, 1))
     elapsed = time.time() - start
     logging.info(f"DONE: Process took {elapsed} seconds, {elapsed / 60} minutes, {elapsed / (60 ** 2)}, hours")

@@ -6,7 +6,10 @@ The ``zarr`` / ``numcodecs`` packages are not in this image.  What is written he
 it.  Chunks are compressed with the numcodecs ``zlib`` codec (``{"id": "zlib", "level": 1}`` -- the stdlib's zlib; the
 reference's stores use zarr's default Blosc codec, which needs the absent ``numcodecs``) or stored raw
 (``compressor=None``); chunks that hold only the fill value are not written, as zarr does.  ``load`` reads raw, zlib
-and gzip stores and refuses every other codec by name."""
+and gzip stores and refuses every other codec by name.
+
+``save_device`` writes the same zlib store from a torch tensor without taking the array to the host first: chunks are
+gathered and deflated on the tensor's device (``lib/deflate.py``), only compressed bytes cross to the host."""
 from __future__ import annotations
 
 import gzip
@@ -14,6 +17,7 @@ import itertools
 import json
 import os
 import shutil
+import time
 import zlib
 from typing import Optional, Sequence
 
@@ -52,6 +56,68 @@ def save(path: str, arr: np.ndarray, chunks: Optional[Sequence[int]] = None, com
         raw = block.tobytes()
         with open(os.path.join(path, ".".join(str(i) for i in idx)), "wb") as f:
             f.write(zlib.compress(raw, int(level)) if compressor else raw)
+
+
+SAVE_DEVICE_BUDGET = 256 << 20  # bytes of staging + encoder buffers per batch of chunks (see save_device)
+
+
+def save_device(path: str, tensor, chunks: Optional[Sequence[int]] = None, budget_bytes: int = SAVE_DEVICE_BUDGET,
+                timings=None) -> None:
+    """The store ``save(path, array, compressor="zlib")`` writes -- same default chunks, same ``.zarray`` text, edge
+    chunks zero-padded, fill-value chunks left out -- from a torch tensor on either device (a numpy array is taken as a
+    CPU tensor).  Chunks are copied into a ``(n, chunk_bytes)`` staging buffer with torch indexing on the tensor's device
+    and deflated there in batches: one batch takes about three times its chunks' bytes (staging, the encoder's worst-case
+    output, its workspace), and a batch is sized to keep that under ``budget_bytes`` (256 MiB by default; at least one
+    chunk), so the memory this takes does not grow with the array.  On a CPU tensor the files are byte for byte
+    those of ``save``; on a device tensor the chunk files hold other bytes that inflate to the same chunks."""
+    import torch
+
+    from . import deflate
+    t = torch.from_numpy(np.ascontiguousarray(tensor)) if isinstance(tensor, np.ndarray) else tensor
+    np_dtype = torch.empty(0, dtype=t.dtype).numpy().dtype
+    if chunks is None:
+        chunks = [min(s, c) for s, c in zip(t.shape, (1, 256, 256, 64)[-t.ndim:])]
+    chunks = [max(1, int(c)) for c in chunks]
+    if os.path.isdir(path):
+        shutil.rmtree(path)
+    os.makedirs(path)
+    meta = {"zarr_format": 2, "shape": list(t.shape), "chunks": chunks, "dtype": _dtype_str(np_dtype),
+            "compressor": {"id": "zlib", "level": 1}, "fill_value": 0, "order": "C", "filters": None}
+    with open(os.path.join(path, ".zarray"), "w") as f:
+        json.dump(meta, f, indent=2)
+    item = np_dtype.itemsize
+    chunk_bytes = int(np.prod(chunks)) * item
+    grid = [range((s + c - 1) // c) for s, c in zip(t.shape, chunks)]
+    todo = [idx for idx in itertools.product(*grid)]
+    per_chunk = chunk_bytes + deflate.device_bytes_per_stream(chunk_bytes)
+    batch = max(1, int(budget_bytes) // per_chunk)
+    by_value = np_dtype.kind not in "iub"   # -0.0 is the fill value too: such dtypes are tested by value, as save does
+    for lo in range(0, len(todo), batch):
+        part = todo[lo:lo + batch]
+        staging = torch.zeros([len(part)] + chunks, dtype=t.dtype, device=t.device)
+        for b, idx in enumerate(part):
+            sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, t.shape))
+            src = t[sl]
+            staging[b][tuple(slice(0, n) for n in src.shape)] = src
+        rows = staging.view(len(part), -1)
+        if by_value:
+            keep = rows.ne(0).any(dim=1).cpu().tolist()
+            part = [idx for idx, k in zip(part, keep) if k]
+            if not part:
+                continue
+            if not all(keep):
+                rows = rows[torch.tensor(keep, device=rows.device)]
+        streams = deflate.deflate_streams(rows.contiguous().view(torch.uint8).view(len(part), chunk_bytes),
+                                          elem_bytes=item if item in (1, 2, 4) else 1, skip_zero=not by_value,
+                                          timings=timings)
+        t0 = time.perf_counter()
+        for idx, stream in zip(part, streams):
+            if stream is None:
+                continue  # only the fill value
+            with open(os.path.join(path, ".".join(str(i) for i in idx)), "wb") as f:
+                f.write(stream)
+        if timings is not None:
+            timings["file_s"] = timings.get("file_s", 0.0) + time.perf_counter() - t0
 
 
 def load(path: str) -> np.ndarray:
