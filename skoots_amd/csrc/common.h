@@ -125,6 +125,17 @@ __device__ inline t16 round_t16(float v) {
     return (t16)v;
 }
 
+// silu(ga * x + gb) of the fused GroupNorm + SiLU, as an fp32 value and rounded to the 16-bit type: the ONE arithmetic of
+// gn_silu_kernel and of every kernel that activates a raw tensor on the way (the conv kernels in LDS, the gather / down /
+// stem / heads kernels on load) -- tests assert that they agree bit for bit.  Hardware exp2 / rcp (relative error ~1e-6,
+// far below the 16-bit values they feed).
+__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float silu_affine(float ga, float x, float gb) {
+    const float y = fmaf(ga, x, gb);
+    return y * sigmoid_fast(y);
+}
+__device__ __forceinline__ t16 silu_affine_t16(float ga, float x, float gb) { return round_t16(silu_affine(ga, x, gb)); }
+
 // Buffer loads: the hardware bounds check returns 0 for an offset past the descriptor's byte count, so a
 // masked lane passes kOob instead of branching around the load (a branch per load lets the compiler chain
 // load -> wait -> use, one memory latency at a time).  The descriptor must be wave-uniform.

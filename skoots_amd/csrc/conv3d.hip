@@ -37,21 +37,15 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.h"
+#include "conv3_device.h"
 
 namespace {
 
-typedef t16 half8 __attribute__((ext_vector_type(8)));
-typedef t16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// the workgroups blockIdx.x in [dbg_off, dbg_off + 4096) dump their phase cycle sums (SK_CONV_DBG_OFF)
+#define SK_T_DUMP(a, w, lane) \
+    SK_T_DUMP_ROW(a, (int)blockIdx.x >= (a).dbg_off && (int)blockIdx.x < (a).dbg_off + sk::kTimingBlocks, (int)blockIdx.x - (a).dbg_off, w, lane)
 
-constexpr int kChunk = 32;       // input channels per LDS image
-constexpr int kPosBytes = 64;    // kChunk * sizeof(fp16)
-constexpr int kPatch = 128;      // voxels per (y,z) patch = 4 waves x 32 columns
 constexpr int kMaxDma = 4;       // DMA wave-instructions per plane per wave (nposp <= 256)
-constexpr int kPadStride = 64;   // bytes per voxel in the epilogue transpose pad (16-B chunks XOR-swizzled)
-constexpr int kPadBytes = 32 * kPadStride;
 constexpr int kMaxChunks = 24;   // phase chunks per step: 8 plain (256 channels: a 128 + 128 concat) or 24 split (3 per 32 channels)
 
 struct SrcDev {
@@ -92,34 +86,6 @@ struct Conv3Args {
     unsigned chinfo[kMaxChunks];
 };
 
-// Timing experiments (wrong results by design) exist only in the -DSK_TUNING build that tools/ use: in the release
-// library no environment variable can change what a kernel computes.
-// (non-temporal epilogue stores: -1.7 % on the conv kernels, +4.5 % on the GroupNorm pass that reads the tensor next --
-// it loses what the conv's stores leave in the Infinity Cache; net zero, not used)
-// Phase timing (tools/conv_phase_timing.py, -DSK_TIMING build only): per wave, cycles between the marks of a phase
-#ifdef SK_TIMING
-#define SK_T_DECL long long tacc_[sk::kTimingSlots] = {0}; long long tprev_ = __builtin_readcyclecounter();
-#define SK_T(i) { const long long t_ = __builtin_readcyclecounter(); tacc_[i] += t_ - tprev_; tprev_ = t_; }
-#define SK_T_DUMP(a, w, lane) if ((a).dbg && (int)blockIdx.x >= (a).dbg_off && (int)blockIdx.x < (a).dbg_off + sk::kTimingBlocks && (w) < 4 && (lane) == 0) { \
-        for (int i_ = 0; i_ < sk::kTimingSlots; ++i_) (a).dbg[((long long)((int)blockIdx.x - (a).dbg_off) * 4 + (w)) * sk::kTimingSlots + i_] = tacc_[i_]; }
-#else
-#define SK_T_DECL
-#define SK_T(i)
-#define SK_T_DUMP(a, w, lane)
-#endif
-#ifdef SK_TUNING
-#define SK_ABL(a, bits) ((a).ablate & (bits))
-#else
-#define SK_ABL(a, bits) 0
-#endif
-// compile-time ablations of conv3_px_kernel's MFMA body (a run-time switch there changes the schedule it is meant to
-// measure): make ... EXTRA="-DSK_TUNING -DSK_PX_ABLATE=48"; 16: no LDS weight reads, 32: no B fragment reads after a
-// step's first tap row, 64: no barrier between the steps.  Results are wrong by design.
-#ifndef SK_PX_ABLATE
-#define SK_PX_ABLATE 0
-#endif
-#define SK_PX_ABL(bits) ((SK_PX_ABLATE) & (bits))
-
 __device__ __forceinline__ void dma16(const char* g, char* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
@@ -154,14 +120,9 @@ __global__ void __launch_bounds__(256, 2) conv3_kernel(Conv3Args a) {
     const int wm = w / NT;           // voxel group of this wave
     const int col = lane & 31, h = lane >> 5;
 
-    // Workgroups are dealt round-robin over the 8 XCDs (private L2 each).  Neighbouring patches
-    // share their y/z halo and consecutive x-chunks share two planes: give each XCD a contiguous
-    // run of the (batch, x-chunk, patch) order so those re-reads hit its own L2 (bijective remap).
     int blk = blockIdx.x;
-    if (!SK_ABL(a, 16)) {
-        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
-        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
-    }
+    if (!SK_ABL(a, 16)) blk = xcd_remap(blk);
+    // (decode_block's arithmetic, its own copy: through the helper the COUT 128 forms of the -DSK_TIMING build get other SGPR numbers)
     const int patch = blk % a.npatch;
     blk /= a.npatch;
     const int xc = blk % a.nxc;
@@ -280,40 +241,7 @@ __global__ void __launch_bounds__(256, 2) conv3_kernel(Conv3Args a) {
     char* pad = lds + R * plane_bytes + w * kPadBytes;
     const int rv = lane >> 2, rc = lane & 3;  // epilogue read-back: voxel (0..15), 16-byte chunk
 
-    // buffer-resource LDS-DMA and stores: 32-bit offsets into this batch item's tensors (one address VGPR instead of
-    // two, 32-bit address arithmetic: -2 % time); an out-of-range offset reads zeros -- what the halo / padding lanes
-    // want -- and drops a masked store
-    // A descriptor covers only the x-planes of ONE step (built per phase from wave-uniform values: a few scalar
-    // instructions): a tensor of one batch item may exceed the 4 GiB a descriptor / a 32-bit offset can span
-    // (the split mode's 512x512x128 tile: 4.3 GB per 32-channel tensor).
-    auto issue_dma = [&](int step, int ch, bool reuse, int rot_n) {
-        const int x0 = xa + step * XS;
-        const unsigned ci = a.chinfo[ch];
-        const int si = ci & 1;
-        const SrcDev s = a.src[si];
-        const int choff = ci >> 8;  // byte offset of the chunk in the voxel line
-        const int first_new = reuse ? 2 : 0;  // planes 0,1 are the previous phase's planes XS, XS + 1
-        const int xlo = s.up ? (max(x0 - 1, 0) >> 1) : max(x0 - 1, 0);   // first source plane of the step
-        const long long wbytes = min((long long)(R + 1) * s.plane, s.batch - (long long)xlo * s.plane);
-        const __amdgpu_buffer_rsrc_t rsrc = sk::make_rsrc(s.data + (long long)b * s.batch + (long long)xlo * s.plane, (unsigned)wbytes);
-        for (int i = SK_ABL(a, 1) ? R : first_new; i < R; ++i) {
-            const int x = x0 - 1 + i;
-            const int slotp = (rot_n + i) % R;
-            const bool xok = x >= 0 && x < a.Xt;
-            char* lbase = lds + slotp * plane_bytes;
-            const unsigned xoff = (unsigned)(((s.up ? (x >> 1) : x) - xlo) * (int)s.plane + choff + d_cs);
-            const unsigned vstride = (unsigned)(s.C * 2);
-#pragma unroll
-            for (int k = 0; k < kMaxDma; ++k) {
-                const int t = w + 4 * k;
-                if (t < ndma) {
-                    const int vox = s.up ? d_up[k] : d_vox[k];
-                    const unsigned voff = (xok && vox >= 0) ? xoff + (unsigned)vox * vstride : sk::kOob;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lbase + t * 1024), 16, voff, 0, 0, 0);
-                }
-            }
-        }
-    };
+#include "conv3_issue_dma.inc"
     // weight fragment index: (((ch*9 + dydz)*2 + ks)*3 + d)*NT + nt
     // weight fragments through a buffer resource: wave-uniform byte offset in an SGPR + the constant lane * 16 in one VGPR
     // (no 64-bit address arithmetic in the tap loop)
@@ -677,6 +605,7 @@ __global__ void __launch_bounds__(256, 2) conv3_kernel(Conv3Args a) {
                 red[(w * 8 + 2 * q + h) * 2 + 1] = ss;
             }
         }
+        // (gn_block_sum's arithmetic, its own copy: through the helper the mix8 forms' registers are numbered differently)
         __syncthreads();
         if (tid < NT * 16) {
             // channel quad Q = cout/4 = 8*nt + k ; waves with wn == nt: w = wm*NT + nt
@@ -730,20 +659,10 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
     // a 32 x 32 (cout, voxel) tile is 2 x 2 of its 16 x 16 results: i = cout half, j = voxel half.
     const int c16 = lane & 15, g = lane >> 4;
 
-    // Workgroups are dealt round-robin over the 8 XCDs (private L2 each).  Neighbouring patches
-    // share their y/z halo and consecutive x-chunks share two planes: give each XCD a contiguous
-    // run of the (batch, x-chunk, patch) order so those re-reads hit its own L2 (bijective remap).
     int blk = blockIdx.x;
-    if (!SK_ABL(a, 16)) {
-        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
-        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
-    }
-    const int patch = blk % a.npatch;
-    blk /= a.npatch;
-    const int xc = blk % a.nxc;
-    const int b = blk / a.nxc;
-    const int block_in_batch = xc * a.npatch + patch;
-    const int nblk = a.npatch * a.nxc;
+    if (!SK_ABL(a, 16)) blk = xcd_remap(blk);
+    int patch, xc, b, block_in_batch, nblk;
+    decode_block(blk, a.npatch, a.nxc, patch, xc, b, block_in_batch, nblk);
 
     // ---- patch geometry ------------------------------------------------------------
     const int pitch = a.pitch;
@@ -886,38 +805,7 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
     const int nsteps = (xb - xa + XS - 1) / XS;
     const int nphases = nsteps * a.nchunks;
 
-    // buffer-resource LDS-DMA and stores (see conv3_kernel)
-    // A descriptor covers only the x-planes of ONE step (built per phase from wave-uniform values: a few scalar
-    // instructions): a tensor of one batch item may exceed the 4 GiB a descriptor / a 32-bit offset can span
-    // (the split mode's 512x512x128 tile: 4.3 GB per 32-channel tensor).
-    auto issue_dma = [&](int step, int ch, bool reuse, int rot_n) {
-        const int x0 = xa + step * XS;
-        const unsigned ci = a.chinfo[ch];
-        const int si = ci & 1;
-        const SrcDev s = a.src[si];
-        const int choff = ci >> 8;  // byte offset of the chunk in the voxel line
-        const int first_new = reuse ? 2 : 0;  // planes 0,1 are the previous phase's planes XS, XS + 1
-        const int xlo = s.up ? (max(x0 - 1, 0) >> 1) : max(x0 - 1, 0);   // first source plane of the step
-        const long long wbytes = min((long long)(R + 1) * s.plane, s.batch - (long long)xlo * s.plane);
-        const __amdgpu_buffer_rsrc_t rsrc = sk::make_rsrc(s.data + (long long)b * s.batch + (long long)xlo * s.plane, (unsigned)wbytes);
-        for (int i = SK_ABL(a, 1) ? R : first_new; i < R; ++i) {
-            const int x = x0 - 1 + i;
-            const int slotp = (rot_n + i) % R;
-            const bool xok = x >= 0 && x < a.Xt;
-            char* lbase = lds + slotp * plane_bytes;
-            const unsigned xoff = (unsigned)(((s.up ? (x >> 1) : x) - xlo) * (int)s.plane + choff + d_cs);
-            const unsigned vstride = (unsigned)(s.C * 2);
-#pragma unroll
-            for (int k = 0; k < kMaxDma; ++k) {
-                const int t = w + 4 * k;
-                if (t < ndma) {
-                    const int vox = s.up ? d_up[k] : d_vox[k];
-                    const unsigned voff = (xok && vox >= 0) ? xoff + (unsigned)vox * vstride : sk::kOob;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lbase + t * 1024), 16, voff, 0, 0, 0);
-                }
-            }
-        }
-    };
+#include "conv3_issue_dma.inc"
     // GroupNorm affine + SiLU of a RAW source, applied in LDS by the lane that staged the chunk (its own `vmcnt` wait
     // covers its own LDS-DMA: no barrier in between); halo / padding lanes staged zeros, which stay zeros
     auto activate = [&](int step, int ch, bool reuse, int rot_n) {
@@ -951,10 +839,8 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
                     const bool real = (s.up ? d_up[k] : d_vox[k]) >= 0;
                     half8 r;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {   // gn_silu_kernel's arithmetic, op for op
-                        const float y = fmaf(ga[e], (float)v[k][e], gb[e]);
-                        const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-y));
-                        const t16 act = sk::round_t16(y * sg);   // unconditional: the asm inside must not sit behind a per-element branch
+                    for (int e = 0; e < 8; ++e) {
+                        const t16 act = sk::silu_affine_t16(ga[e], (float)v[k][e], gb[e]);   // unconditional: the asm inside must not sit behind a per-element branch
                         r[e] = real ? act : v[k][e];
                     }
                     *reinterpret_cast<half8*>(lbase + t * 1024 + lane * 16) = r;
@@ -1335,30 +1221,9 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
     SK_T_DUMP(a, w, lane)
     // ---- block-level reduction of the GroupNorm partials ------------------------------------
     if (a.partial) {
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(lds);  // [4 waves][8 quads of the wave's cout tile][2]
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float s = gsum[i], ss = gsq[i];
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) {   // the 16 lanes that share g
-                s += __shfl_xor(s, m);
-                ss += __shfl_xor(ss, m);
-            }
-            if (c16 == 0) {
-                red[(w * 8 + 4 * i + g) * 2 + 0] = s;
-                red[(w * 8 + 4 * i + g) * 2 + 1] = ss;
-            }
-        }
-        __syncthreads();
-        if (tid < NT * 16) {
-            // channel quad Q = cout/4 = 8*nt + k ; waves with wn == nt: w = wm*NT + nt
-            const int nt = tid / 16, k2 = tid % 16;
-            float t = 0.0f;
-#pragma unroll
-            for (int g = 0; g < 4 / NT; ++g) t += red[(g * NT + nt) * 16 + k2];
-            a.partial[((long long)b * nblk + block_in_batch) * (NT * 16) + tid] = t;
-        }
+        float* red = reinterpret_cast<float*>(lds);
+        gn_wave_sum16(red, gsum, gsq, w, c16, g);
+        gn_block_sum<NT>(red, a.partial, b, nblk, block_in_batch, NT * 16, 0, tid);
     }
 }
 
@@ -1396,65 +1261,11 @@ __global__ void __launch_bounds__(256, 2) conv3_px_kernel(Conv3Args a) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // column tile of this wave (32 voxels of the 128-voxel patch)
     const int c16 = lane & 15, g = lane >> 4;
 
-    int blk = blockIdx.x;   // XCD-aware order, see conv3_kernel
-    {
-        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
-        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
-    }
-    const int patch = blk % a.npatch;
-    blk /= a.npatch;
-    const int xc = blk % a.nxc;
-    const int b = blk / a.nxc;
-    const int block_in_batch = xc * a.npatch + patch;
-    const int nblk = a.npatch * a.nxc;
+    int patch, xc, b, block_in_batch, nblk;
+    decode_block(xcd_remap(blockIdx.x), a.npatch, a.nxc, patch, xc, b, block_in_batch, nblk);
 
-    // ---- patch geometry (conv3_m16_kernel's, one column tile per wave) ---------------------------
-    const int pitch = a.pitch;
-    int off, ybase, zbase, q_row, out_vox0, tile_nvox;
-    int svy, svz;             // (y, z) of the voxel this lane STORES: column c16 + 16 (g & 1) of the wave's tile
-    unsigned vflags = 0;      // bit j: voxel 16 j + c16 on the z = 0 face | << 8: on the z = Zt-1 face | << 16: inside the tile
-    auto zlo = [&](int j) { return (vflags >> j) & 1u; };
-    auto zhi = [&](int j) { return (vflags >> (8 + j)) & 1u; };
-    auto vvalid = [&](int j) { return (vflags >> (16 + j)) & 1u; };
-    // linear mode only (Zt <= 40, conv3_m16_kernel's comment): region position q <-> in-plane voxel v0 - Zt - 1 + q
-    const int needed = kPatch + 2 * a.Zt + 2;   // positions a plane really holds; NPOSP rounds it up to a DMA granule
-    {
-        const int v0 = patch * kPatch;
-        off = v0 - a.Zt - 1;
-        ybase = 0;
-        zbase = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int v = v0 + 32 * w + 16 * j + c16;
-            const int vy = v / a.Zt, vz = v - vy * a.Zt;
-            vflags |= (unsigned)(v < a.Yt * a.Zt) << (16 + j);
-            vflags |= (unsigned)(vz == 0) << j;
-            vflags |= (unsigned)(vz == a.Zt - 1) << (8 + j);
-            if (j == 0) q_row = v - off;
-        }
-        out_vox0 = v0 + 32 * w;
-        tile_nvox = a.Yt * a.Zt;
-        const int sv = out_vox0 + c16 + 16 * (g & 1);
-        svy = sv / a.Zt;
-        svz = sv - svy * a.Zt;
-    }
-    const bool sbox = !a.has_box || (svy >= a.box_lo[1] && svy < a.box_hi[1] && svz >= a.box_lo[2] && svz < a.box_hi[2]);
-
-    // ---- LDS-DMA bookkeeping: this lane's slots of a plane (conv3_m16_kernel's swizzle) -----------
-    constexpr int ndma = NPOSP / 16;
-    int d_vox[kMaxDma];
-    const int d_cs = ((lane & 3) ^ (((lane >> 4) & 1) << 1)) * 16;
-#pragma unroll
-    for (int k = 0; k < kMaxDma; ++k) {
-        const int t = w + 4 * k;
-        const int q = (64 * t + lane) >> 2;
-        const int Pq = q + off;
-        const int y = ybase + (Pq >= 0 ? Pq / pitch : -1), z = zbase + (Pq >= 0 ? Pq % pitch : 0);
-        // positions >= needed are padding that the LDS-DMA never writes (d_vox -2: the lane sits out of the instruction):
-        // two of them hold the bias / the GroupNorm coefficients of a raw source, the last four are the zero window
-        const bool ok = (t < ndma) && y >= 0 && y < a.Yt && z >= 0 && z < a.Zt;
-        d_vox[k] = q >= needed ? -2 : (ok ? (y * a.Zt + z) * 64 + d_cs : -1);   // the BYTE offset of this lane's 16-byte piece in a plane
-    }
+    constexpr int kLineBytes = 64;   // a plane of 32-channel fp16 lines
+#include "conv3_px_geometry.inc"
 
     const int xa = xc * a.XC;
     const int xb = min(xa + a.XC, a.Xt);
@@ -1516,10 +1327,8 @@ __global__ void __launch_bounds__(256, 2) conv3_px_kernel(Conv3Args a) {
                 const bool real = d_vox[k] >= 0;
                 half8 r;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {   // gn_silu_kernel's arithmetic, op for op
-                    const float y = fmaf(ga[e], (float)v[k][e], gb[e]);
-                    const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-y));
-                    const t16 act = sk::round_t16(y * sg);   // unconditional: the asm inside must not sit behind a per-element branch
+                for (int e = 0; e < 8; ++e) {
+                    const t16 act = sk::silu_affine_t16(ga[e], (float)v[k][e], gb[e]);   // unconditional: the asm inside must not sit behind a per-element branch
                     r[e] = real ? act : v[k][e];
                 }
                 if (d_vox[k] != -2) *reinterpret_cast<half8*>(lbase + tt * 1024 + lane * 16) = r;   // not the padding
@@ -1527,23 +1336,8 @@ __global__ void __launch_bounds__(256, 2) conv3_px_kernel(Conv3Args a) {
         }
     };
 
-    // ---- weights: half rows (tap row dydz, cout half i) 0 .. RESH-1 in registers, RESH .. 17 in LDS behind the ring ----
-    // fragment of (row dydz, cout half i, x tap d): ((dydz * 2 + i) * 3 + d) KiB into the packed weight
     const __amdgpu_buffer_rsrc_t wrsrc = sk::make_rsrc(a.wpk, 54u * 1024u);
-    half8 wres[RESH][3];
-#pragma unroll
-    for (int r = 0; r < RESH; ++r)
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            wres[r][d] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, (r * 3 + d) * 1024, 0));
-    char* wlds = lds + NSLOT * plane_bytes;
-    for (int i = tid; i < (18 - RESH) * 3 * 64; i += 256)
-        *reinterpret_cast<uint4*>(wlds + i * 16) = *reinterpret_cast<const uint4*>(a.wpk + RESH * 3 * 1024 + i * 16);
-    // padding positions of a slot: needed, needed + 1 (128 bytes: slot 0 the GroupNorm scales of a raw source, slot 1 the
-    // bias, slot 2 the GroupNorm shifts) | the zero window NPOSP - 4 .. NPOSP - 1
-    if (tid < NSLOT * 16)
-        *reinterpret_cast<uint4*>(lds + (tid >> 4) * plane_bytes + zero_addr + (tid & 15) * 16) = make_uint4(0, 0, 0, 0);
-    if (tid >= 128 && tid < 160) reinterpret_cast<float*>(lds + plane_bytes + needed * kPosBytes)[tid - 128] = a.bias[tid - 128];
+#include "conv3_px_weights.inc"   // wres, wlds
     if (af && tid >= 64 && tid < 128) {   // (2, 32) coefficients of this batch item
         const int c = tid - 64;
         reinterpret_cast<float*>(lds + (c < 32 ? 0 : 2 * plane_bytes) + needed * kPosBytes)[c & 31] = af[(long long)b * 64 + c];
@@ -1569,118 +1363,12 @@ __global__ void __launch_bounds__(256, 2) conv3_px_kernel(Conv3Args a) {
     // ---- accumulators ----------------------------------------------------------------------------------------
     // element r of [i][j]: cout 16 i + 4 g + r, voxel 16 j + c16 of the wave's column tile
     f32x4 P0[2][2], P1[2][2], Q0[2][2], Q1[2][2];
-    // the bias (the accumulators' initial value) is re-read from its copy in LDS -- padding positions of slot 1 -- at every
-    // reset: eight registers less in the loop
-    const float* lbias = reinterpret_cast<const float*>(lds + plane_bytes + needed * kPosBytes) + 4 * g;
-    auto reset = [&](f32x4 (&o)[2][2]) {
-        o[0][0] = o[0][1] = *reinterpret_cast<const f32x4*>(lbias);
-        o[1][0] = o[1][1] = *reinterpret_cast<const f32x4*>(lbias + 16);
-    };
+#include "conv3_px_steps.inc"   // reset, baddr, wfrag, pair_step
     reset(P0);   // (behind the barrier above: the bias in LDS was written by another wave)
     reset(P1);
     reset(Q0);
     reset(Q1);
     float gsum[2] = {0.0f, 0.0f}, gsq[2] = {0.0f, 0.0f};
-
-    auto baddr = [&](int dydz, int j) -> int {
-        const int dz = dydz % 3 - 1;
-        const int q = q_row + (dydz / 3 - 1) * pitch + dz;
-        int addr = (q * 4 + (g ^ (((q >> 2) & 1) << 1))) * 16 + 1024 * j;
-        if (dz < 0) addr = zlo(j) ? zero_addr + (addr & 255) : addr;
-        if (dz > 0) addr = zhi(j) ? zero_addr + (addr & 255) : addr;
-        return addr;
-    };
-    auto wfrag = [&](int dydz, int i, half8 (&dst)[3]) {
-        if (2 * dydz + i < RESH) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) dst[d] = wres[2 * dydz + i][d];
-        } else {
-            const char* p = wlds + (2 * dydz + i - RESH) * 3 * 1024 + lane * 16;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) dst[d] = *reinterpret_cast<const half8*>(p + d * 1024);
-        }
-    };
-
-    // A step over the input planes A (slot sA) and B = A + 1 (slot sB).  oA1 / oA / oB / oB1: the accumulators of the
-    // output planes A-1, A, B, B+1.  Tap d of a weight row multiplies x_in = x_out + d - 1.
-    auto pair_step = [&](auto SA, auto SB, f32x4 (&oA1)[2][2], f32x4 (&oA)[2][2], f32x4 (&oB)[2][2], f32x4 (&oB1)[2][2]) {
-        // compile-time slots: the 18 tap addresses of the patch (plane-relative, loop-invariant) serve both planes of
-        // every step through the immediate offset of ds_read_b128
-        const char* pa = lds + decltype(SA)::value * plane_bytes;
-        const char* pb = lds + decltype(SB)::value * plane_bytes;
-        half8 bq[2][2][2];   // [buffer][plane][j]: the B fragments of a tap row, one row ahead
-        half8 wq[2][3];      // [buffer][d]: the weight fragments of a half row (cout half i of a tap row), one half row ahead
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ad = baddr(0, j);
-            bq[0][0][j] = *reinterpret_cast<const half8*>(pa + ad);
-            bq[0][1][j] = *reinterpret_cast<const half8*>(pb + ad);
-        }
-        wfrag(0, 0, wq[0]);
-        // The 18 half rows of a step, 12 MFMAs each (192 cycles of the matrix pipe).  The LDS reads of half row h + 1 -- its
-        // three weight fragments when its tap row lives in LDS, and the four B fragments of the next tap row -- are issued
-        // in the FIRST MFMA gaps of half row h, in the order half row h + 1 consumes them, so the youngest read is 80+
-        // cycles old (and not needed before the seventh MFMA) when half row h + 1 starts.  The order is pinned: left to
-        // itself the scheduler spread the reads to the END of the half row and every half row began with an
-        // `s_waitcnt lgkmcnt(0)` on a read issued one MFMA earlier (SQ_WAIT_ANY 38 % of the wave-cycles).
-#pragma unroll
-        for (int dydz = 0; dydz < 9; ++dydz) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int h = dydz * 2 + i;   // its weights sit in wq[h & 1], its B fragments in bq[dydz & 1]
-                const half8(&W)[3] = wq[h & 1];
-                const int ndy = i == 0 ? dydz : dydz + 1, ni = i ^ 1;         // the next half row
-                bool wread = ndy < 9 && 2 * ndy + ni >= RESH;                  // ... reads its weights from LDS
-                bool bread = i == 1 && dydz < 8;                               // ... starts a new tap row: B fragments
-                if (SK_PX_ABL(16) && wread) {   // timing experiment: no LDS weight reads (a resident half row instead)
-                    wread = false;
-                    wfrag((2 * ndy + ni) % RESH / 2, (2 * ndy + ni) % RESH % 2, wq[(h + 1) & 1]);
-                } else if (ndy < 9 && !wread) {
-                    wfrag(ndy, ni, wq[(h + 1) & 1]);                           // resident row: register names only
-                }
-                if (SK_PX_ABL(32) && bread) {   // timing experiment: no B fragment reads after the first tap row
-                    bread = false;
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj) bq[(dydz + 1) & 1][pl][jj] = bq[dydz & 1][pl][jj];
-                }
-                // read k of the next half row, in consumption order: W0, A0, B0, W1, W2, A1, B1
-                auto next_read = [&](int k) {
-                    const char* wp = wlds + (2 * ndy + ni - RESH) * 3 * 1024 + lane * 16;
-                    int kk = k;
-                    if (!wread) kk = (k == 0 ? 1 : k == 1 ? 2 : k == 2 ? 5 : 6);   // B fragments only: A0, B0, A1, B1
-                    if (!bread && kk > 0) kk = (kk == 1 ? 3 : 4);                  // weights only: W0, W1, W2
-                    switch (kk) {
-                        case 0: wq[(h + 1) & 1][0] = *reinterpret_cast<const half8*>(wp); break;
-                        case 1: bq[(dydz + 1) & 1][0][0] = *reinterpret_cast<const half8*>(pa + baddr(dydz + 1, 0)); break;
-                        case 2: bq[(dydz + 1) & 1][1][0] = *reinterpret_cast<const half8*>(pb + baddr(dydz + 1, 0)); break;
-                        case 3: wq[(h + 1) & 1][1] = *reinterpret_cast<const half8*>(wp + 1024); break;
-                        case 4: wq[(h + 1) & 1][2] = *reinterpret_cast<const half8*>(wp + 2048); break;
-                        case 5: bq[(dydz + 1) & 1][0][1] = *reinterpret_cast<const half8*>(pa + baddr(dydz + 1, 1)); break;
-                        default: bq[(dydz + 1) & 1][1][1] = *reinterpret_cast<const half8*>(pb + baddr(dydz + 1, 1)); break;
-                    }
-                };
-                const int nreads = (wread ? 3 : 0) + (bread ? 4 : 0);
-#pragma unroll
-                for (int m = 0; m < 12; ++m) {
-                    const int j = m / 6;
-                    const half8 fa = bq[dydz & 1][0][j], fb = bq[dydz & 1][1][j];
-                    switch (m % 6) {   // tap d of a weight row multiplies x_in = x_out + d - 1
-                        case 0: oB[i][j] = SK_MFMA_16x16x32_T16(W[0], fa, oB[i][j], 0, 0, 0); break;
-                        case 1: oB1[i][j] = SK_MFMA_16x16x32_T16(W[0], fb, oB1[i][j], 0, 0, 0); break;
-                        case 2: oA[i][j] = SK_MFMA_16x16x32_T16(W[1], fa, oA[i][j], 0, 0, 0); break;
-                        case 3: oA1[i][j] = SK_MFMA_16x16x32_T16(W[2], fa, oA1[i][j], 0, 0, 0); break;
-                        case 4: oB[i][j] = SK_MFMA_16x16x32_T16(W[1], fb, oB[i][j], 0, 0, 0); break;
-                        default: oA[i][j] = SK_MFMA_16x16x32_T16(W[2], fb, oA[i][j], 0, 0, 0); break;
-                    }
-                    if (m < nreads) next_read(m);
-                    if (m <= nreads) __builtin_amdgcn_sched_barrier(0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
     // one input plane, a subset of its three x taps (the planes at the ends of an x-chunk)
     auto single_step = [&](auto D0, auto D1, auto D2, int s, f32x4 (&o0)[2][2], f32x4 (&o1)[2][2], f32x4 (&o2)[2][2]) {
         const char* pa = lds + s * plane_bytes;
@@ -1850,12 +1538,12 @@ __global__ void __launch_bounds__(256, 2) conv3_px_kernel(Conv3Args a) {
     SK_T(3)
     SK_T_DUMP(a, w, lane)
 
-    // ---- block-level reduction of the GroupNorm partials (conv3_m16_kernel's) --------------------------------
+    // ---- block-level reduction of the GroupNorm partials --------------------------------
     if (a.partial) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(lds);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 2; ++i) {   // (its own copy of gn_wave_sum16: through the helper this kernel's registers are numbered differently)
             float s = gsum[i], ss = gsq[i];
 #pragma unroll
             for (int m = 8; m > 0; m >>= 1) {
@@ -1867,13 +1555,7 @@ __global__ void __launch_bounds__(256, 2) conv3_px_kernel(Conv3Args a) {
                 red[(w * 8 + 4 * i + g) * 2 + 1] = ss;
             }
         }
-        __syncthreads();
-        if (tid < 16) {
-            float tsum = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) tsum += red[q * 16 + tid];
-            a.partial[((long long)b * nblk + block_in_batch) * 16 + tid] = tsum;
-        }
+        gn_block_sum<1>(red, a.partial, b, nblk, block_in_batch, 16, 0, tid);
     }
 }
 
@@ -1898,65 +1580,11 @@ __global__ void __launch_bounds__(256, 2) conv3_pxm_kernel(Conv3Args a) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // column tile of this wave (32 voxels of the 128-voxel patch)
     const int c16 = lane & 15, g = lane >> 4;
 
-    int blk = blockIdx.x;   // XCD-aware order, see conv3_kernel
-    {
-        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
-        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
-    }
-    const int patch = blk % a.npatch;
-    blk /= a.npatch;
-    const int xc = blk % a.nxc;
-    const int b = blk / a.nxc;
-    const int block_in_batch = xc * a.npatch + patch;
-    const int nblk = a.npatch * a.nxc;
+    int patch, xc, b, block_in_batch, nblk;
+    decode_block(xcd_remap(blockIdx.x), a.npatch, a.nxc, patch, xc, b, block_in_batch, nblk);
 
-    // ---- patch geometry (conv3_m16_kernel's, one column tile per wave) ---------------------------
-    const int pitch = a.pitch;
-    int off, ybase, zbase, q_row, out_vox0, tile_nvox;
-    int svy, svz;             // (y, z) of the voxel this lane STORES: column c16 + 16 (g & 1) of the wave's tile
-    unsigned vflags = 0;      // bit j: voxel 16 j + c16 on the z = 0 face | << 8: on the z = Zt-1 face | << 16: inside the tile
-    auto zlo = [&](int j) { return (vflags >> j) & 1u; };
-    auto zhi = [&](int j) { return (vflags >> (8 + j)) & 1u; };
-    auto vvalid = [&](int j) { return (vflags >> (16 + j)) & 1u; };
-    // linear mode only (Zt <= 40, conv3_m16_kernel's comment): region position q <-> in-plane voxel v0 - Zt - 1 + q
-    const int needed = kPatch + 2 * a.Zt + 2;   // positions a plane really holds; NPOSP rounds it up to a DMA granule
-    {
-        const int v0 = patch * kPatch;
-        off = v0 - a.Zt - 1;
-        ybase = 0;
-        zbase = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int v = v0 + 32 * w + 16 * j + c16;
-            const int vy = v / a.Zt, vz = v - vy * a.Zt;
-            vflags |= (unsigned)(v < a.Yt * a.Zt) << (16 + j);
-            vflags |= (unsigned)(vz == 0) << j;
-            vflags |= (unsigned)(vz == a.Zt - 1) << (8 + j);
-            if (j == 0) q_row = v - off;
-        }
-        out_vox0 = v0 + 32 * w;
-        tile_nvox = a.Yt * a.Zt;
-        const int sv = out_vox0 + c16 + 16 * (g & 1);
-        svy = sv / a.Zt;
-        svz = sv - svy * a.Zt;
-    }
-    const bool sbox = !a.has_box || (svy >= a.box_lo[1] && svy < a.box_hi[1] && svz >= a.box_lo[2] && svz < a.box_hi[2]);
-
-    // ---- LDS-DMA bookkeeping: this lane's slots of a plane (conv3_m16_kernel's swizzle) -----------
-    constexpr int ndma = NPOSP / 16;
-    int d_vox[kMaxDma];
-    const int d_cs = ((lane & 3) ^ (((lane >> 4) & 1) << 1)) * 16;
-#pragma unroll
-    for (int k = 0; k < kMaxDma; ++k) {
-        const int t = w + 4 * k;
-        const int q = (64 * t + lane) >> 2;
-        const int Pq = q + off;
-        const int y = ybase + (Pq >= 0 ? Pq / pitch : -1), z = zbase + (Pq >= 0 ? Pq % pitch : 0);
-        // positions >= needed are padding that the LDS-DMA never writes (d_vox -2: the lane sits out of the instruction):
-        // two of them hold the bias / the GroupNorm coefficients of a raw source, the last four are the zero window
-        const bool ok = (t < ndma) && y >= 0 && y < a.Yt && z >= 0 && z < a.Zt;
-        d_vox[k] = q >= needed ? -2 : (ok ? (y * a.Zt + z) * 128 + d_cs : -1);   // the BYTE offset of this lane's 16-byte piece of the hi halves in a plane of [hi | x8 | lo8] lines
-    }
+    constexpr int kLineBytes = 128;   // the hi halves are the first 64 bytes of a [hi | x8 | lo8] line
+#include "conv3_px_geometry.inc"
 
     const int xa = xc * a.XC;
     const int xb = min(xa + a.XC, a.Xt);
@@ -1990,23 +1618,8 @@ __global__ void __launch_bounds__(256, 2) conv3_pxm_kernel(Conv3Args a) {
             }
         }
     };
-    // ---- weights: half rows (tap row dydz, cout half i) 0 .. RESH-1 in registers, RESH .. 17 in LDS behind the ring ----
-    // fragment of (row dydz, cout half i, x tap d): ((dydz * 2 + i) * 3 + d) KiB into the packed weight
     const __amdgpu_buffer_rsrc_t wrsrc = sk::make_rsrc(a.wpk, (unsigned)a.wpk_bytes);
-    half8 wres[RESH][3];
-#pragma unroll
-    for (int r = 0; r < RESH; ++r)
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            wres[r][d] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, (r * 3 + d) * 1024, 0));
-    char* wlds = lds + NSLOT * plane_bytes;
-    for (int i = tid; i < (18 - RESH) * 3 * 64; i += 256)
-        *reinterpret_cast<uint4*>(wlds + i * 16) = *reinterpret_cast<const uint4*>(a.wpk + RESH * 3 * 1024 + i * 16);
-    // padding positions of a slot: needed, needed + 1 (128 bytes: slot 0 the GroupNorm scales of a raw source, slot 1 the
-    // bias, slot 2 the GroupNorm shifts) | the zero window NPOSP - 4 .. NPOSP - 1
-    if (tid < NSLOT * 16)
-        *reinterpret_cast<uint4*>(lds + (tid >> 4) * plane_bytes + zero_addr + (tid & 15) * 16) = make_uint4(0, 0, 0, 0);
-    if (tid >= 128 && tid < 160) reinterpret_cast<float*>(lds + plane_bytes + needed * kPosBytes)[tid - 128] = a.bias[tid - 128];
+#include "conv3_px_weights.inc"   // wres, wlds
     SK_T_DECL
     issue_half(0, xa - 1, 0);
     issue_half(1, xa, 0);
@@ -2018,118 +1631,12 @@ __global__ void __launch_bounds__(256, 2) conv3_pxm_kernel(Conv3Args a) {
     // ---- accumulators ----------------------------------------------------------------------------------------
     // element r of [i][j]: cout 16 i + 4 g + r, voxel 16 j + c16 of the wave's column tile
     f32x4 P0[2][2], P1[2][2], Q0[2][2], Q1[2][2];
-    // the bias (the accumulators' initial value) is re-read from its copy in LDS -- padding positions of slot 1 -- at every
-    // reset: eight registers less in the loop
-    const float* lbias = reinterpret_cast<const float*>(lds + plane_bytes + needed * kPosBytes) + 4 * g;
-    auto reset = [&](f32x4 (&o)[2][2]) {
-        o[0][0] = o[0][1] = *reinterpret_cast<const f32x4*>(lbias);
-        o[1][0] = o[1][1] = *reinterpret_cast<const f32x4*>(lbias + 16);
-    };
+#include "conv3_px_steps.inc"   // reset, baddr, wfrag, pair_step
     reset(P0);   // (behind the barrier above: the bias in LDS was written by another wave)
     reset(P1);
     reset(Q0);
     reset(Q1);
     float gsum[2] = {0.0f, 0.0f}, gsq[2] = {0.0f, 0.0f};
-
-    auto baddr = [&](int dydz, int j) -> int {
-        const int dz = dydz % 3 - 1;
-        const int q = q_row + (dydz / 3 - 1) * pitch + dz;
-        int addr = (q * 4 + (g ^ (((q >> 2) & 1) << 1))) * 16 + 1024 * j;
-        if (dz < 0) addr = zlo(j) ? zero_addr + (addr & 255) : addr;
-        if (dz > 0) addr = zhi(j) ? zero_addr + (addr & 255) : addr;
-        return addr;
-    };
-    auto wfrag = [&](int dydz, int i, half8 (&dst)[3]) {
-        if (2 * dydz + i < RESH) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) dst[d] = wres[2 * dydz + i][d];
-        } else {
-            const char* p = wlds + (2 * dydz + i - RESH) * 3 * 1024 + lane * 16;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) dst[d] = *reinterpret_cast<const half8*>(p + d * 1024);
-        }
-    };
-
-    // A step over the input planes A (slot sA) and B = A + 1 (slot sB).  oA1 / oA / oB / oB1: the accumulators of the
-    // output planes A-1, A, B, B+1.  Tap d of a weight row multiplies x_in = x_out + d - 1.
-    auto pair_step = [&](auto SA, auto SB, f32x4 (&oA1)[2][2], f32x4 (&oA)[2][2], f32x4 (&oB)[2][2], f32x4 (&oB1)[2][2]) {
-        // compile-time slots: the 18 tap addresses of the patch (plane-relative, loop-invariant) serve both planes of
-        // every step through the immediate offset of ds_read_b128
-        const char* pa = lds + decltype(SA)::value * plane_bytes;
-        const char* pb = lds + decltype(SB)::value * plane_bytes;
-        half8 bq[2][2][2];   // [buffer][plane][j]: the B fragments of a tap row, one row ahead
-        half8 wq[2][3];      // [buffer][d]: the weight fragments of a half row (cout half i of a tap row), one half row ahead
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ad = baddr(0, j);
-            bq[0][0][j] = *reinterpret_cast<const half8*>(pa + ad);
-            bq[0][1][j] = *reinterpret_cast<const half8*>(pb + ad);
-        }
-        wfrag(0, 0, wq[0]);
-        // The 18 half rows of a step, 12 MFMAs each (192 cycles of the matrix pipe).  The LDS reads of half row h + 1 -- its
-        // three weight fragments when its tap row lives in LDS, and the four B fragments of the next tap row -- are issued
-        // in the FIRST MFMA gaps of half row h, in the order half row h + 1 consumes them, so the youngest read is 80+
-        // cycles old (and not needed before the seventh MFMA) when half row h + 1 starts.  The order is pinned: left to
-        // itself the scheduler spread the reads to the END of the half row and every half row began with an
-        // `s_waitcnt lgkmcnt(0)` on a read issued one MFMA earlier (SQ_WAIT_ANY 38 % of the wave-cycles).
-#pragma unroll
-        for (int dydz = 0; dydz < 9; ++dydz) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int h = dydz * 2 + i;   // its weights sit in wq[h & 1], its B fragments in bq[dydz & 1]
-                const half8(&W)[3] = wq[h & 1];
-                const int ndy = i == 0 ? dydz : dydz + 1, ni = i ^ 1;         // the next half row
-                bool wread = ndy < 9 && 2 * ndy + ni >= RESH;                  // ... reads its weights from LDS
-                bool bread = i == 1 && dydz < 8;                               // ... starts a new tap row: B fragments
-                if (SK_PX_ABL(16) && wread) {   // timing experiment: no LDS weight reads (a resident half row instead)
-                    wread = false;
-                    wfrag((2 * ndy + ni) % RESH / 2, (2 * ndy + ni) % RESH % 2, wq[(h + 1) & 1]);
-                } else if (ndy < 9 && !wread) {
-                    wfrag(ndy, ni, wq[(h + 1) & 1]);                           // resident row: register names only
-                }
-                if (SK_PX_ABL(32) && bread) {   // timing experiment: no B fragment reads after the first tap row
-                    bread = false;
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj) bq[(dydz + 1) & 1][pl][jj] = bq[dydz & 1][pl][jj];
-                }
-                // read k of the next half row, in consumption order: W0, A0, B0, W1, W2, A1, B1
-                auto next_read = [&](int k) {
-                    const char* wp = wlds + (2 * ndy + ni - RESH) * 3 * 1024 + lane * 16;
-                    int kk = k;
-                    if (!wread) kk = (k == 0 ? 1 : k == 1 ? 2 : k == 2 ? 5 : 6);   // B fragments only: A0, B0, A1, B1
-                    if (!bread && kk > 0) kk = (kk == 1 ? 3 : 4);                  // weights only: W0, W1, W2
-                    switch (kk) {
-                        case 0: wq[(h + 1) & 1][0] = *reinterpret_cast<const half8*>(wp); break;
-                        case 1: bq[(dydz + 1) & 1][0][0] = *reinterpret_cast<const half8*>(pa + baddr(dydz + 1, 0)); break;
-                        case 2: bq[(dydz + 1) & 1][1][0] = *reinterpret_cast<const half8*>(pb + baddr(dydz + 1, 0)); break;
-                        case 3: wq[(h + 1) & 1][1] = *reinterpret_cast<const half8*>(wp + 1024); break;
-                        case 4: wq[(h + 1) & 1][2] = *reinterpret_cast<const half8*>(wp + 2048); break;
-                        case 5: bq[(dydz + 1) & 1][0][1] = *reinterpret_cast<const half8*>(pa + baddr(dydz + 1, 1)); break;
-                        default: bq[(dydz + 1) & 1][1][1] = *reinterpret_cast<const half8*>(pb + baddr(dydz + 1, 1)); break;
-                    }
-                };
-                const int nreads = (wread ? 3 : 0) + (bread ? 4 : 0);
-#pragma unroll
-                for (int m = 0; m < 12; ++m) {
-                    const int j = m / 6;
-                    const half8 fa = bq[dydz & 1][0][j], fb = bq[dydz & 1][1][j];
-                    switch (m % 6) {   // tap d of a weight row multiplies x_in = x_out + d - 1
-                        case 0: oB[i][j] = SK_MFMA_16x16x32_T16(W[0], fa, oB[i][j], 0, 0, 0); break;
-                        case 1: oB1[i][j] = SK_MFMA_16x16x32_T16(W[0], fb, oB1[i][j], 0, 0, 0); break;
-                        case 2: oA[i][j] = SK_MFMA_16x16x32_T16(W[1], fa, oA[i][j], 0, 0, 0); break;
-                        case 3: oA1[i][j] = SK_MFMA_16x16x32_T16(W[2], fa, oA1[i][j], 0, 0, 0); break;
-                        case 4: oB[i][j] = SK_MFMA_16x16x32_T16(W[1], fb, oB[i][j], 0, 0, 0); break;
-                        default: oA[i][j] = SK_MFMA_16x16x32_T16(W[2], fb, oA[i][j], 0, 0, 0); break;
-                    }
-                    if (m < nreads) next_read(m);
-                    if (m <= nreads) __builtin_amdgcn_sched_barrier(0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
     // The fp8 phase of a step: the same two input planes' 8-bit halves (E slots 2, 3) against the fp8 weight image, tap rows in
     // pairs (conv3_m16_kernel's K = 128 blocks: lane group g >> 1 = the row of the pair, g & 1 = x8 | lo8).
     auto pair_f8 = [&](f32x4 (&oA1)[2][2], f32x4 (&oA)[2][2], f32x4 (&oB)[2][2], f32x4 (&oB1)[2][2]) {
@@ -2267,12 +1774,12 @@ __global__ void __launch_bounds__(256, 2) conv3_pxm_kernel(Conv3Args a) {
     }
     SK_T_DUMP(a, w, lane)
 
-    // ---- block-level reduction of the GroupNorm partials (conv3_m16_kernel's) --------------------------------
+    // ---- block-level reduction of the GroupNorm partials --------------------------------
     if (a.partial) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(lds);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 2; ++i) {   // (its own copy of gn_wave_sum16: through the helper this kernel's registers are numbered differently)
             float s = gsum[i], ss = gsq[i];
 #pragma unroll
             for (int m = 8; m > 0; m >>= 1) {
@@ -2284,13 +1791,7 @@ __global__ void __launch_bounds__(256, 2) conv3_pxm_kernel(Conv3Args a) {
                 red[(w * 8 + 4 * i + g) * 2 + 1] = ss;
             }
         }
-        __syncthreads();
-        if (tid < 16) {
-            float tsum = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) tsum += red[q * 16 + tid];
-            a.partial[((long long)b * nblk + block_in_batch) * 16 + tid] = tsum;
-        }
+        gn_block_sum<1>(red, a.partial, b, nblk, block_in_batch, 16, 0, tid);
     }
 }
 
@@ -2409,14 +1910,12 @@ __global__ void __launch_bounds__(256) gather_gemm_kernel(GatherArgs a) {
             const float ga[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};                     \
             const float gb[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};                     \
             _Pragma("unroll") for (int p = 0; p < PV; ++p) _Pragma("unroll") for (int j = 0; j < 8; ++j) {    \
-                if constexpr (SPLIT) { /* gn_silu_split_kernel's arithmetic, op for op: activate hi + lo, split again */ \
-                    const float y = fmaf(ga[j], (float)bv[p][j] + (float)bvl[p][j], gb[j]);                   \
-                    const float sv = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));                            \
+                if constexpr (SPLIT) { /* gn_silu_split_kernel's arithmetic: activate hi + lo, split again */  \
+                    const float sv = sk::silu_affine(ga[j], (float)bv[p][j] + (float)bvl[p][j], gb[j]);       \
                     bv[p][j] = sk::round_t16(sv);                                                             \
                     bvl[p][j] = (t16)(sv - (float)bv[p][j]);                                                  \
                 } else {                                                                                      \
-                    float y = fmaf(ga[j], (float)bv[p][j], gb[j]);                                            \
-                    bv[p][j] = sk::round_t16(y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)));                   \
+                    bv[p][j] = sk::silu_affine_t16(ga[j], (float)bv[p][j], gb[j]);                            \
                 }                                                                                             \
             }                                                                                                 \
         }                                                                                                     \
@@ -2640,11 +2139,7 @@ __global__ void __launch_bounds__(256, 2) down2_act_kernel(DownArgs a) {
                 const half8 v = *lp;
                 half8 r;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {   // gn_silu_kernel's arithmetic, op for op
-                    const float y = fmaf(ga[e], (float)v[e], gb[e]);
-                    const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-y));
-                    r[e] = sk::round_t16(y * sg);
-                }
+                for (int e = 0; e < 8; ++e) r[e] = sk::silu_affine_t16(ga[e], (float)v[e], gb[e]);
                 *lp = r;
                 if (a.writeback && vin[j] >= 0)
                     *reinterpret_cast<half8*>(inb + (vin[j] + toff) * (CIN * 2) + csrc * 16) = r;
@@ -2871,9 +2366,8 @@ __global__ void __launch_bounds__(256, 2) down2_act_split_kernel(DownArgs a) {
                     const half8 vh = *lph, vl = *lpl;
                     half8 rh, rl;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {   // gn_silu_split_kernel's arithmetic, op for op
-                        const float y = fmaf(ga[e], (float)vh[e] + (float)vl[e], gb[e]);
-                        const float sv = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));
+                    for (int e = 0; e < 8; ++e) {   // gn_silu_split_kernel's arithmetic
+                        const float sv = sk::silu_affine(ga[e], (float)vh[e] + (float)vl[e], gb[e]);
                         rh[e] = sk::round_t16(sv);
                         rl[e] = (t16)(sv - (float)rh[e]);
                     }
@@ -2892,8 +2386,7 @@ __global__ void __launch_bounds__(256, 2) down2_act_split_kernel(DownArgs a) {
                         float xs[8], ls[8];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const float y = fmaf(ga[e], (float)vh[e] + (float)vl[e], gb[e]);
-                            const float sv = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));
+                            const float sv = sk::silu_affine(ga[e], (float)vh[e] + (float)vl[e], gb[e]);
                             xs[e] = fminf(fmaxf(sv * 16.0f, -448.0f), 448.0f);
                             ls[e] = fminf(fmaxf((sv - (float)rh[e]) * 32768.0f, -448.0f), 448.0f);
                         }
@@ -3082,17 +2575,23 @@ constexpr int kMix8Fp16Bytes = 54 * 1024, kMix8Fp8Bytes = 5 * 2 * 3 * 2048;
 inline int mix8_fp16_bytes(int cout, int cin) { return (cout / 32) * (cin / 32) * kMix8Fp16Bytes; }
 inline int mix8_fp8_bytes(int cout, int cin) { return cout == 32 ? kMix8Fp8Bytes : (cin / 32) * 27 * (cout / 32) * 2048; }
 
-template <int XS, int RES = 0, bool SPLIT = false, int WL = 0, bool MIX8 = false>
-int launch_conv3_m16(const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    auto kern = conv3_m16_kernel<32, XS, RES, SPLIT, WL, MIX8>;
-    const size_t lds = p.lds + (RES > 0 ? WL * 6144 : 0);   // the ring + the tap rows kept in LDS behind it
-    if (lds > 48 * 1024)
-        SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-    unsigned grid = (unsigned)(p.npatch * p.nxc * a.B);
+// One launch of 256-thread workgroups; more than 48 KiB of dynamic LDS needs the attribute.
+template <class Args>
+int launch(void (*kern)(Args), unsigned grid, size_t lds, const Args& a, hipStream_t stream) {
+    if (lds > 48 * 1024) SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     kern<<<grid, 256, lds, stream>>>(a);
     SK_CHECK_LAUNCH();
     return SK_OK;
+}
+// a 3x3x3 kernel: one workgroup per (batch item, x-chunk, patch)
+int launch_conv3_grid(void (*kern)(Conv3Args), size_t lds, const Conv3Args& a, const Plan& p, hipStream_t stream) {
+    return launch(kern, (unsigned)(p.npatch * p.nxc * a.B), lds, a, stream);
+}
+
+template <int XS, int RES = 0, bool SPLIT = false, int WL = 0, bool MIX8 = false>
+int launch_conv3_m16(const Conv3Args& a, const Plan& p, hipStream_t stream) {
+    // the ring + the tap rows kept in LDS behind it
+    return launch_conv3_grid(conv3_m16_kernel<32, XS, RES, SPLIT, WL, MIX8>, p.lds + (RES > 0 ? WL * 6144 : 0), a, p, stream);
 }
 
 // conv3_px_kernel is built for the plane geometry of the production tile: linear mode with 176 positions per plane
@@ -3106,39 +2605,13 @@ int launch_conv3_m16(const Conv3Args& a, const Plan& p, hipStream_t stream) {
 constexpr int kPxResidentHalfRows = SK_PX_RESH;   // (tools/ A/B: -DSK_PX_RESH=6 is the 80 KiB form)
 constexpr int kPxPositions = 176;
 constexpr size_t kPxLds = (size_t)4 * kPxPositions * kPosBytes + (size_t)(18 - kPxResidentHalfRows) * 3072;
+static_assert(kPxLds <= 80 * 1024, "two workgroups per CU");
 // padding positions behind the `needed` ones: 2 (bias / GroupNorm coefficients) + the 4-position zero window
-bool conv3_px_covers(const Plan& p, int Zt, bool /*raw*/) { return p.mode == 0 && p.nposp == kPxPositions && kPatch + 2 * Zt + 2 + 6 <= kPxPositions; }
-
-int launch_conv3_px(const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    auto kern = conv3_px_kernel<kPxResidentHalfRows, kPxPositions>;
-    const size_t lds = kPxLds;
-    static_assert(kPxLds <= 80 * 1024, "two workgroups per CU");
-    SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    unsigned grid = (unsigned)(p.npatch * p.nxc * a.B);
-    kern<<<grid, 256, lds, stream>>>(a);
-    SK_CHECK_LAUNCH();
-    return SK_OK;
-}
-
-int launch_conv3_pxm(const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    auto kern = conv3_pxm_kernel<kPxResidentHalfRows, kPxPositions>;
-    SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPxLds));
-    unsigned grid = (unsigned)(p.npatch * p.nxc * a.B);
-    kern<<<grid, 256, kPxLds, stream>>>(a);
-    SK_CHECK_LAUNCH();
-    return SK_OK;
-}
+bool conv3_px_covers(const Plan& p, int Zt) { return p.mode == 0 && p.nposp == kPxPositions && kPatch + 2 * Zt + 2 + 6 <= kPxPositions; }
 
 template <int COUT, int XS, int RES = 0, bool SPLIT = false, bool MIX8 = false>
 int launch_conv3(const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    auto kern = conv3_kernel<COUT, XS, RES, SPLIT, MIX8>;
-    if (p.lds > 48 * 1024)
-        SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)p.lds));
-    unsigned grid = (unsigned)(p.npatch * p.nxc * a.B);
-    kern<<<grid, 256, p.lds, stream>>>(a);
-    SK_CHECK_LAUNCH();
-    return SK_OK;
+    return launch_conv3_grid(conv3_kernel<COUT, XS, RES, SPLIT, MIX8>, p.lds, a, p, stream);
 }
 
 }  // namespace
@@ -3228,28 +2701,12 @@ static int launch_down2(const void* in, const float* affine, int writeback, cons
     a.writeback = writeback;
     a.nblk = sk_conv3d_num_blocks(B, ox, oy, oz, cout, 2);   // 256 (cout 64) / 128 (cout 128) voxels per block: NV
     const int lds = 2 * 32768 + 4 * kPadBytes;
-    const unsigned grid = (unsigned)(a.nblk * B);
-    if (split) {
-        if (cin == 32) {
-            auto kern = down2_act_split_kernel<64, 32>;
-            SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            kern<<<grid, 256, lds, stream>>>(a);
-        } else {
-            auto kern = down2_act_split_kernel<128, 64>;
-            SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            kern<<<grid, 256, lds, stream>>>(a);
-        }
-    } else if (cin == 32) {
-        auto kern = down2_act_kernel<64, 32>;
-        SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        kern<<<grid, 256, lds, stream>>>(a);
-    } else {
-        auto kern = down2_act_kernel<128, 64>;
-        SK_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        kern<<<grid, 256, lds, stream>>>(a);
-    }
-    SK_CHECK_LAUNCH();
-    return SK_OK;
+    void (*kern)(DownArgs);
+    if (split)
+        kern = cin == 32 ? down2_act_split_kernel<64, 32> : down2_act_split_kernel<128, 64>;
+    else
+        kern = cin == 32 ? down2_act_kernel<64, 32> : down2_act_kernel<128, 64>;
+    return launch(kern, (unsigned)(a.nblk * B), lds, a, stream);
 }
 
 static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
@@ -3363,11 +2820,11 @@ static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, c
             a.wpk_bytes = a.w8_off + mix8_fp8_bytes(cout, cin);
             a.w8_scale = 0x01010101 * (127 - w8_scale_exp);
             if (cout == 32) {
-                bool use_pxm = conv3_px_covers(p, oz, false);
+                bool use_pxm = conv3_px_covers(p, oz);
 #ifdef SK_TUNING
                 if (getenv("SK_CONV_NO_PX")) use_pxm = false;   // A/B: conv3_m16_kernel's mix8 form
 #endif
-                if (use_pxm) return launch_conv3_pxm(a, p, stream);
+                if (use_pxm) return launch_conv3_grid(conv3_pxm_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, a, p, stream);
                 return p.xs == 3 ? launch_conv3_m16<3, 0, true, 0, true>(a, p, stream) : launch_conv3_m16<4, 0, true, 0, true>(a, p, stream);
             }
             if (cout == 64) return p.xs == 3 ? launch_conv3<64, 3, 0, true, true>(a, p, stream) : launch_conv3<64, 4, 0, true, true>(a, p, stream);
@@ -3378,11 +2835,11 @@ static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, c
             if (cout == 64) return p.xs == 3 ? launch_conv3<64, 3, 0, true>(a, p, stream) : launch_conv3<64, 4, 0, true>(a, p, stream);
             return launch_conv3<128, 2, 0, true>(a, p, stream);
         }
-        bool use_px = cout == 32 && a.nchunks == 1 && n_src == 1 && !srcs[0].upsample && conv3_px_covers(p, oz, a.act[0] != nullptr);
+        bool use_px = cout == 32 && a.nchunks == 1 && n_src == 1 && !srcs[0].upsample && conv3_px_covers(p, oz);
 #ifdef SK_TUNING
         if (getenv("SK_CONV_NO_PX")) use_px = false;   // A/B: the single-chunk COUT-32 layers on conv3_m16_kernel
 #endif
-        if (use_px) return launch_conv3_px(a, p, stream);
+        if (use_px) return launch_conv3_grid(conv3_px_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, a, p, stream);
         if (cout == 32) {   // 16x16x32 kernel
             if (p.xs == 3) return launch_conv3_m16<3>(a, p, stream);
             if (a.nchunks == 1 && !a.ablate) {   // single chunk: 3 tap rows in registers, 2 more in LDS where they fit
@@ -3418,28 +2875,19 @@ static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, c
     g.Cin = srcs[0].c;
     g.ksize = ksize;
     g.nblk = sk_conv3d_num_blocks(B, ox, oy, oz, cout, ksize);
-    unsigned grid = (unsigned)(g.nblk * B);
     const int nsteps = ksize * ksize * ksize * (g.Cin / 16);
     SK_CHECK_ARG(g.Cin <= 128 && nsteps % 2 == 0, "sk_conv3d: ksize %d needs 32 <= cin <= 128 (got %d)", ksize, g.Cin);
     const bool deep = nsteps % 4 == 0;  // pipeline depth 4 (2 only for the 32-channel pointwise case)
-    if (split) {   // depth 2: twice the fragments in flight per step
-        if (cout == 32)
-            gather_gemm_kernel<32, 2, 2, true><<<grid, 256, 0, stream>>>(g);
-        else if (cout == 64)
-            gather_gemm_kernel<64, 2, 2, true><<<grid, 256, 0, stream>>>(g);
-        else
-            gather_gemm_kernel<128, 1, 2, true><<<grid, 256, 0, stream>>>(g);
-        SK_CHECK_LAUNCH();
-        return SK_OK;
-    }
-    if (cout == 32)
-        deep ? gather_gemm_kernel<32, 2, 4><<<grid, 256, 0, stream>>>(g) : gather_gemm_kernel<32, 2, 2><<<grid, 256, 0, stream>>>(g);
+    void (*kern)(GatherArgs);
+    if (split)   // depth 2: twice the fragments in flight per step
+        kern = cout == 32 ? gather_gemm_kernel<32, 2, 2, true> : cout == 64 ? gather_gemm_kernel<64, 2, 2, true> : gather_gemm_kernel<128, 1, 2, true>;
+    else if (cout == 32)
+        kern = deep ? gather_gemm_kernel<32, 2, 4> : gather_gemm_kernel<32, 2, 2>;
     else if (cout == 64)
-        deep ? gather_gemm_kernel<64, 2, 4><<<grid, 256, 0, stream>>>(g) : gather_gemm_kernel<64, 2, 2><<<grid, 256, 0, stream>>>(g);
+        kern = deep ? gather_gemm_kernel<64, 2, 4> : gather_gemm_kernel<64, 2, 2>;
     else
-        deep ? gather_gemm_kernel<128, 1, 4><<<grid, 256, 0, stream>>>(g) : gather_gemm_kernel<128, 1, 2><<<grid, 256, 0, stream>>>(g);
-    SK_CHECK_LAUNCH();
-    return SK_OK;
+        kern = deep ? gather_gemm_kernel<128, 1, 4> : gather_gemm_kernel<128, 1, 2>;
+    return launch(kern, (unsigned)(g.nblk * B), 0, g, stream);
 }
 
 int sk_conv3d(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,

@@ -36,15 +36,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.h"
+#include "conv3_device.h"
 
 namespace {
 
-typedef t16 half8 __attribute__((ext_vector_type(8)));
-typedef t16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kPosBytes = 64;    // 32 channels x fp16
 constexpr int kMaxDma = 3;       // LDS-DMA wave-instructions per fine plane per wave (nposp <= 192)
 constexpr int kMaxDmaL = 2;      // per low-resolution plane per wave (nposl <= 128)
 constexpr int kSkipFrags = 54;   // fragments of a skip chunk: [dydz 9][cout half 2][dx 3]
@@ -72,18 +67,6 @@ struct UpfArgs {
 
 constexpr int kSkipFrags8 = 30;  // MIX8, 2 KiB fp8 fragments of a skip chunk: [tap-row pair 5][cout half 2][dx 3]
 constexpr int kUpFrags8 = 64;    // of an upsampled chunk: [class 4][ty 2][cout half 2][px 2][tx 2] (K = two tz taps)
-
-// Phase timing (-DSK_TIMING build only): per wave, cycles between the marks of a phase
-#ifdef SK_TIMING
-#define SK_T_DECL long long tacc_[sk::kTimingSlots] = {0}; long long tprev_ = __builtin_readcyclecounter();
-#define SK_T(i) { const long long t_ = __builtin_readcyclecounter(); tacc_[i] += t_ - tprev_; tprev_ = t_; }
-#define SK_T_DUMP(a, w, lane) if ((a).dbg && blockIdx.x < sk::kTimingBlocks && (w) < 4 && (lane) == 0) { \
-        for (int i_ = 0; i_ < sk::kTimingSlots; ++i_) (a).dbg[((long long)blockIdx.x * 4 + (w)) * sk::kTimingSlots + i_] = tacc_[i_]; }
-#else
-#define SK_T_DECL
-#define SK_T(i)
-#define SK_T_DUMP(a, w, lane)
-#endif
 
 #define SK_UPF_NAME conv3_upf_kernel
 #define SK_UPF_MIX8 0
@@ -151,11 +134,7 @@ __global__ void __launch_bounds__(256, 2) conv3_upf_px_kernel(UpfArgs a) {
     const int py = w >> 1, pz = w & 1;   // parity class of this wave's output voxels
     const int c16 = lane & 15, g = lane >> 4;
 
-    int blk = blockIdx.x;   // XCD-aware order (conv3d.hip); the two cout halves of a region are neighbours in it
-    {
-        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
-        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
-    }
+    int blk = xcd_remap(blockIdx.x);   // the two cout halves of a region are neighbours in the XCD-aware order
     const int h = blk & 1;   // cout half
     blk >>= 1;
     const int patch = blk % a.npatch;

@@ -29,18 +29,8 @@ __global__ void __launch_bounds__(256, 2) SK_UPF_NAME(UpfArgs a) {
     const int py = w >> 1, pz = w & 1;   // parity class of this wave's output voxels
     const int c16 = lane & 15, g = lane >> 4;
 
-    // XCD-aware workgroup order (conv3d.hip)
-    int blk = blockIdx.x;
-    {
-        const int nwg = gridDim.x, xcd = blk & 7, qn = nwg >> 3, rn = nwg & 7;
-        blk = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blk >> 3);
-    }
-    const int patch = blk % a.npatch;
-    blk /= a.npatch;
-    const int xc = blk % a.nxc;
-    const int b = blk / a.nxc;
-    const int block_in_batch = xc * a.npatch + patch;
-    const int nblk = a.npatch * a.nxc;
+    int patch, xc, b, block_in_batch, nblk;
+    decode_block(xcd_remap(blockIdx.x), a.npatch, a.nxc, patch, xc, b, block_in_batch, nblk);
 
     const int Zl = a.Zl, Zt = a.Zt;
     const int yl0 = patch * a.K;             // first low-resolution row of this workgroup
@@ -601,31 +591,12 @@ __global__ void __launch_bounds__(256, 2) SK_UPF_NAME(UpfArgs a) {
         }
     }
 
-    SK_T_DUMP(a, w, lane)
+    SK_T_DUMP_ROW(a, blockIdx.x < sk::kTimingBlocks, blockIdx.x, w, lane)
     // ---- block-level reduction of the GroupNorm partials ------------------------------------
     if (a.partial) {
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(lds);  // [4 waves][8 quads][2]
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float s = gsum[i], ss = gsq[i];
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) {
-                s += __shfl_xor(s, m);
-                ss += __shfl_xor(ss, m);
-            }
-            if (c16 == 0) {
-                red[(w * 8 + 4 * i + g) * 2 + 0] = s;
-                red[(w * 8 + 4 * i + g) * 2 + 1] = ss;
-            }
-        }
-        __syncthreads();
-        if (tid < 16) {
-            float t = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) t += red[q * 16 + tid];
-            a.partial[((long long)b * nblk + block_in_batch) * a.pstride + a.poff + tid] = t;
-        }
+        float* red = reinterpret_cast<float*>(lds);
+        gn_wave_sum16(red, gsum, gsq, w, c16, g);
+        gn_block_sum<1>(red, a.partial, b, nblk, block_in_batch, a.pstride, a.poff, tid);
     }
 }
 

@@ -63,9 +63,8 @@ __host__ __device__ inline int gnb_blocks(long long voxels, int C) {
 
 // mixed-precision kernels: hardware exp2 / rcp (relative error ~1e-6, far below the fp16 operands they feed); the
 // fp32 parity kernels keep expf and the IEEE division
-__device__ inline float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ inline float silu_grad_fast(float u) {
-    const float s = sigmoid_fast(u);
+    const float s = sk::sigmoid_fast(u);
     return s * (1.0f + u * (1.0f - s));
 }
 
@@ -739,8 +738,7 @@ __global__ void __launch_bounds__(256) gn_silu_f16_kernel(const t16* __restrict_
         float z[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float u = fmaf(ga[j], (float)yv[j], gb[j]);
-            z[j] = u * sigmoid_fast(u);
+            z[j] = sk::silu_affine(ga[j], (float)yv[j], gb[j]);
             o[j] = (t16)z[j];
         }
         *reinterpret_cast<half8_t*>(z16 + i) = o;
@@ -2407,6 +2405,32 @@ int fill_loss_args(LossArgs& a, const float* logits, const float* masks, const f
     return 0;
 }
 
+// The source descriptors of a weight-gradient launch (WgradArgs: fp32 sources, Wgrad16Args: 16-bit): extents of each
+// source at its own resolution, the channel total, and the checks both entry points make (`fn` names the caller in the
+// messages); one batch item of a source must fit 32-bit byte offsets.
+template <class Args>
+int wgrad_fill_srcs(Args& a, const char* fn, const sk_conv_src* srcs, int n_src, int ox, int oy, int oz, int ksize) {
+    a.nsrc = n_src;
+    for (int i = 0; i < n_src; ++i) {
+        SK_CHECK_ARG(srcs[i].data && srcs[i].c > 0 && srcs[i].affine == nullptr, "%s: bad source %d", fn, i);
+        SK_CHECK_ARG(n_src == 1 || srcs[i].c % 32 == 0, "%s: two sources need c %% 32 == 0", fn);
+        int up = srcs[i].upsample ? 1 : 0;
+        SK_CHECK_ARG(!up || (ksize == 3 && ox % 2 == 0 && oy % 2 == 0 && oz % 2 == 0),
+                     "%s: upsampled source needs ksize 3 and even output extents", fn);
+        a.src[i].data = (decltype(a.src[i].data))srcs[i].data;
+        a.src[i].C = srcs[i].c;
+        a.src[i].up = up;
+        int s = (ksize == 3) ? 1 : ksize;
+        a.src[i].Xs = up ? ox / 2 : ox * s;
+        a.src[i].Ys = up ? oy / 2 : oy * s;
+        a.src[i].Zs = up ? oz / 2 : oz * s;
+        a.cin += srcs[i].c;
+        SK_CHECK_ARG((long long)a.src[i].Xs * a.src[i].Ys * a.src[i].Zs * a.src[i].C * (long long)sizeof(*a.src[i].data) < (1LL << 32),
+                     "%s: source %d of one batch item must be < 4 GiB", fn, i);
+    }
+    return SK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2557,22 +2581,7 @@ int sk_train_conv_wgrad(const sk_conv_src* srcs, int n_src, const float* dy, int
     SK_CHECK_ARG(ksize == 1 || ksize == 2 || ksize == 3, "sk_train_conv_wgrad: ksize must be 1, 2 or 3");
     SK_CHECK_ARG(B >= 1 && ox >= 1 && oy >= 1 && oz >= 1 && cout >= 1, "sk_train_conv_wgrad: bad extents");
     WgradArgs a{};
-    a.nsrc = n_src;
-    for (int i = 0; i < n_src; ++i) {
-        SK_CHECK_ARG(srcs[i].data && srcs[i].c > 0 && srcs[i].affine == nullptr, "sk_train_conv_wgrad: bad source %d", i);
-        SK_CHECK_ARG(n_src == 1 || srcs[i].c % 32 == 0, "sk_train_conv_wgrad: two sources need c %% 32 == 0");
-        int up = srcs[i].upsample ? 1 : 0;
-        SK_CHECK_ARG(!up || (ksize == 3 && ox % 2 == 0 && oy % 2 == 0 && oz % 2 == 0),
-                     "sk_train_conv_wgrad: upsampled source needs ksize 3 and even output extents");
-        a.src[i].data = (const float*)srcs[i].data;
-        a.src[i].C = srcs[i].c;
-        a.src[i].up = up;
-        int s = (ksize == 3) ? 1 : ksize;
-        a.src[i].Xs = up ? ox / 2 : ox * s;
-        a.src[i].Ys = up ? oy / 2 : oy * s;
-        a.src[i].Zs = up ? oz / 2 : oz * s;
-        a.cin += srcs[i].c;
-    }
+    if (const int e = wgrad_fill_srcs(a, "sk_train_conv_wgrad", srcs, n_src, ox, oy, oz, ksize)) return e;
     a.dy = dy;
     a.B = B;
     a.ox = ox;
@@ -2584,9 +2593,6 @@ int sk_train_conv_wgrad(const sk_conv_src* srcs, int n_src, const float* dy, int
     a.ncit = (a.cin + 31) / 32;
     wgrad_plan(B, ox, oy, oz, cout, a.cin, ksize, &a.nchunk, &a.nchunk_b, &a.chunk, &a.ngroup);
     SK_CHECK_ARG((long long)ox * oy * oz * cout * 4 < (1LL << 32), "sk_train_conv_wgrad: dy of one batch item must be < 4 GiB");
-    for (int i = 0; i < n_src; ++i)
-        SK_CHECK_ARG((long long)a.src[i].Xs * a.src[i].Ys * a.src[i].Zs * a.src[i].C * 4 < (1LL << 32),
-                     "sk_train_conv_wgrad: source %d of one batch item must be < 4 GiB", i);
     const long long nw = (long long)cout * a.cin * ksize * ksize * ksize;
     a.part = workspace;
     a.part_bias = dbias ? workspace + (long long)a.nchunk * nw : nullptr;
@@ -2663,24 +2669,7 @@ int sk_train_conv_wgrad_f16(const sk_conv_src* srcs, int n_src, const void* dy, 
     SK_CHECK_ARG(ksize == 1 || ksize == 2 || ksize == 3, "sk_train_conv_wgrad_f16: ksize must be 1, 2 or 3");
     SK_CHECK_ARG(B >= 1 && ox >= 1 && oy >= 1 && oz >= 1 && cout >= 1, "sk_train_conv_wgrad_f16: bad extents");
     Wgrad16Args a{};
-    a.nsrc = n_src;
-    for (int i = 0; i < n_src; ++i) {
-        SK_CHECK_ARG(srcs[i].data && srcs[i].c > 0 && srcs[i].affine == nullptr, "sk_train_conv_wgrad_f16: bad source %d", i);
-        SK_CHECK_ARG(n_src == 1 || srcs[i].c % 32 == 0, "sk_train_conv_wgrad_f16: two sources need c %% 32 == 0");
-        int up = srcs[i].upsample ? 1 : 0;
-        SK_CHECK_ARG(!up || (ksize == 3 && ox % 2 == 0 && oy % 2 == 0 && oz % 2 == 0),
-                     "sk_train_conv_wgrad_f16: upsampled source needs ksize 3 and even output extents");
-        a.src[i].data = (const t16*)srcs[i].data;
-        a.src[i].C = srcs[i].c;
-        a.src[i].up = up;
-        int s = (ksize == 3) ? 1 : ksize;
-        a.src[i].Xs = up ? ox / 2 : ox * s;
-        a.src[i].Ys = up ? oy / 2 : oy * s;
-        a.src[i].Zs = up ? oz / 2 : oz * s;
-        a.cin += srcs[i].c;
-        SK_CHECK_ARG((long long)a.src[i].Xs * a.src[i].Ys * a.src[i].Zs * a.src[i].C * 2 < (1LL << 32),
-                     "sk_train_conv_wgrad_f16: source %d of one batch item must be < 4 GiB", i);
-    }
+    if (const int e = wgrad_fill_srcs(a, "sk_train_conv_wgrad_f16", srcs, n_src, ox, oy, oz, ksize)) return e;
     SK_CHECK_ARG((long long)ox * oy * oz * cout * 2 < (1LL << 32), "sk_train_conv_wgrad_f16: dy of one batch item must be < 4 GiB");
     a.dy = (const t16*)dy;
     a.B = B;

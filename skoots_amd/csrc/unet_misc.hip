@@ -233,8 +233,7 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
                 if (MODE == 2) {
                     r[k] = acc[k];
                 } else {
-                    const float yv = fmaf(ga[k], acc[k], gb[k]);
-                    r[k] = yv * __builtin_amdgcn_rcpf(1.0f + __expf(-yv));
+                    r[k] = sk::silu_affine(ga[k], acc[k], gb[k]);
                 }
             }
             char* pad = tpad + w * kPadW;
@@ -418,11 +417,7 @@ __global__ void __launch_bounds__(256) gn_silu_kernel(t16* __restrict__ x,
         half8 v = __builtin_nontemporal_load(&p[i]);
         half8 r;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float y = fmaf(ga[j], (float)v[j], gb[j]);
-            float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-y));
-            r[j] = sk::round_t16(y * sg);
-        }
+        for (int j = 0; j < 8; ++j) r[j] = sk::silu_affine_t16(ga[j], (float)v[j], gb[j]);
         __builtin_nontemporal_store(r, &p[i]);
     }
 }
@@ -449,9 +444,7 @@ __global__ void __launch_bounds__(256) gn_silu_split_kernel(t16* __restrict__ x,
         half8 rh, rl;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float xv = (float)vh[j] + (float)vl[j];
-            const float y = fmaf(ga[j], xv, gb[j]);
-            const float sv = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));
+            const float sv = sk::silu_affine(ga[j], (float)vh[j] + (float)vl[j], gb[j]);
             rh[j] = sk::round_t16(sv);   // the product rounded to fp32 first: the same bits wherever this activation is fused
             rl[j] = (t16)(sv - (float)rh[j]);
         }
@@ -486,9 +479,7 @@ __global__ void __launch_bounds__(256) gn_silu_mix8_kernel(t16* __restrict__ x, 
         float xs[8], ls[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {   // gn_silu_split_kernel's arithmetic up to the split
-            const float xv = (float)vh[j] + (float)vl[j];
-            const float y = fmaf(ga[j], xv, gb[j]);
-            const float sv = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));
+            const float sv = sk::silu_affine(ga[j], (float)vh[j] + (float)vl[j], gb[j]);
             rh[j] = sk::round_t16(sv);
             xs[j] = fminf(fmaxf(sv * 16.0f, -448.0f), 448.0f);
             ls[j] = fminf(fmaxf((sv - (float)rh[j]) * 32768.0f, -448.0f), 448.0f);
@@ -581,18 +572,14 @@ __global__ void __launch_bounds__(256) heads_kernel(HeadArgs a) {
                 for (int j = 0; j < 8; ++j) {
                     float y = (float)raw[j] + (float)rlo[j];
                     if (a.affine) {
-                        y = fmaf(ga[ks][j], y, gb[ks][j]);
-                        y = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));
+                        y = sk::silu_affine(ga[ks][j], y, gb[ks][j]);
                     }
                     raw[j] = (t16)y;
                     bl[ks][j] = (t16)(y - (float)raw[j]);
                 }
             } else if (a.affine) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float y = fmaf(ga[ks][j], (float)raw[j], gb[ks][j]);
-                    raw[j] = sk::round_t16(y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)));
-                }
+                for (int j = 0; j < 8; ++j) raw[j] = sk::silu_affine_t16(ga[ks][j], (float)raw[j], gb[ks][j]);
             }
             bf[ks] = raw;
         }
@@ -610,9 +597,9 @@ __global__ void __launch_bounds__(256) heads_kernel(HeadArgs a) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k)  // tanh(x) = 1 - 2 / (1 + e^{2x})
                     ob[k * a.n + v] = (t16)(1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * acc[k])));
-                ob[3 * a.n + v] = (t16)(__builtin_amdgcn_rcpf(1.0f + __expf(-acc[3])));
+                ob[3 * a.n + v] = (t16)sk::sigmoid_fast(acc[3]);
             } else {
-                ob[4 * a.n + v] = (t16)(__builtin_amdgcn_rcpf(1.0f + __expf(-acc[0])));
+                ob[4 * a.n + v] = (t16)sk::sigmoid_fast(acc[0]);
             }
         }
     }
