@@ -747,6 +747,43 @@ int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t stream_bytes, 
                        int64_t* dst_offsets, uint8_t* all_zero, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Reading eval()'s files back: inflate decoder for zarr chunks and TIFF strips
+ * ------------------------------------------------------------------------ */
+
+/* status[i] of sk_inflate_streams: 0, or why stream i was refused */
+#define SK_INFLATE_E_HEADER 1        /* RFC 1950 header: method not 8, window above 32 KiB, check bits wrong, or FDICT set */
+#define SK_INFLATE_E_BLOCK_TYPE 2    /* reserved block type 3 */
+#define SK_INFLATE_E_STORED 3        /* stored block: LEN is not the complement of NLEN */
+#define SK_INFLATE_E_CODES 4         /* dynamic block: over-subscribed or incomplete code-length set, bad repeat, no end-of-block code */
+#define SK_INFLATE_E_SYMBOL 5        /* bits that are no code of the block, literal/length symbol 286 / 287, distance code 30 / 31 */
+#define SK_INFLATE_E_DISTANCE 6      /* distance reaches before the start of the output */
+#define SK_INFLATE_E_INPUT 7         /* input exhausted before the stream (and its Adler-32) ended */
+#define SK_INFLATE_E_OUTPUT_LONG 8   /* the stream holds more bytes than expected */
+#define SK_INFLATE_E_OUTPUT_SHORT 9  /* the stream ended with fewer bytes than expected */
+#define SK_INFLATE_E_ADLER 10        /* Adler-32 of the output differs from the trailer */
+#define SK_INFLATE_E_RANGE 11        /* src_offsets / dst_offsets of the stream are negative or decreasing */
+
+/* Inflates n_streams independent streams.  Stream i is src[src_offsets[i] .. src_offsets[i+1]) (any alignment) and
+ * must inflate to exactly dst_offsets[i+1] - dst_offsets[i] bytes at dst + dst_offsets[i]; both offset arrays live
+ * on the device (n_streams + 1 entries, 8-byte aligned).  wrapper: 0 = raw RFC 1951, 1 = RFC 1950 (header checked,
+ * FDICT refused, Adler-32 verified).  status[i] (device) = 0 or one SK_INFLATE_E_* code; a failed stream never stops
+ * the others.  Replaces zlib.decompress per chunk / strip on the host (the reference leaves reading to zarr / skimage,
+ * eval.py:61, 160-176).  All three block types, any number of blocks, empty stored blocks, every window size; bytes
+ * after the end of a stream are ignored.  status[i] == 0 exactly when zlib inflates the stream without error to its
+ * end and to the expected number of bytes (zlib's rules for code-length sets included).  The decoder reads nothing
+ * outside a stream's src range and writes nothing outside its dst range whatever the bytes are; of a refused stream
+ * the dst range holds an undefined prefix.  One wave per stream: the speed comes from many streams per call.  The
+ * output depends on the stream alone.  Arguments are checked before the launch. */
+int sk_inflate_streams(const uint8_t* src, const int64_t* src_offsets, int n_streams, uint8_t* dst,
+                       const int64_t* dst_offsets, int wrapper, int32_t* status, void* stream);
+
+/* Undoes TIFF predictor 2 (horizontal differencing) in place: n_rows rows of row_pixels pixels,
+ * samples_per_pixel (1..16) samples of bytes_per_sample (1, 2, 4) little-endian bytes each; sums wrap modulo
+ * 2^bits as libtiff's do.  rows is aligned to its samples. */
+int sk_tiff_undo_predictor(void* rows, int64_t n_rows, int row_pixels, int samples_per_pixel, int bytes_per_sample,
+                           void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

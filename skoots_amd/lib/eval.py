@@ -242,13 +242,27 @@ def _write_mask_tif(path: str, mask_zxy: np.ndarray) -> None:
     pages[0].save(path, save_all=True, append_images=pages[1:], compression="tiff_adobe_deflate")
 
 
+# Whether eval() reads its files -- the image and, with used_cached_data, the two zarr stores -- through the device
+# readers (tiff.read_stack, zarr_store.load_device: compressed bytes are uploaded and inflated by csrc/inflate.hip) or
+# through the host readers and an upload.  The results are the same; DESIGN.md section 16 has the timings behind the default.
+READ_ON_DEVICE = False
+
+
+def _to_f32(t: torch.Tensor) -> torch.Tensor:
+    """Integer samples as float32, what ``ndarray.astype(np.float32)`` gives; uint16 goes through its bit pattern."""
+    if t.dtype == torch.uint16:
+        return (t.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
+    return t.to(torch.float32)
+
+
 def _cfg_get(cfg, section: str, key: str, default=None):
     sec = cfg[section] if isinstance(cfg, dict) else getattr(cfg, section)
     return sec.get(key, default) if isinstance(sec, dict) else getattr(sec, key, default)
 
 
 @torch.inference_mode()
-def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16") -> None:
+def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16",
+         read_on_device: Optional[bool] = None) -> None:
     """Evaluates SKOOTS on an arbitrary image (drop-in for ``skoots.lib.eval.eval``).
 
     ``precision`` (not in the reference's signature; keyword with the reference's behaviour as default): "fp16" = what the
@@ -261,6 +275,11 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     written by ``zarr_store.save_device``: the zarr package itself is not in this image; chunks and TIFF pages are
     deflated on the device, ``lib/deflate.py``),
     ``<base>_skoots_benchmark.txt`` and ``<base>_instance_mask.tif`` (Z,X,Y), and prints DONE.
+
+    ``read_on_device`` (keyword, not in the reference's signature; ``None`` = the module's ``READ_ON_DEVICE``, which is
+    ``False`` until the device readers have been timed against the host ones): with ``True`` the image and, with ``used_cached_data``, the two
+    stores are read by ``tiff.read_stack`` / ``zarr_store.load_device`` (compressed bytes go to the device and are inflated
+    there) instead of the host readers + an upload; the results do not depend on it.
 
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
     ``SKOOTS.VECTOR_SCALING`` and ``MODEL.*``), ``model_state_dict`` and optionally
@@ -279,29 +298,48 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     base = os.path.splitext(image_path)[0]
 
     logging.info(f"Loading image from file: {image_path}")
-    image = _read_image(image_path)  # [Z, X, Y(, C)]
-    image = image[..., np.newaxis] if image.ndim == 3 else image
-    image = image.transpose(-1, 1, 2, 0)
-    image = image[[2], ...] if image.shape[0] > 3 else image  # eval.py:64 -> [C=1, X, Y, Z]
-    c, x, y, z = image.shape
-    logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {image.dtype}")
-    img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16)  # eval.py:80
+    from . import tiff, zarr_store
+    if read_on_device is None:
+        read_on_device = READ_ON_DEVICE   # looked up now, so that setting the module's switch takes effect
+    if read_on_device:
+        stack = tiff.read_stack(image_path, device)  # [Z, X, Y(, C)], strips inflated on the device
+        stack = stack.unsqueeze(-1) if stack.ndim == 3 else stack
+        stack = stack.permute(3, 1, 2, 0)
+        stack = stack[[2], ...] if stack.shape[0] > 3 else stack  # eval.py:64 -> [C=1, X, Y, Z]
+        c, x, y, z = stack.shape
+        logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {stack.dtype}")
+        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous()  # eval.py:80
+        # the statistics fallback stays the CPU reduction over the same fp16 values: the image comes back for it only
+        img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None
+    else:
+        image = _read_image(image_path)  # [Z, X, Y(, C)]
+        image = image[..., np.newaxis] if image.ndim == 3 else image
+        image = image.transpose(-1, 1, 2, 0)
+        image = image[[2], ...] if image.shape[0] > 3 else image  # eval.py:64 -> [C=1, X, Y, Z]
+        c, x, y, z = image.shape
+        logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {image.dtype}")
+        img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16)  # eval.py:80
+        dev_img = None
     mean = checkpoint["dataset_mean"] if "dataset_mean" in checkpoint else img16.mean()  # eval.py:87
     std = checkpoint["dataset_std"] if "dataset_std" in checkpoint else img16.std()  # eval.py:88
     scale = [int(v) for v in _cfg_get(cfg, "SKOOTS", "VECTOR_SCALING")]  # eval.py:99
 
     logging.info("Constructing SKOOTS model")
     model = unet.cfg_to_model(cfg, device, checkpoint["model_state_dict"], precision=precision)
-    from . import tiff, zarr_store
     skel_path, vec_path = base + "_skoots_skeleton.zarr", base + "_skoots_vectors.zarr"  # eval.py:102-103
 
     benchmark_start = time.time()
-    dev_img = img16.to(device)
+    if dev_img is None:
+        dev_img = img16.to(device)
     if used_cached_data and os.path.exists(skel_path) and os.path.exists(vec_path):  # eval.py:105 (os.exists bug fixed)
         from ..parallel import ShardedVolume  # noqa: F401
         state = VolumeState((x, y, z), device)
-        state.skeleton.copy_(torch.from_numpy(zarr_store.load(skel_path)[0]).to(device))
-        vp = torch.from_numpy(zarr_store.load(vec_path)).to(device)
+        if read_on_device:   # chunk files go up as they are and are inflated on the device
+            state.skeleton.copy_(zarr_store.load_device(skel_path, device)[0])
+            vp = zarr_store.load_device(vec_path, device)
+        else:
+            state.skeleton.copy_(torch.from_numpy(zarr_store.load(skel_path)[0]).to(device))
+            vp = torch.from_numpy(zarr_store.load(vec_path)).to(device)
         _ffi.check(_ffi.lib.sk_vec_interleave(_ffi.ptr(vp), _ffi.ptr(state.vec4), x * y * z,
                                               _ffi.stream_ptr(device)))
         state.label()

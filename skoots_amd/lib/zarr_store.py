@@ -9,7 +9,8 @@ reference's stores use zarr's default Blosc codec, which needs the absent ``numc
 and gzip stores and refuses every other codec by name.
 
 ``save_device`` writes the same zlib store from a torch tensor without taking the array to the host first: chunks are
-gathered and deflated on the tensor's device (``lib/deflate.py``), only compressed bytes cross to the host."""
+gathered and deflated on the tensor's device (``lib/deflate.py``), only compressed bytes cross to the host.
+``load_device`` is the way back: chunk files go to the device as they are and are inflated there."""
 from __future__ import annotations
 
 import gzip
@@ -146,4 +147,82 @@ def load(path: str) -> np.ndarray:
         block = np.frombuffer(raw, dtype=dt).reshape(chunks)
         sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, shape))
         out[sl] = block[tuple(slice(0, s.stop - s.start) for s in sl)]
+    return out
+
+
+LOAD_DEVICE_BUDGET = 256 << 20  # bytes of compressed + inflated chunks per batch (see load_device)
+
+
+def load_device(path: str, device, budget_bytes: int = LOAD_DEVICE_BUDGET, timings=None):
+    """The tensor ``torch.from_numpy(load(path)).to(device)`` gives, same metadata checks and error texts, without the
+    array ever existing on the host: raw and ``zlib`` chunk files are uploaded as they are and (``zlib``) inflated on
+    the device (``lib/deflate.py: inflate_streams``), in batches, then cropped (edge chunks) and copied to their place, one
+    copy per chunk.  ``budget_bytes`` (256 MiB by default; a batch holds at least one chunk) bounds what a batch adds on
+    the device besides the result: the uploaded chunk files + their inflated chunks.  The host holds the same chunk files
+    twice for a moment (the list and its join for the one upload), which the budget does not count.
+    Missing chunks are the fill value.  ``gzip`` chunks are decompressed on the host and uploaded.  On ``"cpu"`` the
+    same code runs with the stdlib's zlib.  A chunk that does not inflate to the chunk's size raises ``ValueError``
+    naming its file."""
+    import torch
+
+    from . import deflate
+    with open(os.path.join(path, ".zarray")) as f:
+        meta = json.load(f)
+    comp = meta.get("compressor")
+    codec = comp.get("id") if comp else None
+    if meta.get("zarr_format") != 2 or meta.get("filters") or codec not in (None, "zlib", "gzip"):
+        raise RuntimeError(f"{path}: zarr v2 stores with compressor {codec!r} / filters {meta.get('filters')!r} cannot be "
+                           "read here (raw, zlib and gzip only: numcodecs / Blosc are not in this image)")
+    if meta.get("order", "C") != "C":
+        raise RuntimeError(f"{path}: only C-order stores are supported")
+    shape, chunks, dt = meta["shape"], meta["chunks"], np.dtype(meta["dtype"])
+    if dt.byteorder == ">" or dt.kind not in "iufb":
+        return torch.from_numpy(load(path)).to(device)   # nothing torch can view bytes as: the host reader decides
+    tdt = torch.from_numpy(np.empty(0, dtype=dt)).dtype
+    dev = torch.device(device)
+    out = torch.full(shape, meta.get("fill_value") or 0, dtype=tdt, device=dev)
+    chunk_bytes = int(np.prod(chunks)) * dt.itemsize
+    grid = [range((s + c - 1) // c) for s, c in zip(shape, chunks)]
+    todo = []
+    for idx in itertools.product(*grid):
+        fn = os.path.join(path, ".".join(str(i) for i in idx))
+        if os.path.exists(fn):
+            todo.append((idx, fn, os.path.getsize(fn)))
+
+    def flush(part, files):
+        t0 = time.perf_counter()
+        if codec == "zlib":
+            try:
+                rows = deflate.inflate_streams(files, chunk_bytes, dev, timings=timings)
+            except deflate.InflateError as e:
+                raise ValueError(f"{part[e.index][1]}: {e}") from None
+        else:
+            for (idx, fn, _), raw in zip(part, files):
+                if len(raw) != chunk_bytes:
+                    raise ValueError(f"{fn}: {len(raw)} bytes, a chunk of {chunks} {dt} has {chunk_bytes}")
+            rows = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev).view(len(part), chunk_bytes)
+        blocks = rows.view(tdt).view([len(part)] + list(chunks))
+        for b, (idx, _, _) in enumerate(part):
+            sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, shape))
+            out[sl] = blocks[b][tuple(slice(0, s.stop - s.start) for s in sl)]
+        if timings is not None:
+            timings["inflate_scatter_s"] = timings.get("inflate_scatter_s", 0.0) + time.perf_counter() - t0
+
+    part, files, held = [], [], 0
+    for item in todo:
+        if part and held + item[2] + chunk_bytes > int(budget_bytes):
+            flush(part, files)
+            part, files, held = [], [], 0
+        t0 = time.perf_counter()
+        with open(item[1], "rb") as f:
+            raw = f.read()
+        if codec == "gzip":
+            raw = gzip.decompress(raw)
+        if timings is not None:
+            timings["file_s"] = timings.get("file_s", 0.0) + time.perf_counter() - t0
+        part.append(item)
+        files.append(raw)
+        held += len(raw) + chunk_bytes
+    if part:
+        flush(part, files)
     return out

@@ -17,6 +17,9 @@ import numpy as np
 import torch
 from torch import Tensor
 
+# Whether the masks are read by tiff.read_stack on the device or on the host and uploaded.
+READ_ON_DEVICE = False
+
 _LOG_LEVELS = [logging.DEBUG, logging.INFO, logging.WARNING, logging.ERROR, logging.CRITICAL]
 
 
@@ -30,8 +33,19 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     return parser.parse_args(argv)
 
 
-def load_mask(path: str) -> Tensor:
-    """(C = 1, X, Y, Z) int32 host tensor from a .tif or .npy stored [Z, X, Y(, C)] (validate/utils.py:8-26)."""
+def load_mask(path: str, device=None) -> Tensor:
+    """(C = 1, X, Y, Z) int32 tensor from a .tif or .npy stored [Z, X, Y(, C)] (validate/utils.py:8-26): on the host, or
+    with ``device`` read by ``tiff.read_stack`` (deflate strips are inflated on the device; permute and cast happen
+    there) -- the same values either way."""
+    if device is not None:
+        from ..lib.tiff import read_stack
+        t = read_stack(path, device)
+        t = t.unsqueeze(-1) if t.ndim == 3 else t
+        t = t.permute(3, 1, 2, 0)
+        t = t[[2], ...] if t.shape[0] > 3 else t
+        if t.dtype == torch.uint16:   # through the bit pattern: int16 storage holds the uint16 values
+            return (t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF)
+        return t.contiguous().to(torch.int32)
     from ..lib.eval import _read_image
     image = _read_image(path)
     image = image[..., np.newaxis] if image.ndim == 3 else image
@@ -128,7 +142,8 @@ def main(argv: Optional[Sequence[str]] = None) -> Tuple[str, str]:
     if not (os.path.exists(gt_path) and os.path.exists(pred_path)):
         raise RuntimeError(f"{os.path.exists(gt_path)=}, {os.path.exists(pred_path)=}")
     base = os.path.splitext(pred_path)[0]
-    gt, pred = crop(load_mask(gt_path)), crop(load_mask(pred_path))
+    dev = "cuda" if READ_ON_DEVICE else None
+    gt, pred = crop(load_mask(gt_path, dev)), crop(load_mask(pred_path, dev))
     logging.debug(f"Ground Truth Shape: {gt.shape}, Predicted Shape: {pred.shape}")
     if gt.shape != pred.shape:
         raise ValueError(f"ground truth {tuple(gt.shape)} and prediction {tuple(pred.shape)} differ in shape")
