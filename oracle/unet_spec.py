@@ -57,7 +57,8 @@ class UNetSpec(nn.Module):
                  depths: Sequence[int] = (2, 2, 2, 2, 2)):
         super().__init__()
         d0, d1, d2, d3, d4 = dims
-        assert d3 == d1 and d4 == d0, "decoder widths mirror the encoder"
+        # d4 is free: dec0 reads cat[skip0 (d0), up (d4)] whatever the two widths are (tests run a last width of 64)
+        assert d3 == d1, "the half-resolution decoder width mirrors the encoder"
         self.dims, self.depths = tuple(dims), tuple(depths)
 
         def stack(cin, cout, n):

@@ -12,24 +12,27 @@ Reference: the inner step of skoots/train/engine.py:456-499 --
 Here the same step runs as explicit kernels of libskoots_hip.so (no autograd): the forward
 keeps each block's raw conv output, GroupNorm affine and statistics; the loss and its gradient
 come from one fused kernel pair; the backward walks the recorded layer list in reverse (GN+SiLU
-backward, weight gradient, data gradient); AdamW updates one flat parameter buffer.  All fp32
-(the reference runs bf16 with channels_last_3d, engine.py:68,107-109; fp32 is the higher
-precision).  The network graph is oracle/unet_spec.py's; data loading, augmentation, schedulers
+backward, weight gradient, data gradient); AdamW updates one flat parameter buffer.  Master
+parameters, GroupNorm statistics, loss and optimizer are fp32 in every precision; the convolutions
+and the tensors between them are fp32 ("fp32", the parity mode) or 16-bit on the MFMA kernels
+("mixed" = fp16, "bf16": the reference runs bf16 with channels_last_3d, engine.py:68,107-109).
+Which way each data gradient of the backward travels is decided in routes.py, before the first
+kernel.  The network graph is oracle/unet_spec.py's; data loading, augmentation, schedulers
 and logging of the reference's loop are out of scope.
 """
 from __future__ import annotations
 
-import os
-
 import ctypes as C
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
 from .. import _ffi
 from ..unet import GN_EPS, GN_GROUPS
+from .routes import FAST_KINDS, GraphBlock, Kind, Route, route_gradients
 
 
 class _Layer:
@@ -75,6 +78,31 @@ class _Lib:
         return fn
 
 
+class _Grad16(NamedTuple):
+    """A gradient held as a 16-bit tensor: ``data`` * ``scale[1]`` is the gradient (a fast block's dy; a data gradient
+    on a 16-bit route).  ``complete`` is False for a Route.PENDING contribution, which the stride-2 reader's interleave
+    pass still has to sum."""
+    data: Tensor
+    scale: Tensor
+    complete: bool
+
+
+@dataclass
+class _Block:
+    """One entry of the tape: what the forward keeps of a block for its backward."""
+    kind: Kind
+    layer: _Layer
+    srcs: List[Tuple[Tensor, int]]   # (tensor as the caller passed it, upsampled)
+    y: Tensor                        # raw conv output (16-bit for FAST / STEM; the logits for the heads)
+    affine: Optional[Tensor]         # GroupNorm scale / shift per (b, c) and mean / rstd per (b, group); None without norm
+    stats: Optional[Tensor]
+    out: Tensor                      # what the consumers read
+
+    def graph(self) -> GraphBlock:
+        return GraphBlock(self.layer.name, self.kind, self.layer.ksize, self.layer.cout, self.out.data_ptr(),
+                          tuple((t.data_ptr(), up, t.shape[-1]) for t, up in self.srcs))
+
+
 class TrainUNet:
     """The U-Net of oracle/unet_spec.py with fp32 master parameters on the GPU.
 
@@ -102,9 +130,6 @@ class TrainUNet:
         self._L = _Lib("_bf16" if precision == "bf16" else "", torch.device(device))
         self.device = torch.device(device)
         self.dims, self.depths = tuple(dims), tuple(depths)
-        # A/B switches of the mixed step (tools/bench_train.py sets them; defaults = the fast choices)
-        self.fast_stem = True          # stem as an fp16-operand fast block
-        self.fast_heads = True         # heads straight on the fp16 activation
         self.f16_grad_handoff = bool(f16_grad_handoff)   # single-reader fp16 data gradients handed on without an fp32 copy
         # tests only: a list here makes backward() record, per fast block, copies of exactly the 16-bit tensors its kernels
         # read and wrote (sources, raw output, incoming gradient, dy, data gradients, scales) next to the parameter
@@ -158,9 +183,10 @@ class TrainUNet:
             l.cout, l.cin = int(l.weight.shape[0]), int(l.weight.shape[1])
             if tuple(l.weight.shape[2:]) != (l.ksize,) * 3:
                 raise ValueError(f"{l.name}: weight shape {tuple(l.weight.shape)} does not fit ksize {l.ksize}")
-        self._tape: List[tuple] = []
+        self._tape: List[_Block] = []
         self._ws: Optional[Tensor] = None
         self._half: Dict[int, Tensor] = {}   # data_ptr of an fp32 activation -> its fp16 twin (mixed mode)
+        self._keep: List[Tensor] = []        # buffers of the forward that must outlive their launch (see the stem)
         self._zero_page = torch.zeros(4096, dtype=torch.uint8, device=self.device)
         self._zero_bias = torch.zeros(128, dtype=torch.float32, device=self.device)
 
@@ -176,6 +202,11 @@ class TrainUNet:
         if self._ws is None or self._ws.numel() < floats:
             self._ws = torch.empty(int(floats), dtype=torch.float32, device=self.device)
         return self._ws
+
+    def _run(self, name: str, *args) -> None:
+        """One entry point of the library on the stream of the running pass: tensors go as their data pointers (None as
+        a null pointer), the stream goes last, a non-zero status raises."""
+        _ffi.check(getattr(self._L, name)(*[a.data_ptr() if isinstance(a, Tensor) else a for a in args], self._st))
 
     @staticmethod
     def _srcs(srcs) -> "C.Array":
@@ -198,14 +229,12 @@ class TrainUNet:
         c_n = layer.cin if c_n is None else c_n
         cout_eff, cin_eff = (c_n, layer.cout) if transposed else (layer.cout, layer.cin)
         buf = torch.empty(layer.ksize ** 3 * (cin_eff // 16) * (cout_eff // 32) * 1024, dtype=torch.uint8, device=self.device)
-        _ffi.check(self._L.sk_train_pack_weight(_ffi.ptr(layer.weight), layer.cout, layer.cin, layer.ksize, int(transposed),
-                                                 c_lo, c_n, _ffi.ptr(buf), _ffi.stream_ptr(self.device)))
+        self._run("sk_train_pack_weight", layer.weight, layer.cout, layer.cin, layer.ksize, int(transposed), c_lo, c_n, buf)
         return buf
 
     def _to_half(self, t: Tensor, scale: Optional[Tensor] = None) -> Tensor:
         h = torch.empty(t.shape, dtype=self.t16, device=self.device)
-        _ffi.check(self._L.sk_train_cast_f32_f16(_ffi.ptr(t), _ffi.ptr(h), t.numel(), _ffi.ptr(scale),
-                                                  _ffi.stream_ptr(self.device)))
+        self._run("sk_train_cast_f32_f16", t, h, t.numel(), scale)
         return h
 
     def _fast_conv(self, srcs16: List[Tuple[Tensor, int]], packed: Tensor, bias: Tensor, out_shape, cout: int, ksize: int,
@@ -213,76 +242,72 @@ class TrainUNet:
         B = srcs16[0][0].shape[0]
         ox, oy, oz = out_shape
         y16 = torch.empty((B, ox, oy, oz, cout), dtype=self.t16, device=self.device)
-        _ffi.check(self._L.sk_conv3d(self._srcs(srcs16), len(srcs16), _ffi.ptr(packed), _ffi.ptr(bias), _ffi.ptr(y16), B,
-                                      ox, oy, oz, cout, ksize, _ffi.ptr(partial), _ffi.ptr(self._zero_page),
-                                      _ffi.stream_ptr(self.device)))
+        self._run("sk_conv3d", self._srcs(srcs16), len(srcs16), packed, bias, y16, B, ox, oy, oz, cout, ksize, partial,
+                  self._zero_page)
         return y16
 
     def _h(self, t: Tensor) -> Tensor:
         """fp16 form of an activation: itself, or the registered twin of an fp32 tensor."""
         return t if t.dtype == self.t16 else self._half[t.data_ptr()]
 
+    # -- forward blocks -------------------------------------------------------------------------
+    def _norm_tail(self, kind: Kind, layer: _Layer, srcs, y: Tensor, partial: Tensor, nblk: int,
+                   want32: bool = False) -> Tensor:
+        """The second half of every GroupNorm block: statistics from the conv's partial sums, SiLU(GroupNorm(y)) in
+        y's precision, and the tape entry.  ``want32``: a 16-bit block also writes an fp32 activation and hands that
+        on (its consumer is an fp32 kernel, i.e. the heads); the 16-bit one stays registered as its twin."""
+        B, ox, oy, oz, cout = y.shape
+        vox = ox * oy * oz
+        affine = torch.empty((B, 2, cout), dtype=torch.float32, device=self.device)
+        stats = torch.empty((B, GN_GROUPS, 2), dtype=torch.float32, device=self.device)
+        self._run("sk_groupnorm_finalize_stats", partial, B, nblk, GN_GROUPS, cout, vox, layer.gamma, layer.beta, GN_EPS,
+                  affine, stats)
+        out = torch.empty_like(y)
+        if kind is Kind.FP32:
+            self._run("sk_train_gn_silu", y, affine, out, B, vox, cout)
+        else:
+            z16 = out
+            z32 = torch.empty(y.shape, dtype=torch.float32, device=self.device) if want32 else None
+            self._run("sk_train_gn_silu_f16", y, affine, z16, z32, B, vox, cout)
+            if want32:
+                self._half[z32.data_ptr()] = z16
+                out = z32
+        self._tape.append(_Block(kind, layer, srcs, y, affine, stats, out))
+        return out
+
     def _block_mixed(self, layer: _Layer, srcs: List[Tuple[Tensor, int]], out_shape: Tuple[int, int, int],
                      want32: bool = False) -> Tensor:
-        """Fast block: keeps the RAW fp16 conv output for the backward and hands the fp16 activation on (an fp32
-        copy only when ``want32``: the consumer is an fp32 kernel, i.e. the heads)."""
+        """Fast block: keeps the RAW fp16 conv output for the backward and hands the fp16 activation on."""
         B = srcs[0][0].shape[0]
         ox, oy, oz = out_shape
-        st = _ffi.stream_ptr(self.device)
         srcs16 = [(self._h(t), up) for t, up in srcs]
         nblk = self._L.sk_conv3d_num_blocks(B, ox, oy, oz, layer.cout, layer.ksize)
         partial = torch.empty((B, nblk, layer.cout // 4, 2), dtype=torch.float32, device=self.device)
         y16 = self._fast_conv(srcs16, self._pack(layer), layer.bias, out_shape, layer.cout, layer.ksize, partial)
-        vox = ox * oy * oz
-        affine = torch.empty((B, 2, layer.cout), dtype=torch.float32, device=self.device)
-        stats = torch.empty((B, GN_GROUPS, 2), dtype=torch.float32, device=self.device)
-        _ffi.check(self._L.sk_groupnorm_finalize_stats(_ffi.ptr(partial), B, nblk, GN_GROUPS, layer.cout, vox,
-                                                        _ffi.ptr(layer.gamma), _ffi.ptr(layer.beta), GN_EPS,
-                                                        _ffi.ptr(affine), _ffi.ptr(stats), st))
-        z16 = torch.empty_like(y16)
-        z32 = torch.empty(y16.shape, dtype=torch.float32, device=self.device) if want32 else None
-        _ffi.check(self._L.sk_train_gn_silu_f16(_ffi.ptr(y16), _ffi.ptr(affine), _ffi.ptr(z16), _ffi.ptr(z32), B, vox,
-                                                 layer.cout, st))
-        out = z16
-        if want32:
-            self._half[z32.data_ptr()] = z16
-            out = z32
-        self._tape.append((layer, srcs, y16, affine, stats, out))
-        return out
+        return self._norm_tail(Kind.FAST, layer, srcs, y16, partial, nblk, want32)
 
     def _stem_fast(self, layer: _Layer, srcs, out_shape) -> bool:
         """The stem (Cin = 1, 27 taps, Cout 32) as a fast block: fp16 image operand, exact weights (hi + lo split)."""
         B = srcs[0][0].shape[0]
         return (self.fast16 and layer.norm and layer.cin == 1 and layer.cout == 32 and layer.ksize == 3 and
-                len(srcs) == 1 and B <= 32 and out_shape[2] % 2 == 0 and self.fast_stem)
+                len(srcs) == 1 and B <= 32 and out_shape[2] % 2 == 0)
 
     def _block_stem_mixed(self, layer: _Layer, srcs, out_shape) -> Tensor:
         image = srcs[0][0]                       # (B, X, Y, Z, 1) fp32
         B = image.shape[0]
         X, Y, Z = out_shape
-        st = _ffi.stream_ptr(self.device)
         nblk = self._L.sk_conv3d_stem_num_blocks(X, Y, Z)
         partial = torch.empty((B, nblk, 8, 2), dtype=torch.float32, device=self.device)
         wsb = int(self._L.sk_conv3d_stem_workspace_bytes(B, X, Y, Z))
         ws = torch.empty(wsb, dtype=torch.uint8, device=self.device)
         w_t = layer.weight.reshape(32, 27).t().contiguous()   # (27, 32) tap-major, the stem kernel's layout
         y16 = torch.empty((B, X, Y, Z, 32), dtype=self.t16, device=self.device)
-        _ffi.check(self._L.sk_train_stem_fwd_f16(_ffi.ptr(image), B, X, Y, Z, _ffi.ptr(w_t), _ffi.ptr(layer.bias),
-                                                  _ffi.ptr(y16), _ffi.ptr(partial), _ffi.ptr(ws), wsb, st))
-        vox = X * Y * Z
-        affine = torch.empty((B, 2, 32), dtype=torch.float32, device=self.device)
-        stats = torch.empty((B, GN_GROUPS, 2), dtype=torch.float32, device=self.device)
-        _ffi.check(self._L.sk_groupnorm_finalize_stats(_ffi.ptr(partial), B, nblk, GN_GROUPS, 32, vox,
-                                                        _ffi.ptr(layer.gamma), _ffi.ptr(layer.beta), GN_EPS,
-                                                        _ffi.ptr(affine), _ffi.ptr(stats), st))
-        z16 = torch.empty_like(y16)
-        _ffi.check(self._L.sk_train_gn_silu_f16(_ffi.ptr(y16), _ffi.ptr(affine), _ffi.ptr(z16), None, B, vox, 32, st))
-        self._keep = getattr(self, "_keep", []) + [ws, w_t]   # alive until the stream has consumed them
-        self._tape.append((layer, srcs, y16, affine, stats, z16))
-        return z16
+        self._run("sk_train_stem_fwd_f16", image, B, X, Y, Z, w_t, layer.bias, y16, partial, ws, wsb)
+        self._keep += [ws, w_t]   # alive until the stream has consumed them
+        return self._norm_tail(Kind.STEM, layer, srcs, y16, partial, nblk)
 
     def _heads_fast(self, layer: _Layer) -> bool:
-        return (self.fast16 and not layer.norm and layer.ksize == 1 and layer.cout == 5 and layer.cin == 32 and self.fast_heads)
+        return self.fast16 and not layer.norm and layer.ksize == 1 and layer.cout == 5 and layer.cin == 32
 
     def _block_heads_mixed(self, layer: _Layer, srcs, out_shape) -> Tensor:
         """1x1x1 heads straight on the fp16 activation (an HBM stream: no fp32 copy of the last feature map)."""
@@ -290,9 +315,8 @@ class TrainUNet:
         B = z16.shape[0]
         ox, oy, oz = out_shape
         logits = torch.empty((B, ox, oy, oz, 5), dtype=torch.float32, device=self.device)
-        _ffi.check(self._L.sk_train_heads_fwd_f16(_ffi.ptr(z16), _ffi.ptr(layer.weight), _ffi.ptr(layer.bias),
-                                                   _ffi.ptr(logits), B * ox * oy * oz, _ffi.stream_ptr(self.device)))
-        self._tape.append((layer, srcs, logits, None, None, logits))
+        self._run("sk_train_heads_fwd_f16", z16, layer.weight, layer.bias, logits, B * ox * oy * oz)
+        self._tape.append(_Block(Kind.HEADS16, layer, srcs, logits, None, None, logits))
         return logits
 
     def _block(self, layer: _Layer, srcs: List[Tuple[Tensor, int]], out_shape: Tuple[int, int, int],
@@ -311,27 +335,17 @@ class TrainUNet:
     def _block_fp32(self, layer: _Layer, srcs: List[Tuple[Tensor, int]], out_shape: Tuple[int, int, int]) -> Tensor:
         B = srcs[0][0].shape[0]
         ox, oy, oz = out_shape
-        st = _ffi.stream_ptr(self.device)
         y = torch.empty((B, ox, oy, oz, layer.cout), dtype=torch.float32, device=self.device)
         if not layer.norm:
-            _ffi.check(self._L.sk_conv3d_f32(self._srcs(srcs), len(srcs), _ffi.ptr(layer.weight), _ffi.ptr(layer.bias),
-                                              _ffi.ptr(y), B, ox, oy, oz, layer.cout, layer.ksize, None, st))
-            self._tape.append((layer, srcs, y, None, None, y))
+            self._run("sk_conv3d_f32", self._srcs(srcs), len(srcs), layer.weight, layer.bias, y, B, ox, oy, oz, layer.cout,
+                      layer.ksize, None)
+            self._tape.append(_Block(Kind.FP32, layer, srcs, y, None, None, y))
             return y
         nblk = self._L.sk_conv3d_f32_num_blocks(ox, oy, oz)
         partial = torch.empty((B, nblk, layer.cout // 4, 2), dtype=torch.float32, device=self.device)
-        _ffi.check(self._L.sk_conv3d_f32(self._srcs(srcs), len(srcs), _ffi.ptr(layer.weight), _ffi.ptr(layer.bias),
-                                          _ffi.ptr(y), B, ox, oy, oz, layer.cout, layer.ksize, _ffi.ptr(partial), st))
-        vox = ox * oy * oz
-        affine = torch.empty((B, 2, layer.cout), dtype=torch.float32, device=self.device)
-        stats = torch.empty((B, GN_GROUPS, 2), dtype=torch.float32, device=self.device)
-        _ffi.check(self._L.sk_groupnorm_finalize_stats(_ffi.ptr(partial), B, nblk, GN_GROUPS, layer.cout, vox,
-                                                        _ffi.ptr(layer.gamma), _ffi.ptr(layer.beta), GN_EPS,
-                                                        _ffi.ptr(affine), _ffi.ptr(stats), st))
-        z = torch.empty_like(y)
-        _ffi.check(self._L.sk_train_gn_silu(_ffi.ptr(y), _ffi.ptr(affine), _ffi.ptr(z), B, vox, layer.cout, st))
-        self._tape.append((layer, srcs, y, affine, stats, z))
-        return z
+        self._run("sk_conv3d_f32", self._srcs(srcs), len(srcs), layer.weight, layer.bias, y, B, ox, oy, oz, layer.cout,
+                  layer.ksize, partial)
+        return self._norm_tail(Kind.FP32, layer, srcs, y, partial, nblk)
 
     def forward(self, images: Tensor) -> Tensor:
         """images: (B, 1, X, Y, Z) or (B, X, Y, Z), already normalised (the reference's loader does
@@ -349,6 +363,7 @@ class TrainUNet:
         self._tape = []
         self._half = {}
         self._image = x
+        self._st = _ffi.stream_ptr(self.device)
         a = x
         for l in self.enc0:
             a = self._block(l, [(a, 0)], L0)
@@ -375,197 +390,170 @@ class TrainUNet:
         self._half = {}
         self._keep = []
 
+    # -- backward -------------------------------------------------------------------------------
     def backward(self, dlogits: Tensor) -> None:
-        """Walk the recorded layers in reverse; gradients of every parameter land in ``flat_grad``."""
+        """Walk the recorded blocks in reverse; gradients of every parameter land in ``flat_grad``.  ``grads`` maps a
+        tensor's data pointer to its gradient so far: an fp32 tensor or a :class:`_Grad16`."""
         if not self._tape:
             raise RuntimeError("backward() needs a preceding forward()")
-        st = _ffi.stream_ptr(self.device)
-        grads: Dict[int, object] = {self._tape[-1][5].data_ptr(): dlogits}
-        # a tensor read by ONE fast conv and produced by a fast block receives its gradient as the scaled fp16 output of
-        # that conv's data-gradient kernel and hands it to the GroupNorm backward as it is: (dx16, scale), no fp32 copy
-        n_readers: Dict[int, int] = {}
-        for _, srcs_, *_rest in self._tape:
-            for t_, _up in srcs_:
-                n_readers[t_.data_ptr()] = n_readers.get(t_.data_ptr(), 0) + 1
-        fast_out = {e[5].data_ptr() for e in self._tape if e[2].dtype == self.t16}
-        k2_read = {t_.data_ptr() for l_, srcs_, y_, *_r in self._tape if l_.ksize == 2 and y_.dtype == self.t16
-                   for t_, _u in srcs_}
-        for layer, srcs, y, affine, stats, out in reversed(self._tape):
-            dz = grads.pop(out.data_ptr())
-            B, ox, oy, oz, cout = y.shape
-            vox = ox * oy * oz
-            fast = y.dtype == self.t16   # recorded by _block_mixed
-            ws = None
-            dz_scale = None
-            if isinstance(dz, tuple):
-                final = len(dz) == 3   # (tensor, scale, True): complete, whatever the number of readers (see below)
-                dz, dz_scale = dz[0], dz[1]
-                assert fast and (final or n_readers.get(out.data_ptr(), 0) == 1), "a pending fp16 gradient was never summed"
-            if fast:
-                # GroupNorm + SiLU backward straight to the scaled fp16 output gradient (no fp32 dy, no max / cast passes)
-                ws = self._workspace(max(self._L.sk_train_gn_bwd_f16_workspace_floats(B, vox, cout),
-                                         self._L.sk_train_conv_wgrad_workspace_floats(B, ox, oy, oz, cout, layer.cin, layer.ksize)))
-                scale = torch.empty(3, dtype=torch.float32, device=self.device)
-                dy16 = torch.empty(y.shape, dtype=self.t16, device=self.device)
-                if dz_scale is None:
-                    _ffi.check(self._L.sk_train_gn_silu_bwd_f16(_ffi.ptr(dz), _ffi.ptr(y), _ffi.ptr(affine), _ffi.ptr(stats),
-                                                                 _ffi.ptr(layer.gamma), B, vox, cout, GN_GROUPS,
-                                                                 _ffi.ptr(dy16), _ffi.ptr(scale), _ffi.ptr(layer.g_gamma),
-                                                                 _ffi.ptr(layer.g_beta), _ffi.ptr(ws), st))
-                else:
-                    _ffi.check(self._L.sk_train_gn_silu_bwd_f16h(_ffi.ptr(dz), _ffi.ptr(dz_scale), _ffi.ptr(y),
-                                                                  _ffi.ptr(affine), _ffi.ptr(stats), _ffi.ptr(layer.gamma), B,
-                                                                  vox, cout, GN_GROUPS, _ffi.ptr(dy16), _ffi.ptr(scale),
-                                                                  _ffi.ptr(layer.g_gamma), _ffi.ptr(layer.g_beta),
-                                                                  _ffi.ptr(ws), st))
-                dy = None
-                if layer.cin == 1:   # the stem: taps as the GEMM's N, fp32 image x scaled fp16 dy
-                    _ffi.check(self._L.sk_train_stem_wgrad_f16(_ffi.ptr(srcs[0][0]), _ffi.ptr(dy16), _ffi.ptr(scale), B, ox,
-                                                                oy, oz, _ffi.ptr(layer.g_weight), _ffi.ptr(layer.g_bias),
-                                                                _ffi.ptr(ws), st))
-                else:
-                    srcs16 = [(self._h(t), up) for t, up in srcs]
-                    _ffi.check(self._L.sk_train_conv_wgrad_f16(self._srcs(srcs16), len(srcs16), _ffi.ptr(dy16), _ffi.ptr(scale),
-                                                                B, ox, oy, oz, cout, layer.ksize, _ffi.ptr(layer.g_weight),
-                                                                _ffi.ptr(layer.g_bias), _ffi.ptr(ws), _ffi.ptr(self._zero_page),
-                                                                st))
+        self._st = _ffi.stream_ptr(self.device)
+        routes = route_gradients([b.graph() for b in self._tape], self._image.data_ptr(), self.f16_grad_handoff)
+        deliver = {Route.FP32: self._dx_fp32, Route.DIRECT: self._dx_direct, Route.PENDING: self._dx_pending,
+                   Route.INTERLEAVED: self._dx_interleaved, Route.POOLED: self._dx_pooled, Route.HEADS: self._dx_heads}
+        grads: Dict[int, object] = {self._tape[-1].out.data_ptr(): dlogits}
+        for blk, blk_routes in zip(reversed(self._tape), reversed(routes)):
+            dz = grads.pop(blk.out.data_ptr())
+            dy = self._param_grads(blk, dz)
+            rec = self._audit_record(blk, dz, dy)
+            lo = 0   # channel offset of the source in the conv's concatenated input
+            for (t, up), route in zip(blk.srcs, blk_routes):
+                if route is not Route.NONE:
+                    deliver[route](blk, dy, t, up, lo, grads, rec)
+                lo += t.shape[-1]
+        self.release()
+
+    def _param_grads(self, blk: _Block, dz):
+        """The parameter side of a block's backward: GroupNorm + SiLU backward of the incoming gradient ``dz`` (an fp32
+        tensor or a complete :class:`_Grad16`), then the conv's weight and bias gradient.  Returns the gradient of the
+        raw conv output for the routes: a :class:`_Grad16` from a fast block, else fp32."""
+        layer, srcs, y = blk.layer, blk.srcs, blk.y
+        B, ox, oy, oz, cout = y.shape
+        vox = ox * oy * oz
+        if blk.kind in FAST_KINDS:
+            # GroupNorm + SiLU backward straight to the scaled fp16 output gradient (no fp32 dy, no max / cast passes)
+            ws = self._workspace(max(self._L.sk_train_gn_bwd_f16_workspace_floats(B, vox, cout),
+                                     self._L.sk_train_conv_wgrad_workspace_floats(B, ox, oy, oz, cout, layer.cin, layer.ksize)))
+            scale = torch.empty(3, dtype=torch.float32, device=self.device)
+            dy16 = torch.empty(y.shape, dtype=self.t16, device=self.device)
+            if isinstance(dz, _Grad16):
+                assert dz.complete, f"{layer.name}: route_gradients hands a pending gradient to an interleave only"
+                self._run("sk_train_gn_silu_bwd_f16h", dz.data, dz.scale, y, blk.affine, blk.stats, layer.gamma, B, vox, cout,
+                          GN_GROUPS, dy16, scale, layer.g_gamma, layer.g_beta, ws)
             else:
-                if layer.norm:
-                    ws = self._workspace(self._L.sk_train_gn_bwd_workspace_floats(B, vox, cout))
-                    _ffi.check(self._L.sk_train_gn_silu_bwd(_ffi.ptr(dz), _ffi.ptr(y), _ffi.ptr(affine), _ffi.ptr(stats),
-                                                             _ffi.ptr(layer.gamma), B, vox, cout, GN_GROUPS, _ffi.ptr(dz),
-                                                             _ffi.ptr(layer.g_gamma), _ffi.ptr(layer.g_beta), _ffi.ptr(ws), st))
-                dy = dz
-                if srcs[0][0].dtype == self.t16:   # the heads on the fp16 activation (_block_heads_mixed)
-                    nv = B * vox
-                    ws = self._workspace(self._L.sk_train_heads_wgrad_workspace_floats(nv))
-                    _ffi.check(self._L.sk_train_heads_wgrad_f16(_ffi.ptr(srcs[0][0]), _ffi.ptr(dy), _ffi.ptr(layer.g_weight),
-                                                                 _ffi.ptr(layer.g_bias), nv, _ffi.ptr(ws), st))
-                else:
-                    ws = self._workspace(self._L.sk_train_conv_wgrad_workspace_floats(B, ox, oy, oz, cout, layer.cin,
-                                                                                       layer.ksize))
-                    _ffi.check(self._L.sk_train_conv_wgrad(self._srcs(srcs), len(srcs), _ffi.ptr(dy), B, ox, oy, oz, cout,
-                                                            layer.ksize, _ffi.ptr(layer.g_weight), _ffi.ptr(layer.g_bias),
-                                                            _ffi.ptr(ws), st))
-            rec = None
-            if self.audit is not None and fast:
-                rec = {"name": layer.name, "ksize": layer.ksize,
-                       "srcs": [((self._h(t) if layer.cin != 1 else t).clone(), up) for t, up in srcs],
-                       "y16": y.clone(), "affine": affine.clone(), "stats": stats.clone(),
-                       "dz": (dz.clone(), None) if dz_scale is None else (dz.clone(), dz_scale.clone()),
-                       "dy16": dy16.clone(), "scale": scale.clone(), "g_weight": layer.g_weight.clone(),
-                       "g_bias": layer.g_bias.clone(), "g_gamma": layer.g_gamma.clone(), "g_beta": layer.g_beta.clone(),
-                       "weight": layer.weight.clone(), "bias": layer.bias.clone(), "gamma": layer.gamma.clone(),
-                       "beta": layer.beta.clone(), "dx16": {}}
-                self.audit.append(rec)
-            lo = 0
-            for t, up in srcs:
-                c = t.shape[-1]
-                if t.data_ptr() == self._image.data_ptr():
-                    lo += c
-                    continue  # no gradient w.r.t. the input image
-                key = t.data_ptr()
-                if fast and c not in (32, 64, 128):
-                    raise RuntimeError(f"{layer.name}: mixed precision needs source widths of 32, 64 or 128 channels")
-                if layer.ksize == 2 and fast:
-                    # stride-2 data gradient: eight pointwise products W_p^T dY on the fast kernel, one per parity of the
-                    # fine voxel, then interleaved into the fine grid
-                    pend = grads.get(key)
-                    pend = pend if isinstance(pend, tuple) else None   # the decoder's fp16 contribution, not yet summed
-                    have = key in grads and pend is None
-                    # this conv is the tensor's last reader to report (the decoder's contribution, if any, is `pend`): the
-                    # sum leaves as a scaled 16-bit tensor + its scale for the producer's GroupNorm backward, no fp32 copy
-                    h_out = (self.f16_grad_handoff and not have and key in fast_out and
-                             n_readers.get(key, 0) == (2 if pend is not None else 1))
-                    if not have and not h_out:
-                        grads[key] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-                    packed = self._pack(layer, 2, 0, c)
-                    per = packed.numel() // 8
-                    t16 = torch.empty((8, B, ox, oy, oz, c), dtype=self.t16, device=self.device)
-                    for par in range(8):
-                        _ffi.check(self._L.sk_conv3d(self._srcs([(dy16, 0)]), 1, _ffi.ptr(packed[par * per:(par + 1) * per]),
-                                                      _ffi.ptr(self._zero_bias), _ffi.ptr(t16[par]), B, ox, oy, oz, c, 1, None,
-                                                      _ffi.ptr(self._zero_page), st))
-                    if h_out:
-                        dx16 = torch.empty(t.shape, dtype=self.t16, device=self.device)
-                        oscale = torch.empty(3, dtype=torch.float32, device=self.device)
-                        _ffi.check(self._L.sk_train_interleave2_h(_ffi.ptr(t16), _ffi.ptr(pend[0]) if pend is not None else None,
-                                                                   _ffi.ptr(pend[1]) if pend is not None else None,
-                                                                   _ffi.ptr(dx16), _ffi.ptr(oscale), B, ox, oy, oz, c,
-                                                                   _ffi.ptr(scale), st))
-                        grads[key] = (dx16, oscale, True)
-                    elif pend is not None:
-                        _ffi.check(self._L.sk_train_interleave2_add16(_ffi.ptr(t16), _ffi.ptr(pend[0]), _ffi.ptr(pend[1]),
-                                                                       _ffi.ptr(grads[key]), B, ox, oy, oz, c, _ffi.ptr(scale),
-                                                                       st))
-                    else:
-                        _ffi.check(self._L.sk_train_interleave2(_ffi.ptr(t16), _ffi.ptr(grads[key]), B, ox, oy, oz, c,
-                                                                 _ffi.ptr(scale), int(have), st))
-                elif layer.ksize == 2:
-                    have = key in grads
-                    if not have:
-                        grads[key] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-                    _ffi.check(self._L.sk_train_conv_dgrad(_ffi.ptr(dy), _ffi.ptr(layer.weight), _ffi.ptr(grads[key]), B,
-                                                            ox, oy, oz, cout, layer.cin, 0, layer.cin, 2, int(have), st))
-                elif fast:
-                    # data gradient on the fast conv kernel: the layer's weight packed transposed + tap-flipped
-                    dx16 = self._fast_conv([(dy16, 0)], self._pack(layer, True, lo, c), self._zero_bias, (ox, oy, oz), c,
-                                           layer.ksize, None)
-                    if rec is not None:
-                        rec["dx16"][lo] = dx16.clone()
-                    if up:
-                        if key in grads:
-                            raise RuntimeError("an upsampled tensor has one consumer in this graph")
-                        if self.f16_grad_handoff and key in fast_out and n_readers.get(key, 0) == 1:
-                            c16 = torch.empty(t.shape, dtype=self.t16, device=self.device)
-                            oscale = torch.empty(3, dtype=torch.float32, device=self.device)
-                            _ffi.check(self._L.sk_train_sumpool2_hh(_ffi.ptr(dx16), _ffi.ptr(scale), _ffi.ptr(c16),
-                                                                     _ffi.ptr(oscale), B, ox // 2, oy // 2, oz // 2, c, st))
-                            grads[key] = (c16, oscale, True)
-                        else:
-                            grads[key] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-                            _ffi.check(self._L.sk_train_sumpool2_f16(_ffi.ptr(dx16), _ffi.ptr(scale), _ffi.ptr(grads[key]), B,
-                                                                      ox // 2, oy // 2, oz // 2, c, st))
-                    elif (key in fast_out and key not in grads and self.f16_grad_handoff and
-                          (n_readers.get(key, 0) == 1 or (n_readers.get(key, 0) == 2 and key in k2_read))):
-                        # single reader: handed to the GroupNorm backward as it is; a skip tensor whose other reader is a
-                        # fast stride-2 conv (processed later): summed inside that conv's interleave pass
-                        grads[key] = (dx16, scale)
-                    else:
-                        have = key in grads
-                        if not have:
-                            grads[key] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-                        _ffi.check(self._L.sk_train_cast_f16_f32(_ffi.ptr(dx16), _ffi.ptr(grads[key]), t.numel(),
-                                                                  _ffi.ptr(scale), int(have), st))
-                elif up:
-                    fine = torch.empty((B, ox, oy, oz, c), dtype=torch.float32, device=self.device)
-                    _ffi.check(self._L.sk_train_conv_dgrad(_ffi.ptr(dy), _ffi.ptr(layer.weight), _ffi.ptr(fine), B, ox, oy,
-                                                            oz, cout, layer.cin, lo, c, layer.ksize, 0, st))
-                    if key in grads:
-                        raise RuntimeError("an upsampled tensor has one consumer in this graph")
-                    grads[key] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-                    _ffi.check(self._L.sk_train_sumpool2(_ffi.ptr(fine), _ffi.ptr(grads[key]), B, ox // 2, oy // 2,
-                                                          oz // 2, c, st))
-                elif (self.f16_grad_handoff and t.dtype == self.t16 and layer.ksize == 1 and cout == 5 and len(srcs) == 1 and
-                      key in fast_out and key not in grads and n_readers.get(key, 0) == 1 and c % 8 == 0 and 256 % (c // 8) == 0):
-                    # the heads on the 16-bit activation: their data gradient leaves as a scaled 16-bit tensor as well
-                    dl_scale = torch.zeros(3, dtype=torch.float32, device=self.device)
-                    _ffi.check(self._L.sk_train_absmax_scale(_ffi.ptr(dy), dy.numel(), _ffi.ptr(dl_scale), st))
-                    dx16 = torch.empty(t.shape, dtype=self.t16, device=self.device)
-                    oscale = torch.empty(3, dtype=torch.float32, device=self.device)
-                    _ffi.check(self._L.sk_train_heads_dgrad_f16(_ffi.ptr(dy), _ffi.ptr(dl_scale), _ffi.ptr(layer.weight),
-                                                                 _ffi.ptr(dx16), _ffi.ptr(oscale), B * vox, c, st))
-                    grads[key] = (dx16, oscale, True)
-                else:
-                    have = key in grads
-                    if not have:
-                        grads[key] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
-                    _ffi.check(self._L.sk_train_conv_dgrad(_ffi.ptr(dy), _ffi.ptr(layer.weight), _ffi.ptr(grads[key]), B,
-                                                            ox, oy, oz, cout, layer.cin, lo, c, layer.ksize, int(have), st))
-                lo += c
-        self._tape = []
-        self._half = {}
-        self._keep = []
+                self._run("sk_train_gn_silu_bwd_f16", dz, y, blk.affine, blk.stats, layer.gamma, B, vox, cout, GN_GROUPS,
+                          dy16, scale, layer.g_gamma, layer.g_beta, ws)
+            if blk.kind is Kind.STEM:   # taps as the GEMM's N, fp32 image x scaled fp16 dy
+                self._run("sk_train_stem_wgrad_f16", srcs[0][0], dy16, scale, B, ox, oy, oz, layer.g_weight, layer.g_bias, ws)
+            else:
+                srcs16 = [(self._h(t), up) for t, up in srcs]
+                self._run("sk_train_conv_wgrad_f16", self._srcs(srcs16), len(srcs16), dy16, scale, B, ox, oy, oz, cout,
+                          layer.ksize, layer.g_weight, layer.g_bias, ws, self._zero_page)
+            return _Grad16(dy16, scale, True)
+        if layer.norm:   # in place: dz becomes dy
+            ws = self._workspace(self._L.sk_train_gn_bwd_workspace_floats(B, vox, cout))
+            self._run("sk_train_gn_silu_bwd", dz, y, blk.affine, blk.stats, layer.gamma, B, vox, cout, GN_GROUPS, dz,
+                      layer.g_gamma, layer.g_beta, ws)
+        if blk.kind is Kind.HEADS16:
+            ws = self._workspace(self._L.sk_train_heads_wgrad_workspace_floats(B * vox))
+            self._run("sk_train_heads_wgrad_f16", srcs[0][0], dz, layer.g_weight, layer.g_bias, B * vox, ws)
+        else:
+            ws = self._workspace(self._L.sk_train_conv_wgrad_workspace_floats(B, ox, oy, oz, cout, layer.cin, layer.ksize))
+            self._run("sk_train_conv_wgrad", self._srcs(srcs), len(srcs), dz, B, ox, oy, oz, cout, layer.ksize,
+                      layer.g_weight, layer.g_bias, ws)
+        return dz
+
+    def _audit_record(self, blk: _Block, dz, dy) -> Optional[dict]:
+        """With ``audit`` on, copies of what a fast block's kernels read and wrote; the routes add their ``dx16``."""
+        if self.audit is None or blk.kind not in FAST_KINDS:
+            return None
+        layer = blk.layer
+        rec = {"name": layer.name, "ksize": layer.ksize,
+               "srcs": [((self._h(t) if blk.kind is not Kind.STEM else t).clone(), up) for t, up in blk.srcs],
+               "y16": blk.y.clone(), "affine": blk.affine.clone(), "stats": blk.stats.clone(),
+               "dz": (dz.data.clone(), dz.scale.clone()) if isinstance(dz, _Grad16) else (dz.clone(), None),
+               "dy16": dy.data.clone(), "scale": dy.scale.clone(), "g_weight": layer.g_weight.clone(),
+               "g_bias": layer.g_bias.clone(), "g_gamma": layer.g_gamma.clone(), "g_beta": layer.g_beta.clone(),
+               "weight": layer.weight.clone(), "bias": layer.bias.clone(), "gamma": layer.gamma.clone(),
+               "beta": layer.beta.clone(), "dx16": {}}
+        self.audit.append(rec)
+        return rec
+
+    # -- one method per Route: (block, its dy, source tensor, upsampled, channel offset, grads, audit record) --------
+    def _acc32(self, grads, t: Tensor) -> Tuple[Tensor, int]:
+        """The fp32 gradient of ``t`` and whether an earlier reader already wrote it (the kernel then accumulates)."""
+        have = t.data_ptr() in grads
+        if not have:
+            grads[t.data_ptr()] = torch.empty(t.shape, dtype=torch.float32, device=self.device)
+        return grads[t.data_ptr()], int(have)
+
+    def _dgrad16(self, blk: _Block, dy: _Grad16, t: Tensor, lo: int, rec) -> Tensor:
+        """Data gradient on the fast conv kernel: the layer's weight packed transposed + tap-flipped."""
+        c = t.shape[-1]
+        dx16 = self._fast_conv([(dy.data, 0)], self._pack(blk.layer, True, lo, c), self._zero_bias, blk.y.shape[1:4], c,
+                               blk.layer.ksize, None)
+        if rec is not None:
+            rec["dx16"][lo] = dx16.clone()
+        return dx16
+
+    def _parity_products(self, blk: _Block, dy: _Grad16, c: int) -> Tensor:
+        """Stride-2 data gradient: eight pointwise products W_p^T dY on the fast kernel, one per parity of the fine
+        voxel; the interleave kernels place them in the fine grid."""
+        B, ox, oy, oz, _ = blk.y.shape
+        packed = self._pack(blk.layer, 2, 0, c)
+        per = packed.numel() // 8
+        t16 = torch.empty((8, B, ox, oy, oz, c), dtype=self.t16, device=self.device)
+        for par in range(8):
+            self._run("sk_conv3d", self._srcs([(dy.data, 0)]), 1, packed[par * per:(par + 1) * per], self._zero_bias,
+                      t16[par], B, ox, oy, oz, c, 1, None, self._zero_page)
+        return t16
+
+    def _dx_fp32(self, blk, dy, t, up, lo, grads, rec) -> None:
+        layer = blk.layer
+        B, ox, oy, oz, cout = blk.y.shape
+        c = t.shape[-1]
+        if blk.kind in FAST_KINDS and layer.ksize == 2:
+            dst, have = self._acc32(grads, t)
+            self._run("sk_train_interleave2", self._parity_products(blk, dy, c), dst, B, ox, oy, oz, c, dy.scale, have)
+        elif blk.kind in FAST_KINDS:
+            dx16 = self._dgrad16(blk, dy, t, lo, rec)
+            dst, have = self._acc32(grads, t)
+            if up:
+                self._run("sk_train_sumpool2_f16", dx16, dy.scale, dst, B, ox // 2, oy // 2, oz // 2, c)
+            else:
+                self._run("sk_train_cast_f16_f32", dx16, dst, t.numel(), dy.scale, have)
+        elif up and layer.ksize != 2:
+            fine = torch.empty((B, ox, oy, oz, c), dtype=torch.float32, device=self.device)
+            self._run("sk_train_conv_dgrad", dy, layer.weight, fine, B, ox, oy, oz, cout, layer.cin, lo, c, layer.ksize, 0)
+            self._run("sk_train_sumpool2", fine, self._acc32(grads, t)[0], B, ox // 2, oy // 2, oz // 2, c)
+        else:
+            dst, have = self._acc32(grads, t)
+            c_lo, c_n = (0, layer.cin) if layer.ksize == 2 else (lo, c)   # a stride-2 conv has one source
+            self._run("sk_train_conv_dgrad", dy, layer.weight, dst, B, ox, oy, oz, cout, layer.cin, c_lo, c_n, layer.ksize,
+                      have)
+
+    def _dx_direct(self, blk, dy, t, up, lo, grads, rec) -> None:
+        grads[t.data_ptr()] = _Grad16(self._dgrad16(blk, dy, t, lo, rec), dy.scale, True)
+
+    def _dx_pending(self, blk, dy, t, up, lo, grads, rec) -> None:
+        grads[t.data_ptr()] = _Grad16(self._dgrad16(blk, dy, t, lo, rec), dy.scale, False)
+
+    def _dx_interleaved(self, blk, dy, t, up, lo, grads, rec) -> None:
+        B, ox, oy, oz, _ = blk.y.shape
+        pend = grads.get(t.data_ptr())   # the decoder's Route.PENDING contribution, if the tensor has a second reader
+        pend_data, pend_scale = (pend.data, pend.scale) if pend is not None else (None, None)
+        t16 = self._parity_products(blk, dy, t.shape[-1])
+        dx16 = torch.empty(t.shape, dtype=self.t16, device=self.device)
+        oscale = torch.empty(3, dtype=torch.float32, device=self.device)
+        self._run("sk_train_interleave2_h", t16, pend_data, pend_scale, dx16, oscale, B, ox, oy, oz, t.shape[-1],
+                  dy.scale)
+        grads[t.data_ptr()] = _Grad16(dx16, oscale, True)
+
+    def _dx_pooled(self, blk, dy, t, up, lo, grads, rec) -> None:
+        B, ox, oy, oz, _ = blk.y.shape
+        dx16 = self._dgrad16(blk, dy, t, lo, rec)
+        c16 = torch.empty(t.shape, dtype=self.t16, device=self.device)
+        oscale = torch.empty(3, dtype=torch.float32, device=self.device)
+        self._run("sk_train_sumpool2_hh", dx16, dy.scale, c16, oscale, B, ox // 2, oy // 2, oz // 2, t.shape[-1])
+        grads[t.data_ptr()] = _Grad16(c16, oscale, True)
+
+    def _dx_heads(self, blk, dy, t, up, lo, grads, rec) -> None:
+        dl_scale = torch.zeros(3, dtype=torch.float32, device=self.device)
+        self._run("sk_train_absmax_scale", dy, dy.numel(), dl_scale)
+        dx16 = torch.empty(t.shape, dtype=self.t16, device=self.device)
+        oscale = torch.empty(3, dtype=torch.float32, device=self.device)
+        self._run("sk_train_heads_dgrad_f16", dy, dl_scale, blk.layer.weight, dx16, oscale, t.numel() // t.shape[-1],
+                  t.shape[-1])
+        grads[t.data_ptr()] = _Grad16(dx16, oscale, True)
 
 
 def _loss_term(spec):

@@ -638,6 +638,45 @@ def test_train_step_mixed_precision_vs_oracle():
     print(f"mixed precision: worst gradient error / max = {worst:.2e}")
 
 
+@pytest.mark.parametrize("dims,B,shape,fp32_block", [((32, 64, 128, 64, 64), 1, (16, 12, 8), "heads"),
+                                                     ((32, 64, 128, 64, 32), 33, (8, 8, 8), "enc0.0")])
+def test_mixed_step_with_an_fp32_block_vs_oracle(dims, B, shape, fp32_block):
+    """The two fp32 blocks a 16-bit step falls back to, which the default network at a small batch never takes:
+    heads that are not 32 -> 5 (a last width of 64: fp32 heads on an fp32 copy of dec0.1's activation, ``want32``, and
+    an fp32 gradient into a fast block with the hand-off on), and the stem at B > 32 (fp32 stem, its output cast to
+    16 bits for enc0.1, enc0.1's data gradient cast back to fp32).  Same kernels at the same precision as
+    test_train_step_mixed_precision_vs_oracle, hence its bounds: losses within 2e-3, every parameter gradient
+    within 3 % of that tensor's max and 1 % in RMS."""
+    from oracle import train_step as O
+    from oracle import unet_spec
+    from skoots_amd.train import TrainStep, TrainUNet
+    from skoots_amd.train.routes import Kind
+    ref = unet_spec.build(dims=dims).train()
+    sigma, scale = torch.tensor([20.0, 20.0, 20.0]), torch.tensor((60, 60, 12))
+    model = TrainUNet(ref.state_dict(), DEV, dims=dims, precision="mixed")
+    step = TrainStep(model)
+    images, masks, skele, baked = _synthetic_batch(B, *shape, 40)
+    want = O.train_step(ref, O.make_optimizer(ref), images, masks, skele, baked, sigma, scale)
+    ref_grads = {k: p.grad.clone() for k, p in ref.named_parameters()}
+    logits = model.forward(images.to(DEV))
+    kinds = {b.layer.name: b.kind for b in model._tape}
+    assert kinds.pop(fp32_block) is Kind.FP32 and Kind.FP32 not in kinds.values(), kinds
+    got, dl = step.fused_loss(logits, masks.to(DEV), skele.to(DEV), baked.to(DEV), sigma.tolist())
+    model.backward(dl)
+    print(f"{fp32_block} fp32: losses", got.cpu().numpy(), "oracle", want.numpy())
+    worst, worst_rms = 0.0, 0.0
+    errs = {}
+    for k, g in model.grads().items():
+        r = ref_grads[k].double()
+        e = (g.cpu().double() - r)
+        errs[k] = ((e.abs().max() / r.abs().max()).item(), (e.pow(2).mean().sqrt() / r.abs().max()).item())
+        worst, worst_rms = max(worst, errs[k][0]), max(worst_rms, errs[k][1])
+    print(f"{fp32_block} fp32: worst gradient error / max = {worst:.2e}, worst rms / max = {worst_rms:.2e}")
+    np.testing.assert_allclose(got.cpu().numpy(), want.numpy(), rtol=0, atol=2e-3)
+    for k, (emax, erms) in errs.items():
+        assert emax <= 3e-2 and erms <= 1e-2, (k, emax, erms)
+
+
 @pytest.mark.parametrize("precision", ["fp32", "mixed", "bf16"])
 def test_training_step_is_deterministic(precision):
     """Two runs of forward + loss + backward from the same state give bit-identical gradients: every reduction is
