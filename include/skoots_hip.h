@@ -784,6 +784,31 @@ int sk_tiff_undo_predictor(void* rows, int64_t n_rows, int row_pixels, int sampl
                            void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * --convert: eval()'s stores and .trch tensors -> the pages of a TIFF stack
+ * ------------------------------------------------------------------------ */
+
+#define SK_CONVERT_U8 0
+#define SK_CONVERT_F16 1
+#define SK_CONVERT_F32 2
+
+#define SK_CONVERT_CAST 0   /* astype(np.uint8) */
+#define SK_CONVERT_TRUNC 1  /* store array, max < 2: ((x + 1) / 2) * 255, truncated */
+#define SK_CONVERT_ROUND 2  /* .trch tensor, min < 0: the same, .float().round() */
+
+/* src: contiguous (C, X, Y, Z) of src_dtype (SK_CONVERT_U8 / _F16 / _F32); dst: contiguous (Z, X, Y, C) uint8, the
+ * pages x.transpose(3, 1, 2, 0) gives; C = 1..4.  One pass, replacing the torch / numpy chain of
+ * skoots/utils/convert_trch_to_tif.py:48-55 (mode 1), :59-65 (mode 2) and the transposes at :55 / :73.
+ *   mode 0  plain cast: truncate toward zero, keep the low 8 bits (uint8: a copy).  The reference's astype(np.uint8)
+ *           defines no result outside [0, 256): what this gives there is UNPINNED.
+ *   mode 1  t = ((x + 1) / 2) * 255 with every operation rounded in the array's own float type (fp16: three fp16
+ *           roundings; uint8: the add wraps in uint8, the division promotes to fp32), truncated; 0 where x == 0.
+ *   mode 2  the same t, converted to fp32, rounded half to even; 0 where x == 0.
+ * In modes 1 and 2 a t outside [0, 256) is unpinned in the same way (low 8 bits of the saturated int32).
+ * No workspace.  Arguments are checked before the launch. */
+int sk_convert_pages_u8(const void* src, int src_dtype, int mode, int C, int X, int Y, int Z, uint8_t* dst,
+                        void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

@@ -1,6 +1,8 @@
 """``python -m skoots_amd --image P --pretrained-checkpoint C [--log 0-4]``: the eval flags of
 the reference CLI (skoots/__main__.py:19-46, 78-98), and ``--skeletonize-train-data PATH [--mask-filter .labels]
-[--anisotropyXY a] [--anisotropyZ b]`` (skoots/__main__.py:49-68, 101-106).  ``--convert`` is out of scope."""
+[--anisotropyXY a] [--anisotropyZ b]`` (skoots/__main__.py:49-68, 101-106), and ``--convert PATH``: eval's zarr stores
+and ``.trch`` tensors under PATH -> TIFF stacks, no eval (skoots/__main__.py:70-74, 84, 108-109).  With it every switch of
+the reference's main command exists here."""
 import argparse
 import glob
 import logging
@@ -11,7 +13,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="SKOOTS (MI355X)", description="skoots parameters")
     eval_args = parser.add_argument_group("eval arguments")
     eval_args.add_argument("--image", type=str,
-                           help="path to image (or a directory of *.tif); required unless --skeletonize-train-data")
+                           help="path to image (or a directory of *.tif); required unless --skeletonize-train-data "
+                                "or --convert")
     eval_args.add_argument("--pretrained-checkpoint", type=str, help="path to a pretrained skoots model")
     eval_args.add_argument("--use-cached", action="store_true",
                            help="skips model evaluation and loads previously evaluated arrays")
@@ -23,13 +26,15 @@ def build_parser() -> argparse.ArgumentParser:
     accessory_args.add_argument("--mask-filter", default=".labels", help="filter of mask file")
     accessory_args.add_argument("--anisotropyXY", type=float, default=1.0, help="resample factor of x and y")
     accessory_args.add_argument("--anisotropyZ", type=float, default=1.0, help="resample factor of z")
+    accessory_args.add_argument("--convert", type=str,
+                                help="converts all skoots eval outputs in directory to a tif image")
     return parser
 
 
 def parse_args(argv=None) -> argparse.Namespace:
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.skeletonize_train_data is None and args.image is None:
+    if args.skeletonize_train_data is None and args.convert is None and args.image is None:
         parser.error("the following arguments are required: --image")
     return args
 
@@ -43,6 +48,10 @@ def main(argv=None):
         scale = (args.anisotropyXY, args.anisotropyXY, args.anisotropyZ)
         print("skeletonizing...")
         create_gt_skeletons(args.skeletonize_train_data, args.mask_filter, scale)
+    if args.convert is not None:
+        from skoots_amd.utils.convert_trch_to_tif import convert
+        convert(args.convert)
+    if args.skeletonize_train_data is not None or args.convert is not None:   # no eval (skoots/__main__.py:84)
         return
     assert args.pretrained_checkpoint is not None, (
         "Cannot evaluate SKOOTS wihtout pretrained model. --pretrained_checkpoint must not be None")

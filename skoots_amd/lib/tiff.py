@@ -219,35 +219,43 @@ def _undo_predictor(pages, p0: TiffPage) -> None:
 WRITE_STACK_BUDGET = 256 << 20  # bytes of page data + encoder buffers per batch of pages
 _TIFF_MAX = 2 ** 32 - 1
 _IFD_TAGS = 10
-_IFD_BYTES = 2 + 12 * _IFD_TAGS + 4
 
 
 def _page_rows(pages):
-    """(Z, H, W) array or tensor of uint8 / uint16 / int32 -> ((Z, H * W * itemsize) uint8 tensor, bits, sample format)."""
+    """(Z, H, W) array or tensor of uint8 / uint16 / int32, or (Z, H, W, C) uint8 with C in {1, 3, 4} ->
+    ((Z, page bytes) uint8 tensor, bits, sample format, samples per pixel)."""
     import torch
-    if isinstance(pages, np.ndarray):
-        if pages.dtype not in (np.uint8, np.uint16, np.int32) or pages.ndim != 3:
-            raise ValueError(f"write_stack takes (Z, H, W) uint8 / uint16 / int32, got {pages.shape} {pages.dtype}")
+    is_np = isinstance(pages, np.ndarray)
+    ok = (np.uint8, np.uint16, np.int32) if is_np else (torch.uint8, torch.uint16, torch.int32)
+    grey = pages.ndim == 3 and pages.dtype in ok
+    colour = pages.ndim == 4 and pages.dtype == ok[0] and pages.shape[3] in (1, 3, 4)
+    if not (grey or colour):
+        raise ValueError("write_stack takes (Z, H, W) uint8 / uint16 / int32 or (Z, H, W, C) uint8 with C in {1, 3, 4}, "
+                         f"got {tuple(pages.shape)} {pages.dtype}")
+    spp = int(pages.shape[3]) if colour else 1
+    if is_np:
         fmt = 2 if pages.dtype == np.int32 else 1
         arr = np.ascontiguousarray(pages)
         raw = torch.from_numpy(arr.view(np.uint8).reshape(arr.shape[0], -1) if arr.size else
                                np.zeros((arr.shape[0], 0), np.uint8))
-        return raw, 8 * arr.dtype.itemsize, fmt
-    if pages.ndim != 3 or pages.dtype not in (torch.uint8, torch.uint16, torch.int32):
-        raise ValueError(f"write_stack takes (Z, H, W) uint8 / uint16 / int32, got {tuple(pages.shape)} {pages.dtype}")
+        return raw, 8 * arr.dtype.itemsize, fmt, spp
     t = pages.contiguous()
-    return t.view(torch.uint8).reshape(t.shape[0], -1), 8 * t.element_size(), 2 if t.dtype == torch.int32 else 1
+    return t.view(torch.uint8).reshape(t.shape[0], -1), 8 * t.element_size(), 2 if t.dtype == torch.int32 else 1, spp
 
 
 def _write_pages(path: str, rows, height: int, width: int, bits: int, sample_format: int,
-                 budget_bytes: int = WRITE_STACK_BUDGET, timings=None) -> None:
-    """``rows``: (Z, page_bytes) uint8 tensor on either device, page z = row z in C order, little-endian samples."""
+                 budget_bytes: int = WRITE_STACK_BUDGET, timings=None, samples: int = 1) -> None:
+    """``rows``: (Z, page_bytes) uint8 tensor on either device, page z = row z in C order, little-endian samples;
+    ``samples`` = 3 / 4: chunky RGB / RGBA pixels of 8-bit samples."""
     import time
 
     from . import deflate
     n_pages, page_bytes = int(rows.shape[0]), int(rows.shape[1])
-    if n_pages < 1 or height * width * (bits // 8) != page_bytes:
-        raise ValueError(f"{n_pages} pages of {page_bytes} bytes do not make {height} x {width} x {bits} bit pages")
+    if samples not in (1, 3, 4) or (samples > 1 and (bits, sample_format) != (8, 1)):
+        raise ValueError(f"{samples} samples of {bits} bits per pixel: pages are grey, or 8-bit RGB / RGBA")
+    if n_pages < 1 or height * width * samples * (bits // 8) != page_bytes:
+        raise ValueError(f"{n_pages} pages of {page_bytes} bytes do not make {height} x {width} x {bits} bit pages"
+                         + (f" of {samples} samples" if samples > 1 else ""))
     batch = max(1, int(budget_bytes) // (page_bytes + deflate.device_bytes_per_stream(page_bytes)))
     strips = []
     for lo in range(0, n_pages, batch):
@@ -257,7 +265,14 @@ def _write_pages(path: str, rows, height: int, width: int, bits: int, sample_for
     for s in strips:
         offsets.append(at)
         at += len(s) + (len(s) & 1)
-    total = at + n_pages * _IFD_BYTES
+    # RGB(A): BitsPerSample holds `samples` shorts, more than the 4-byte value field takes; every directory points at
+    # one copy of them behind the strips
+    bits_at, n_tags = at, _IFD_TAGS
+    if samples > 1:
+        at += 2 * samples
+        n_tags = _IFD_TAGS + (samples == 4)   # PlanarConfiguration in SampleFormat's place; RGBA: + ExtraSamples
+    ifd_bytes = 2 + 12 * n_tags + 4
+    total = at + n_pages * ifd_bytes
     if total > _TIFF_MAX:
         raise ValueError(f"{path}: {total} bytes do not fit a classic TIFF (32-bit offsets); BigTIFF is not supported")
     t0 = time.perf_counter()
@@ -267,27 +282,37 @@ def _write_pages(path: str, rows, height: int, width: int, bits: int, sample_for
             f.write(s)
             if len(s) & 1:
                 f.write(b"\0")
+        if samples > 1:
+            f.write(struct.pack(f"<{samples}H", *([bits] * samples)))
         for z, s in enumerate(strips):
-            ifd = at + z * _IFD_BYTES
-            tags = ((256, 4, width), (257, 4, height), (258, 3, bits), (259, 3, 8), (262, 3, 1), (273, 4, offsets[z]),
-                    (277, 3, 1), (278, 4, height), (279, 4, len(s)), (339, 3, sample_format))
+            ifd = at + z * ifd_bytes
+            if samples == 1:
+                tags = ((256, 4, 1, width), (257, 4, 1, height), (258, 3, 1, bits), (259, 3, 1, 8), (262, 3, 1, 1),
+                        (273, 4, 1, offsets[z]), (277, 3, 1, 1), (278, 4, 1, height), (279, 4, 1, len(s)),
+                        (339, 3, 1, sample_format))
+            else:   # unsigned samples are SampleFormat's default; ExtraSamples 2 = unassociated alpha
+                tags = ((256, 4, 1, width), (257, 4, 1, height), (258, 3, samples, bits_at), (259, 3, 1, 8),
+                        (262, 3, 1, 2), (273, 4, 1, offsets[z]), (277, 3, 1, samples), (278, 4, 1, height),
+                        (279, 4, 1, len(s)), (284, 3, 1, 1)) + (((338, 3, 1, 2),) if samples == 4 else ())
             f.write(struct.pack("<H", len(tags)))
-            for tag, typ, val in tags:   # a SHORT value sits in the low half of the 4-byte value field
-                f.write(struct.pack("<HHII", tag, typ, 1, val))
-            f.write(struct.pack("<I", ifd + _IFD_BYTES if z + 1 < n_pages else 0))
+            for tag, typ, count, val in tags:   # a SHORT value sits in the low half of the 4-byte value field
+                f.write(struct.pack("<HHII", tag, typ, count, val))
+            f.write(struct.pack("<I", ifd + ifd_bytes if z + 1 < n_pages else 0))
     if timings is not None:
         timings["file_s"] = timings.get("file_s", 0.0) + time.perf_counter() - t0
 
 
 def write_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timings=None) -> None:
-    """(Z, H, W) uint8 / uint16 / int32 tensor (either device) or array -> multi-page TIFF with Adobe-deflate strips.
+    """(Z, H, W) uint8 / uint16 / int32 tensor (either device) or array -> multi-page TIFF with Adobe-deflate strips;
+    (Z, H, W, C) uint8 with C = 3 / 4 -> RGB / RGBA pages (PhotometricInterpretation 2, SamplesPerPixel C, chunky, C
+    BitsPerSample shorts out of line, ExtraSamples 2 for C = 4), and (Z, H, W, 1) is written as grey.
 
     One directory and one strip per page; tags 256, 257, 258, 259 (= 8), 262 (= 1), 273, 277, 278, 279, 339.  Every
     strip is one zlib stream from :func:`skoots_amd.lib.deflate.deflate_streams`, made on the tensor's device in batches
     of pages that keep page data + encoder buffers under ``budget_bytes``; the compressed strips are held on the host
     until the layout is known.  A file past 2**32 - 1 bytes raises ``ValueError`` before anything is written."""
-    rows, bits, fmt = _page_rows(pages)
-    _write_pages(path, rows, int(pages.shape[1]), int(pages.shape[2]), bits, fmt, budget_bytes, timings)
+    rows, bits, fmt, spp = _page_rows(pages)
+    _write_pages(path, rows, int(pages.shape[1]), int(pages.shape[2]), bits, fmt, budget_bytes, timings, samples=spp)
 
 
 def write_label_stack(path: str, labels_zxy, timings=None) -> None:
