@@ -809,6 +809,29 @@ int sk_convert_pages_u8(const void* src, int src_dtype, int mode, int C, int X, 
                         void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Instance measurements: volume, box, moments and face area of every instance
+ * ------------------------------------------------------------------------ */
+
+/* One pass over an (X, Y, Z) int32 instance mask (z fastest) measures every instance at once; the reference sketches
+ * the step with one full-volume mask per id (skoots/validate/compare.py: stats_per_instance) and one Python iteration
+ * per id (validate/lib.py: mask_to_bbox).  lut (max_id + 1 entries) maps a raw id to its row 1..N as in sk_mask_iou;
+ * ids <= 0 or above max_id, and rows outside 1..N, are background.  Row r fills
+ *   sums[(r - 1) * 13 ..]  int64: n, Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz over the voxel indices, then fx, fy, fz,
+ *                          the exposed faces whose normal lies along x / y / z;
+ *   boxes[(r - 1) * 6 ..]  int32: min x, y, z, then max x, y, z, inclusive (mask_to_bbox's convention); a row without
+ *                          voxels keeps INT32_MAX / -1.
+ * A face of a voxel of row a is exposed when the neighbour across it lies outside the volume or has another row,
+ * background included: a face between two instances counts once for each.  The entry point initialises both outputs
+ * itself (stream-ordered) and measures in one launch; background voxels take no atomic, and only integer atomics are
+ * used, so the result is exact and the same on every run.  Checked before anything is written: extents and N not
+ * negative, X Y Z max(X, Y, Z)^2 < 2^63 (the second moments stay inside int64), no NULL pointer.  An empty volume or
+ * N == 0 returns SK_OK and writes nothing.  sk_instance_stats_row_values(0) = 13 and (1) = 6: the int64 / int32
+ * values per row, for a caller that sizes the buffers. */
+int sk_instance_stats_row_values(int which);
+int sk_instance_stats(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, int64_t* sums,
+                      int32_t* boxes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

@@ -178,6 +178,8 @@ _SIGS = {
     "sk_inflate_streams": (i32, [vp, vp, i32, vp, vp, i32, vp, vp]),
     "sk_tiff_undo_predictor": (i32, [vp, i64, i32, i32, i32, vp]),
     "sk_convert_pages_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "sk_instance_stats_row_values": (i32, [i32]),
+    "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

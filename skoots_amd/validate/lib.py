@@ -5,6 +5,9 @@ ground-truth instance in Python and forms full-volume masks (and, for clDice, tw
 pair; here one kernel pass builds the (gt, pred) contingency tables and a second one turns them into the matrices
 (``mask_metrics`` gives all three from one pass).  The bookkeeping on the small matrix
 (``accuracies_from_iou``, ``f1_score``, ``get_segmentation_errors``) is host logic on its values.
+
+``instance_sums`` measures every instance of one mask in a single kernel pass; ``mask_to_bbox`` is the
+reference's function of that name on top of it, and ``validate/compare.py`` derives the per-instance statistics.
 """
 from __future__ import annotations
 
@@ -136,3 +139,77 @@ def get_segmentation_errors(ground_truth: Tensor, predicted: Tensor) -> Tuple[fl
     over = (iou.gt(0.2).sum(dim=1) > 1).sum().item() / n
     under = (iou.gt(0.2).sum(dim=0) > 1).sum().item() / m
     return over, under
+
+
+# ---- per-instance measurements ----
+
+N_SUMS, N_BOX = 13, 6      # int64 / int32 values per instance of sk_instance_stats (checked against the library below)
+_INT32_MAX = 2 ** 31 - 1
+
+
+def check_shape(shape) -> None:
+    """The library's guard, applied before any call: X Y Z max(X, Y, Z)^2 < 2^63 keeps the second moments in int64."""
+    X, Y, Z = (int(v) for v in shape)
+    if min(X, Y, Z) < 0 or max(X, Y, Z) > _INT32_MAX or X * Y * Z * max(X, Y, Z) ** 2 >= 2 ** 63:
+        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure: X*Y*Z*max(X, Y, Z)^2 must stay below "
+                         "2^63, or the second moments leave int64")
+
+
+def _as_volume(x: Tensor, name: str) -> Tensor:
+    """(X, Y, Z) view of an integer device tensor given as (X, Y, Z) or (1, X, Y, Z)."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError(f"{name} must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU "
+                         "fallback")
+    if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
+        raise TypeError(f"{name} must have an integer dtype, got {x.dtype}")
+    if x.ndim == 4 and x.shape[0] == 1:
+        x = x[0]
+    if x.ndim != 3:
+        raise ValueError(f"{name} must be (X, Y, Z) or (1, X, Y, Z), got shape {tuple(x.shape)}")
+    if x.dtype in (getattr(torch, n) for n in ("uint16", "uint32", "uint64") if hasattr(torch, n)):
+        x = x.to(torch.int64)
+    return x
+
+
+def instance_sums(x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """(ids (N) int64 ascending, sums (N, 13) int64, boxes (N, 6) int32) of the positive ids of an (X, Y, Z) integer
+    device tensor: one ``sk_instance_stats`` launch for every instance (include/skoots_hip.h names the columns).
+
+    Ids reach the kernel through the ``_lut`` table, which has ``max id + 1`` entries; when the largest id exceeds four
+    times the voxel count (or int32) the mask is relabelled through ``torch.unique(return_inverse=True)`` instead, so
+    that a few huge ids do not allocate a huge table."""
+    assert _ffi.lib.sk_instance_stats_row_values(0) == N_SUMS and _ffi.lib.sk_instance_stats_row_values(1) == N_BOX
+    x = _as_volume(x, "x")
+    check_shape(x.shape)
+    dev = x.device
+    mx = int(x.max().item()) if x.numel() else 0
+    if mx <= 0:
+        return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_SUMS), dtype=torch.int64, device=dev),
+                torch.empty((0, N_BOX), dtype=torch.int32, device=dev))
+    if mx > 4 * x.numel() or mx > _INT32_MAX:
+        u, inv = torch.unique(x, return_inverse=True)
+        k = int((u <= 0).sum().item())                       # sorted: the non-positive values come first
+        ids = u[k:].to(torch.int64)
+        a = (inv - (k - 1)).clamp_(min=0).to(torch.int32).contiguous()    # the row itself
+        lut = torch.arange(ids.numel() + 1, dtype=torch.int32, device=dev)
+        max_id = int(ids.numel())
+    else:
+        a = x.to(torch.int32).contiguous()
+        ids, lut, max_id = _lut(a)
+        ids = ids.to(torch.int64)
+    N = int(ids.numel())
+    sums = torch.zeros((N, N_SUMS), dtype=torch.int64, device=dev)
+    boxes = torch.zeros((N, N_BOX), dtype=torch.int32, device=dev)
+    X, Y, Z = (int(v) for v in a.shape)
+    _ffi.check(_ffi.lib.sk_instance_stats(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(sums),
+                                          _ffi.ptr(boxes), _ffi.stream_ptr(dev)))
+    return ids, sums, boxes
+
+
+def mask_to_bbox(mask: Tensor) -> Tuple[Tensor, Tensor]:
+    """(unique positive ids (N), boxes (6, N) as [x0, y0, z0, x1, y1, z1], inclusive) of a (1, X, Y, Z) instance mask
+    -- skoots/validate/lib.py:12-54, from the one-pass kernel instead of one Python iteration per instance.
+    Deliberate difference: the boxes are int32; the reference's int16 wraps beyond 32 767."""
+    assert mask.ndim == 4, "Mask ndim != 4"
+    ids, _, boxes = instance_sums(mask)
+    return ids.to(mask.dtype), boxes.t().contiguous()
