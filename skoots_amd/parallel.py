@@ -443,10 +443,8 @@ class ShardedVolume:
             del extra[max(0, n_streams - 1):]
             while len(extra) < n_streams - 1:
                 extra.append(model.clone_context())
-            for c in extra:   # same weights object; follow the switches of the primary
-                assert c.enc0 is model.enc0 and c.dec0 is model.dec0, "a stream context must share its model's layers"
-                c.precision, c.fold_upsample, c.box_store, c.defer_activation = (model.precision, model.fold_upsample,
-                                                                                model.box_store, model.defer_activation)
+            for c in extra:   # same weights object; the precision and the switches are the primary's (clone_context)
+                assert c.layers is model.layers, "a stream context must share its model's layers"
             ctxs = [model] + extra
         else:
             ctxs = [None]
