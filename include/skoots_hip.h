@@ -784,6 +784,55 @@ int sk_tiff_undo_predictor(void* rows, int64_t n_rows, int row_pixels, int sampl
                            void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Reading the reference's stores: Blosc-1 frames with the LZ4 codec
+ * ------------------------------------------------------------------------ */
+
+/* status[i] of sk_lz4_streams, status of sk_blosc_decode_host / sk_blosc_plan_host: 0, or why it was refused */
+#define SK_LZ4_E_RANGE 1         /* a table row outside [0, src_bytes) / [0, dst_bytes), negative, of an unknown kind, or stored with src_len != dst_len */
+#define SK_LZ4_E_INPUT 2         /* a token, a length byte, a literal run or an offset reaches past the end of the stream (a stream that ends right after a match included) */
+#define SK_LZ4_E_OFFSET 3        /* offset 0, or an offset that reaches before the start of the output */
+#define SK_LZ4_E_OUTPUT_LONG 4   /* the stream expands to more bytes than expected */
+#define SK_LZ4_E_OUTPUT_SHORT 5  /* the input ended after a literal run before dst_len bytes were produced */
+#define SK_BLOSC_E_HEADER 6      /* shorter than 16 bytes, version not 2, cbytes not the frame's length, nbytes not dst_bytes, typesize 0, blocksize 0 */
+#define SK_BLOSC_E_CODEC 7       /* inner codec not lz4, bitshuffle, or byte shuffle with a typesize above 16 */
+#define SK_BLOSC_E_FRAME 8       /* the block table, a block start or a split prefix reaches outside the frame, or a split block that does not divide */
+
+#define SK_LZ4_KIND_LZ4 0        /* one LZ4 raw block */
+#define SK_LZ4_KIND_STORED 1     /* the bytes as they are */
+
+/* Expands n_streams independent streams.  table (device, int64 (n_streams, 5), 8-byte aligned) holds per stream
+ * src_begin, src_len, dst_begin, dst_len, kind: src[src_begin .. + src_len) (any alignment) must expand to exactly
+ * dst_len bytes at dst + dst_begin.  status[i] (device) = 0 or one SK_LZ4_E_* code: 0 exactly when the row lies
+ * inside both buffers and the stream parses as an LZ4 raw block (token, literal length extended by 255s, literals,
+ * 2-byte little-endian offset, match length extended likewise, + 4), ends at src_len after a literal run and has
+ * produced dst_len bytes.  A failed stream never stops the others.  One wave64 workgroup per stream; matches read a
+ * 64 KiB ring of the output in LDS, never dst.  Every row is checked in the kernel: nothing is read outside a row's
+ * src range and nothing written outside its dst range whatever the bytes are; of a refused stream the dst range holds
+ * an undefined prefix.  Arguments are checked before the launch.  No reference counterpart (numcodecs / c-blosc on the host). */
+int sk_lz4_streams(const uint8_t* src, int64_t src_bytes, const int64_t* table, int n_streams, uint8_t* dst,
+                   int64_t dst_bytes, int32_t* status, void* stream);
+
+/* Undoes Blosc's byte shuffle: for every row (begin, bytes) of blocks (device, int64 (n_blocks, 2), 8-byte aligned),
+ * with ne = bytes / typesize, dst[begin + e * typesize + j] = src[begin + j * ne + e] and the bytes % typesize tail
+ * bytes are copied.  typesize 2..16, src != dst, begin of any alignment.  Nothing outside a block's range is read in
+ * src or written in dst; rows with a negative begin or bytes <= 0 are left alone. */
+int sk_blosc_unshuffle(const uint8_t* src, uint8_t* dst, const int64_t* blocks, int n_blocks, int typesize, void* stream);
+
+/* HOST, no GPU work.  Walks one frame that must expand to dst_bytes: header and block-table checks and the walk over
+ * the split prefixes, every offset checked against frame_bytes before it is used.  Fills streams (cap_streams rows of
+ * 5, as sk_lz4_streams takes them, offsets relative to the frame and to its output) and blocks (cap_blocks rows of
+ * begin, bytes: the blocks that are byte-shuffled) as far as the capacities reach; counts[0..3] = rows of each the
+ * frame has, typesize, 1 if blocks have to be unshuffled.  *status = 0 or SK_BLOSC_E_*.  The one frame parser: the
+ * host decoder and the device path's table both come from it. */
+int sk_blosc_plan_host(const uint8_t* frame, int64_t frame_bytes, int64_t dst_bytes, int64_t* streams,
+                       int64_t cap_streams, int64_t* blocks, int64_t cap_blocks, int64_t* counts, int32_t* status);
+
+/* HOST, no GPU work.  Decodes a whole frame into dst[0 .. dst_bytes): the same walk, the same LZ4 decoder text as
+ * the kernel compiled as host C++, the same acceptance rules and status codes.  *status = 0 or the first
+ * SK_LZ4_E_* / SK_BLOSC_E_* code met; of a refused frame dst holds undefined bytes.  Thread-safe. */
+int sk_blosc_decode_host(const uint8_t* frame, int64_t frame_bytes, uint8_t* dst, int64_t dst_bytes, int32_t* status);
+
+/* ------------------------------------------------------------------------ *
  * --convert: eval()'s stores and .trch tensors -> the pages of a TIFF stack
  * ------------------------------------------------------------------------ */
 

@@ -177,6 +177,10 @@ _SIGS = {
     "sk_deflate_streams": (i32, [vp, i32, i64, i32, vp, vp, vp, vp, sz, vp]),
     "sk_inflate_streams": (i32, [vp, vp, i32, vp, vp, i32, vp, vp]),
     "sk_tiff_undo_predictor": (i32, [vp, i64, i32, i32, i32, vp]),
+    "sk_lz4_streams": (i32, [vp, i64, vp, i32, vp, i64, vp, vp]),
+    "sk_blosc_unshuffle": (i32, [vp, vp, vp, i32, i32, vp]),
+    "sk_blosc_plan_host": (i32, [vp, i64, i64, vp, i64, vp, i64, vp, vp]),
+    "sk_blosc_decode_host": (i32, [vp, i64, vp, i64, vp]),
     "sk_convert_pages_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "sk_instance_stats_row_values": (i32, [i32]),
     "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),

@@ -3,14 +3,19 @@
 
 The ``zarr`` / ``numcodecs`` packages are not in this image.  What is written here follows the published v2 layout
 (``.zarray`` JSON + one C-order file per chunk, edge chunks padded to the full chunk shape), so the real package opens
-it.  Chunks are compressed with the numcodecs ``zlib`` codec (``{"id": "zlib", "level": 1}`` -- the stdlib's zlib; the
-reference's stores use zarr's default Blosc codec, which needs the absent ``numcodecs``) or stored raw
-(``compressor=None``); chunks that hold only the fill value are not written, as zarr does.  ``load`` reads raw, zlib
-and gzip stores and refuses every other codec by name.
+it.  Chunks are compressed with the numcodecs ``zlib`` codec (``{"id": "zlib", "level": 1}`` -- the stdlib's zlib) or
+stored raw (``compressor=None``); chunks that hold only the fill value are not written, as zarr does.  ``load`` reads
+raw, zlib and gzip stores and the stores the reference itself writes: zarr's default ``blosc`` compressor with the lz4
+codec and byte shuffle (``lib/blosc.py``; the frame carries everything, the ``.zarray`` fields ``cname``, ``shuffle`` and
+``blocksize`` are not looked at).  Before any chunk of a ``blosc`` store is decoded the first 16 bytes of every chunk
+file are checked: a file that is no Blosc-1 frame of a chunk, another inner codec (blosclz, zlib, zstd, snappy) or
+bitshuffle refuses the whole store with a ``RuntimeError`` that names the file and the codec.  Every other codec and
+every filter is refused by name.  Blosc is only read, never written: the zlib stores open everywhere.
 
 ``save_device`` writes the same zlib store from a torch tensor without taking the array to the host first: chunks are
 gathered and deflated on the tensor's device (``lib/deflate.py``), only compressed bytes cross to the host.
-``load_device`` is the way back: chunk files go to the device as they are and are inflated there."""
+``load_device`` is the way back: chunk files go to the device as they are and are inflated (zlib) or expanded and
+unshuffled (blosc) there."""
 from __future__ import annotations
 
 import gzip
@@ -121,21 +126,43 @@ def save_device(path: str, tensor, chunks: Optional[Sequence[int]] = None, budge
             timings["file_s"] = timings.get("file_s", 0.0) + time.perf_counter() - t0
 
 
+def _codec(path: str, meta: dict) -> Optional[str]:
+    """The codec id of a store both readers can read; everything else is refused by name, with one text."""
+    comp = meta.get("compressor")
+    codec = comp.get("id") if comp else None
+    if meta.get("zarr_format") != 2 or meta.get("filters") or codec not in (None, "zlib", "gzip", "blosc"):
+        raise RuntimeError(f"{path}: zarr v2 stores with compressor {codec!r} / filters {meta.get('filters')!r} cannot be "
+                           "read here (raw, zlib, gzip and blosc with the lz4 codec only)")
+    if meta.get("order", "C") != "C":
+        raise RuntimeError(f"{path}: only C-order stores are supported")
+    return codec
+
+
+def _check_blosc_frames(files: Sequence[str], chunk_bytes: int) -> None:
+    """Looks at the first 16 bytes of every chunk file of a ``blosc`` store before any chunk is decoded: a file that is
+    not a Blosc-1 frame of this store's chunks with the lz4 codec and at most a byte shuffle refuses the whole store."""
+    from . import blosc
+    for fn in files:
+        with open(fn, "rb") as f:
+            head = f.read(16)
+        why = blosc.refusal(head, os.path.getsize(fn), chunk_bytes)
+        if why is not None:
+            raise RuntimeError(f"{fn}: not a chunk a 'blosc' store of this reader holds: {why}")
+
+
 def load(path: str) -> np.ndarray:
     with open(os.path.join(path, ".zarray")) as f:
         meta = json.load(f)
-    comp = meta.get("compressor")
-    codec = comp.get("id") if comp else None
-    if meta.get("zarr_format") != 2 or meta.get("filters") or codec not in (None, "zlib", "gzip"):
-        raise RuntimeError(f"{path}: zarr v2 stores with compressor {codec!r} / filters {meta.get('filters')!r} cannot be "
-                           "read here (raw, zlib and gzip only: numcodecs / Blosc are not in this image)")
-    if meta.get("order", "C") != "C":
-        raise RuntimeError(f"{path}: only C-order stores are supported")
+    codec = _codec(path, meta)
     shape, chunks, dt = meta["shape"], meta["chunks"], np.dtype(meta["dtype"])
     out = np.full(shape, meta.get("fill_value") or 0, dtype=dt)
     grid = [range((s + c - 1) // c) for s, c in zip(shape, chunks)]
-    for idx in itertools.product(*grid):
-        fn = os.path.join(path, ".".join(str(i) for i in idx))
+    names = [os.path.join(path, ".".join(str(i) for i in idx)) for idx in itertools.product(*grid)]
+    if codec == "blosc":
+        from . import blosc
+        chunk_bytes = int(np.prod(chunks)) * dt.itemsize
+        _check_blosc_frames([fn for fn in names if os.path.exists(fn)], chunk_bytes)
+    for idx, fn in zip(itertools.product(*grid), names):
         if not os.path.exists(fn):
             continue  # missing chunk = fill value
         with open(fn, "rb") as f:
@@ -144,6 +171,11 @@ def load(path: str) -> np.ndarray:
             raw = zlib.decompress(raw)
         elif codec == "gzip":
             raw = gzip.decompress(raw)
+        elif codec == "blosc":
+            try:
+                raw = blosc.decode_host([raw], chunk_bytes)[0].tobytes()
+            except blosc.BloscError as e:
+                raise ValueError(f"{fn}: the Blosc frame does not decode: {e.reason}") from None
         block = np.frombuffer(raw, dtype=dt).reshape(chunks)
         sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, shape))
         out[sl] = block[tuple(slice(0, s.stop - s.start) for s in sl)]
@@ -160,21 +192,17 @@ def load_device(path: str, device, budget_bytes: int = LOAD_DEVICE_BUDGET, timin
     copy per chunk.  ``budget_bytes`` (256 MiB by default; a batch holds at least one chunk) bounds what a batch adds on
     the device besides the result: the uploaded chunk files + their inflated chunks.  The host holds the same chunk files
     twice for a moment (the list and its join for the one upload), which the budget does not count.
-    Missing chunks are the fill value.  ``gzip`` chunks are decompressed on the host and uploaded.  On ``"cpu"`` the
-    same code runs with the stdlib's zlib.  A chunk that does not inflate to the chunk's size raises ``ValueError``
-    naming its file."""
+    Missing chunks are the fill value.  ``gzip`` chunks are decompressed on the host and uploaded.  ``blosc`` chunk
+    files (lz4 codec) are uploaded as they are too and decoded by ``lib/blosc.py: decode_device`` (one wave per LZ4
+    stream, then the byte unshuffle, which takes one more copy of the batch's chunks that the budget does not count).
+    On ``"cpu"`` the same code runs with the stdlib's zlib and the host build of the Blosc decoder.  A chunk that does
+    not decode to the chunk's size raises ``ValueError`` naming its file."""
     import torch
 
     from . import deflate
     with open(os.path.join(path, ".zarray")) as f:
         meta = json.load(f)
-    comp = meta.get("compressor")
-    codec = comp.get("id") if comp else None
-    if meta.get("zarr_format") != 2 or meta.get("filters") or codec not in (None, "zlib", "gzip"):
-        raise RuntimeError(f"{path}: zarr v2 stores with compressor {codec!r} / filters {meta.get('filters')!r} cannot be "
-                           "read here (raw, zlib and gzip only: numcodecs / Blosc are not in this image)")
-    if meta.get("order", "C") != "C":
-        raise RuntimeError(f"{path}: only C-order stores are supported")
+    codec = _codec(path, meta)
     shape, chunks, dt = meta["shape"], meta["chunks"], np.dtype(meta["dtype"])
     if dt.byteorder == ">" or dt.kind not in "iufb":
         return torch.from_numpy(load(path)).to(device)   # nothing torch can view bytes as: the host reader decides
@@ -188,6 +216,9 @@ def load_device(path: str, device, budget_bytes: int = LOAD_DEVICE_BUDGET, timin
         fn = os.path.join(path, ".".join(str(i) for i in idx))
         if os.path.exists(fn):
             todo.append((idx, fn, os.path.getsize(fn)))
+    if codec == "blosc":
+        from . import blosc
+        _check_blosc_frames([fn for _, fn, _ in todo], chunk_bytes)
 
     def flush(part, files):
         t0 = time.perf_counter()
@@ -196,6 +227,11 @@ def load_device(path: str, device, budget_bytes: int = LOAD_DEVICE_BUDGET, timin
                 rows = deflate.inflate_streams(files, chunk_bytes, dev, timings=timings)
             except deflate.InflateError as e:
                 raise ValueError(f"{part[e.index][1]}: {e}") from None
+        elif codec == "blosc":
+            try:
+                rows = blosc.decode_device(files, chunk_bytes, dev, timings=timings)
+            except blosc.BloscError as e:
+                raise ValueError(f"{part[e.index][1]}: the Blosc frame does not decode: {e.reason}") from None
         else:
             for (idx, fn, _), raw in zip(part, files):
                 if len(raw) != chunk_bytes:
