@@ -881,6 +881,45 @@ int sk_instance_stats(const int32_t* labels, int X, int Y, int Z, const int32_t*
                       int32_t* boxes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * flood_and_stitch (skoots/utils/flood_and_stitch.py)
+ * ------------------------------------------------------------------------ */
+
+/* flood_and_stitch.py:63-69 (scipy.ndimage.label on every slice): P planes of H x W uint8 (foreground = nonzero),
+ * labelled 4-connected, every plane on its own, all planes in one launch sequence.  Voxel (p, h, w) is read at
+ * mask[p in_sp + h in_sh + w in_sw] and written at labels[p out_sp + h out_sh + w out_sw] (element strides, all
+ * positive), so any axis of a contiguous volume is a plane axis in place; the kernels are tuned for in_sw = out_sw = 1.
+ * Ids are GLOBAL: 1 + the component's rank among all components in (plane, row, column) order of first voxels, so
+ * plane p owns offsets[p] + 1 .. offsets[p + 1] in scipy's order.  offsets: P + 1 int32 (exclusive prefix of the
+ * planes' component counts), *total = offsets[P]; both device.  P H W < 2^31 - 4096, and the planes' 16 x 64 tiles
+ * and their 2048-voxel chunks (a plane's last one may be partial) number at most 2^22 each: a workgroup per tile and per
+ * chunk, so tens of millions of tiny planes are refused, not launched.  workspace: the query's bytes (0 for extents the
+ * entry point refuses). */
+size_t sk_label_planes_workspace_bytes(int P, int H, int W);
+int sk_label_planes(const uint8_t* mask, int P, int H, int W, int64_t in_sp, int64_t in_sh, int64_t in_sw, int32_t* labels,
+                    int64_t out_sp, int64_t out_sh, int64_t out_sw, int32_t* offsets, int32_t* total, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
+/* flood_and_stitch.py:93-101 for every label of every slice at once: one row (id_a, id_b, n) per pair of components of
+ * planes p and p + 1 of the global-id labels (strides as above) that share n > 0 voxel positions; one launch for all
+ * plane pairs.  rows: capacity x 3 int32, compacted, in no particular order.  The pairs are counted in an
+ * open-addressing table of `capacity` slots inside `workspace` (the query's bytes, 8-byte aligned; zeroed here).
+ * counts (3 uint32, device): [0] pairs stored, [1] 0 if every pair found a slot; otherwise the refused pairs, each
+ * counted once per top-left corner of its overlap region -- exact where every such region has one corner, never too
+ * small otherwise (the exact number of distinct refused pairs would need the very table that is full); [2] rows
+ * written = [0].  With counts[1] != 0 the rows are incomplete: run again with capacity >= 2 (counts[0] + counts[1]). */
+size_t sk_plane_overlaps_workspace_bytes(int capacity);
+int sk_plane_overlaps(const int32_t* labels, int P, int H, int W, int64_t sp, int64_t sh, int64_t sw, int32_t* rows, int capacity,
+                      uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* flood_and_stitch.py:74-128, the two greedy stitching passes, on tables only (stitch_host.cpp; plain C++, every
+ * pointer HOST).  offsets_host: n_planes + 1 entries as sk_label_planes writes them; rows_host: n_rows x 3 as
+ * sk_plane_overlaps writes them, sorted by (id_a, id_b).  lut_host[id] (offsets[n_planes] + 1 entries, lut[0] = 0) = the
+ * label component `id` carries after both passes (before the final renumbering), *max_label_host the largest.
+ * SK_ERR_ARG for malformed tables, SK_ERR_CAPACITY if a new id would pass INT32_MAX. */
+int sk_stitch_walk_host(const int32_t* offsets_host, int n_planes, const int32_t* rows_host, int64_t n_rows, int32_t* lut_host,
+                        int32_t* max_label_host);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 
