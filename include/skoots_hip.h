@@ -880,6 +880,22 @@ int sk_instance_stats_row_values(int which);
 int sk_instance_stats(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, int64_t* sums,
                       int32_t* boxes, void* stream);
 
+/* Marching-cubes cell classes of every instance (ABI 15): what the reference measures with
+ * skimage.measure.marching_cubes on one binary mask per id (skoots/validate/stats.py:30-48), as one pass.  labels, lut,
+ * max_id and N are those of sk_instance_stats.  Cell (x, y, z) is the 2 x 2 x 2 block of voxels with that low corner;
+ * bit b of its configuration for row a is set when the voxel (x + (b & 1), y + ((b >> 1) & 1), z + ((b >> 2) & 1)) has
+ * row a.  For every row a among the corners of a cell whose configuration is not 255,
+ *   cells[(a - 1) * n_classes + class_of[configuration]] += 1      (int64),
+ * so a cell shared by k instances counts once for each of them.  class_of: 256 bytes in device memory; an entry
+ * >= n_classes is skipped.  closed = 0 has the cells 0 .. extent - 2 of every axis (a surface cut by the volume's face
+ * stays open, as in the reference; no cell when an extent is 1); closed = 1 has -1 .. extent - 1, the mask padded with one
+ * layer of background, and a corner outside the volume matches no row.  The entry point zeroes cells itself
+ * (stream-ordered); integer atomics only, so the result is exact and the same on every run.  Checked before anything is
+ * written: extents, N and max_id not negative, X Y Z < 2^62, n_classes in 1..32, closed 0 or 1, no NULL pointer,
+ * pointers aligned to their elements.  An empty volume or N == 0 returns SK_OK and writes nothing. */
+int sk_instance_mesh_cells(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                           const uint8_t* class_of, int n_classes, int closed, int64_t* cells, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * flood_and_stitch (skoots/utils/flood_and_stitch.py)
  * ------------------------------------------------------------------------ */

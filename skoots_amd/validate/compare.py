@@ -7,23 +7,29 @@ integer sums and a box per instance, and ``derive`` turns them into volume, cent
 ellipsoid with the same second moments.  Every kernel output is an integer, so the measurement is exact and the same
 on every run.
 
-There is no marching-cubes surface area: ``face_area`` is the area of the exposed voxel faces, which is exact for what
-it defines and overestimates a curved surface.
+``face_area`` is the area of the exposed voxel faces, which is exact for what it defines and overestimates a curved
+surface.  The reference's marching-cubes ``surface_area`` is available with ``surface="open"`` (its
+meaning) or ``"closed"``: a second kernel pass (``sk_instance_mesh_cells``) counts every instance's
+cells per triangle class, integers again, and ``class_areas`` turns the counts into an area on the host.
 """
 from __future__ import annotations
 
 import argparse
 import logging
+import math
 import os
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from .lib import check_shape, instance_sums
+from .lib import check_shape, id_rows, instance_mesh_cells, instance_sums
+from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
                "axis_minor")
+SURFACE_COLUMNS = "surface_area,surface_to_volume"       # appended with --surface-area
+SURFACE_MODES = (None, "open", "closed")
 
 # An eigenvalue of the covariance matrix below this share of the largest one is the round-off of an exactly flat
 # object (a line, a one-voxel-thick sheet) and is set to 0 together with negative round-off: 2 sqrt(5 lambda) would
@@ -85,7 +91,40 @@ def derive(sums: Tensor, boxes: Tensor, shape, spacing=(1.0, 1.0, 1.0)) -> Dict[
     }
 
 
-def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0)) -> Dict[str, Tensor]:
+def class_areas(spacing=(1.0, 1.0, 1.0)) -> Tensor:
+    """(30) float64 host tensor: the mesh area of one cell of each class of ``mc_table.CLASS_TRIANGLES`` at the voxel
+    spacing (sx, sy, sz).  A triangle of type (a, b, c) has the cross product (a sy sz, b sx sz, c sx sy) / 4 and half
+    its length as area; a class sums its triangles in the table's order, so the value is the same wherever it is
+    computed."""
+    sx, sy, sz = _spacing(spacing)
+    tri = [math.sqrt((a * sy * sz) ** 2 + (b * sx * sz) ** 2 + (c * sx * sy) ** 2) / 8.0 for a, b, c in TRIANGLE_TYPES]
+    out = []
+    for row in CLASS_TRIANGLES:
+        area = 0.0
+        for n, t in zip(row, tri):
+            area += n * t
+        out.append(area)
+    return torch.tensor(out, dtype=torch.float64)
+
+
+def mesh_area(cells: Tensor, spacing=(1.0, 1.0, 1.0)) -> Tensor:
+    """(N) float64 host tensor: ``cells.double() @ class_areas(spacing)`` of (N, 30) cell counts, summed on the host
+    class by class in the table's order, so that a row's area does not depend on how many rows are computed with it or
+    on a BLAS: the dict, the CSV file and ``get_surface_area`` agree to the last bit."""
+    c = cells.cpu().to(torch.float64)
+    area = torch.zeros(c.shape[0], dtype=torch.float64)
+    for k, a in enumerate(class_areas(spacing).tolist()):
+        area += c[:, k] * a
+    return area
+
+
+def surface_columns(cells: Tensor, volume: Tensor, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor]:
+    """``surface_area`` and ``surface_to_volume`` (float64, host) from the (N, 30) cell counts and the (N) volumes"""
+    area = mesh_area(cells, spacing)
+    return {"surface_area": area, "surface_to_volume": area / volume.cpu().to(torch.float64)}
+
+
+def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -94,44 +133,70 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0)) -> Dict[str, Tenso
     ``centroid`` (N, 3) float64 in physical units, ``face_area`` float64, ``faces`` (N, 3) int64 exposed faces with
     their normal along x / y / z, ``axis_lengths`` (N, 3) float64 descending, and ``sums`` (N, 13) int64, the raw
     accumulators.  (The reference's sketch of the same name returns ``id``, ``volume`` and a marching-cubes
-    ``surface_area`` and cannot run: skoots/validate/compare.py:8-28.)"""
+    ``surface_area`` and cannot run: skoots/validate/compare.py:8-28.)
+
+    ``surface="open"`` or ``"closed"`` adds, from one more kernel pass, ``mesh_cells`` (N, 30) int64, ``surface_area``
+    float64 -- the area of the marching-cubes mesh of ``x == id``, which is what the reference's ``get_surface_area``
+    returns -- and ``surface_to_volume`` = ``surface_area / volume``.  "open" is the reference's meaning: where an
+    instance touches a face of the volume its surface stays open.  "closed" measures the mask padded with one layer of
+    background.  Deliberate difference: an instance that fills the whole volume in open mode, or any instance of a
+    volume with an extent below 2, has area 0 here; scikit-image raises there ("No surface found", "must be at least
+    2x2x2"), which would fail the whole mask for one instance (DESIGN.md §21)."""
+    if surface not in SURFACE_MODES:
+        raise ValueError(f"surface must be one of {SURFACE_MODES}, got {surface!r}")
     spacing = _spacing(anisotropy)
-    ids, sums, boxes = instance_sums(x)
+    rows = id_rows(x)                                       # once, for both kernels
+    ids, sums, boxes = instance_sums(x, rows)
     shape = tuple(x.shape[-3:])
     out = {"id": ids}
     # N rows of a few numbers: derived on the host, where the eigenvalues are computed anyway, and uploaded -- the
     # same machine code as format_csv runs, so the file and this dict agree to the last bit
     out.update({k: v.to(sums.device) for k, v in derive(sums.cpu(), boxes.cpu(), shape, spacing).items()})
     out["sums"] = sums
+    if surface is not None:
+        _, cells = instance_mesh_cells(x, closed=surface == "closed", rows=rows)
+        out["mesh_cells"] = cells
+        out.update({k: v.to(sums.device) for k, v in surface_columns(cells, out["volume"], spacing).items()})
     return out
 
 
 def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=(1.0, 1.0, 1.0),
-               min_voxels: int = 1) -> str:
+               min_voxels: int = 1, mesh_cells: Optional[Tensor] = None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
-    instance with at least ``min_voxels`` voxels; floats are printed with ``repr``."""
+    instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
+    counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
+    it was before they existed."""
     spacing = _spacing(spacing)
-    d = {k: v.cpu().tolist() for k, v in derive(sums.cpu(), boxes.cpu(), shape, spacing).items()}
+    d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
+    if mesh_cells is not None:
+        d.update(surface_columns(mesh_cells, d["volume"], spacing))
+    d = {k: v.cpu().tolist() for k, v in d.items()}
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
-             CSV_COLUMNS + "\n"]
+             CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
         cells = [int(u), d["voxels"][i], repr(d["volume"][i]), *d["bbox"][i], int(d["touches_border"][i]),
                  *(repr(v) for v in d["centroid"][i]), repr(d["face_area"][i]),
                  *(repr(v) for v in d["axis_lengths"][i])]
+        if mesh_cells is not None:
+            cells += [repr(d["surface_area"][i]), repr(d["surface_to_volume"][i])]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser = argparse.ArgumentParser(prog="python -m skoots_amd.validate.compare",
-                                     description="SKOOTS: volume, box, centroid, face area and axes of every instance")
+                                     description="SKOOTS: volume, box, centroid, face area and axes of every instance, "
+                                                 "and the mesh surface area on request")
     parser.add_argument("mask", type=str, help="Path to an instance mask (.tif or .npy, stored [Z, X, Y])")
     parser.add_argument("--spacing", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("SX", "SY", "SZ"),
                         help="Voxel spacing along x, y and z")
     parser.add_argument("--min-voxels", type=int, default=1, help="Leave out instances with fewer voxels")
+    parser.add_argument("--surface-area", type=str, default=None, choices=("open", "closed"),
+                        help="Append surface_area,surface_to_volume: the marching-cubes mesh area of every instance, "
+                             "left open where the volume's faces cut it (the reference's meaning) or closed there")
     parser.add_argument("--out", type=str, default=None, help="Output file (default: <mask>_instance_stats.csv)")
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
@@ -150,8 +215,11 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
     mask = load_mask(args.mask)
     logging.debug(f"Mask Shape: {tuple(mask.shape)}")
     check_shape(mask.shape[-3:])
-    ids, sums, boxes = instance_sums(mask.to("cuda"))       # the HIP library: no CPU fallback
-    text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels)
+    dev_mask = mask.to("cuda")                              # the HIP library: no CPU fallback
+    rows = id_rows(dev_mask)                                # once, for both kernels
+    ids, sums, boxes = instance_sums(dev_mask, rows)
+    cells = instance_mesh_cells(dev_mask, args.surface_area == "closed", rows)[1] if args.surface_area else None
+    text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)

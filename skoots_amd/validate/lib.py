@@ -8,6 +8,7 @@ pair; here one kernel pass builds the (gt, pred) contingency tables and a second
 
 ``instance_sums`` measures every instance of one mask in a single kernel pass; ``mask_to_bbox`` is the
 reference's function of that name on top of it, and ``validate/compare.py`` derives the per-instance statistics.
+``instance_mesh_cells`` counts every instance's marching-cubes cells per class in one more pass.
 """
 from __future__ import annotations
 
@@ -171,21 +172,18 @@ def _as_volume(x: Tensor, name: str) -> Tensor:
     return x
 
 
-def instance_sums(x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-    """(ids (N) int64 ascending, sums (N, 13) int64, boxes (N, 6) int32) of the positive ids of an (X, Y, Z) integer
-    device tensor: one ``sk_instance_stats`` launch for every instance (include/skoots_hip.h names the columns).
+def _id_rows(x: Tensor):
+    """The prologue of the per-instance kernels: ``(a, ids, lut, max_id)`` for an (X, Y, Z) integer device tensor --
+    ``a`` int32 contiguous, ``ids`` (N) int64 ascending, and the table that takes a value of ``a`` to its row 1..N --
+    or ``None`` when x has no positive id.
 
     Ids reach the kernel through the ``_lut`` table, which has ``max id + 1`` entries; when the largest id exceeds four
     times the voxel count (or int32) the mask is relabelled through ``torch.unique(return_inverse=True)`` instead, so
     that a few huge ids do not allocate a huge table."""
-    assert _ffi.lib.sk_instance_stats_row_values(0) == N_SUMS and _ffi.lib.sk_instance_stats_row_values(1) == N_BOX
-    x = _as_volume(x, "x")
-    check_shape(x.shape)
     dev = x.device
     mx = int(x.max().item()) if x.numel() else 0
     if mx <= 0:
-        return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_SUMS), dtype=torch.int64, device=dev),
-                torch.empty((0, N_BOX), dtype=torch.int32, device=dev))
+        return None
     if mx > 4 * x.numel() or mx > _INT32_MAX:
         u, inv = torch.unique(x, return_inverse=True)
         k = int((u <= 0).sum().item())                       # sorted: the non-positive values come first
@@ -197,6 +195,33 @@ def instance_sums(x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         a = x.to(torch.int32).contiguous()
         ids, lut, max_id = _lut(a)
         ids = ids.to(torch.int64)
+    return a, ids, lut, max_id
+
+
+def id_rows(x: Tensor):
+    """``(volume, rows)`` of an integer device tensor (X, Y, Z) or (1, X, Y, Z): its (X, Y, Z) view and ``_id_rows`` of
+    it.  ``instance_sums`` and ``instance_mesh_cells`` take the pair as ``rows=``, so a caller that runs both kernels
+    on one mask pays for ``x.max()``, ``torch.unique`` and the table once."""
+    x = _as_volume(x, "x")
+    return x, _id_rows(x)
+
+
+def instance_sums(x: Tensor, rows=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(ids (N) int64 ascending, sums (N, 13) int64, boxes (N, 6) int32) of the positive ids of an (X, Y, Z) integer
+    device tensor: one ``sk_instance_stats`` launch for every instance (include/skoots_hip.h names the columns).
+    ``_id_rows`` says how the ids reach the kernel; ``rows`` is ``id_rows(x)`` when the caller already has it."""
+    assert _ffi.lib.sk_instance_stats_row_values(0) == N_SUMS and _ffi.lib.sk_instance_stats_row_values(1) == N_BOX
+    if rows is None:
+        x = _as_volume(x, "x")
+        check_shape(x.shape)                                 # before anything touches the device
+        rows = (x, _id_rows(x))
+    x, rows = rows
+    check_shape(x.shape)
+    dev = x.device
+    if rows is None:
+        return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_SUMS), dtype=torch.int64, device=dev),
+                torch.empty((0, N_BOX), dtype=torch.int32, device=dev))
+    a, ids, lut, max_id = rows
     N = int(ids.numel())
     sums = torch.zeros((N, N_SUMS), dtype=torch.int64, device=dev)
     boxes = torch.zeros((N, N_BOX), dtype=torch.int32, device=dev)
@@ -204,6 +229,34 @@ def instance_sums(x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     _ffi.check(_ffi.lib.sk_instance_stats(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(sums),
                                           _ffi.ptr(boxes), _ffi.stream_ptr(dev)))
     return ids, sums, boxes
+
+
+def instance_mesh_cells(x: Tensor, closed: bool = False, rows=None) -> Tuple[Tensor, Tensor]:
+    """(ids (N) int64 ascending, cells (N, 30) int64) of the positive ids of an (X, Y, Z) integer device tensor: how
+    many marching-cubes cells of each class of ``mc_table.CLASS_TRIANGLES`` every instance has, from one
+    ``sk_instance_mesh_cells`` launch.  ``cells.double() @ class_areas(spacing)`` is the area of the
+    mesh scikit-image's marching cubes gives ``x == id``.
+
+    ``closed=False`` is the reference's meaning: the cells lie inside the volume, so a surface cut by a face of the
+    volume stays open there.  ``closed=True`` measures the mask padded with one layer of background.  ``rows`` is
+    ``id_rows(x)`` when the caller already has it."""
+    from .mc_table import CLASS_OF, CLASS_TRIANGLES
+    x, rows = id_rows(x) if rows is None else rows
+    X, Y, Z = (int(v) for v in x.shape)
+    if X * Y * Z >= 2 ** 62:
+        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure: X*Y*Z must stay below 2^62")
+    dev = x.device
+    n_classes = len(CLASS_TRIANGLES)
+    if rows is None:
+        return (torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty((0, n_classes), dtype=torch.int64, device=dev))
+    a, ids, lut, max_id = rows
+    N = int(ids.numel())
+    cells = torch.zeros((N, n_classes), dtype=torch.int64, device=dev)
+    class_of = torch.tensor(CLASS_OF, dtype=torch.uint8, device=dev)
+    _ffi.check(_ffi.lib.sk_instance_mesh_cells(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(class_of),
+                                               n_classes, int(bool(closed)), _ffi.ptr(cells), _ffi.stream_ptr(dev)))
+    return ids, cells
 
 
 def mask_to_bbox(mask: Tensor) -> Tuple[Tensor, Tensor]:

@@ -4,10 +4,9 @@
 ``get_volume`` has the evident intent of the reference's function of that name, which cannot run
 (``torch.sum`` of a Python int raises ``TypeError``, stats.py:24).
 
-There is deliberately no ``get_surface_area``.  The reference's is a marching-cubes mesh area
-(``skimage.measure.marching_cubes``, stats.py:30-48); scikit-image is not available where this project is tested, so
-such an area could not be checked against it, and a function of the same name with another meaning would mislead.
-``get_face_area`` is what is offered instead: the area of the exposed voxel faces, exact for what it defines and an
+``get_surface_area`` is the reference's marching-cubes mesh area (``skimage.measure.marching_cubes`` and
+``mesh_surface_area``, stats.py:30-48) without a mesh: one kernel pass counts the mask's cells per triangle class
+(DESIGN.md §21).  ``get_face_area`` is the area of the exposed voxel faces, exact for what it defines and an
 overestimate of a curved surface.
 """
 from __future__ import annotations
@@ -17,8 +16,8 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor
 
-from .compare import _spacing
-from .lib import instance_sums
+from .compare import _spacing, mesh_area
+from .lib import instance_mesh_cells, instance_sums
 
 
 def _one_row(x: Tensor) -> Tensor:
@@ -45,3 +44,18 @@ def get_face_area(x: Tensor, spacing: Union[List[float], Tensor]) -> Tensor:
     sx, sy, sz = _spacing(spacing)
     f = _one_row(x)[10:13].to(torch.float64)
     return f[0] * (sy * sz) + f[1] * (sx * sz) + f[2] * (sx * sy)
+
+
+def get_surface_area(x: Tensor, anisotropy_ratio: Union[List[float], Tensor], closed: bool = False) -> Tensor:
+    """The area of the marching-cubes mesh of ``x > 0`` at the voxel spacing ``anisotropy_ratio`` (float64, on x's
+    device) -- stats.py:30-48, which meshes ``x.gt(0).mul(255)`` at level 127.5.  ``closed=False`` is the reference's
+    meaning: the mesh stays open where the mask touches a face of the volume; ``closed=True`` pads the mask with one
+    layer of background first.
+
+    Deliberate difference: a mask without surface inside the volume (empty, or full in open mode) or with an extent
+    below 2 gives 0 where scikit-image raises ("No surface found", "must be at least 2x2x2")."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    _, cells = instance_mesh_cells((x > 0).to(torch.int32), closed=closed)
+    area = mesh_area(cells, anisotropy_ratio)            # checks the spacing, also for a mask without foreground
+    return (area[0] if area.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
