@@ -668,13 +668,26 @@ int sk_skeleton_to_mask(const float* points, int64_t n_points, const int32_t* of
  * stay in the workspace for sk_skeletonize_emit.  Synchronises `stream` (the crop table is copied from the host).
  * sk_skeletonize_emit: points[offsets[i] ..] = the skeleton voxels of object i in raster order of its crop, as int32
  * crop coordinates (x, y, z); offsets (n + 1) int32 is the exclusive prefix sum of counts; no row at or beyond
- * n_points is written. */
+ * n_points is written.
+ *
+ * sk_skeleton_graph (ABI 16): the skeletons that sk_skeletonize left in the workspace, read as
+ * graphs -- called after it with the same boxes and workspace, like sk_skeletonize_emit; one workgroup per object.  A
+ * link is an unordered pair of skeleton voxels of one object that are 26-neighbours, the degree of a voxel the number
+ * of its links.  graph (n, 12) int64, row i: [0] skeleton voxels (= counts[i]), [1] voxels of degree 0, [2] of degree
+ * 1 (endpoints), [3] of degree 2 (chain voxels), [4] of degree >= 3 (junction voxels), [5..11] links by direction
+ * class (|dx|, |dy|, |dz|) = (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1).  Every link is counted once;
+ * [2] + 2 [3] + the degrees of the junction voxels = 2 sum([5..11]).  All sums are integers reduced inside the
+ * workgroup: the same on every run.  An empty skeleton gives a row of zeros.
+ * sk_skeleton_graph_row_values: 12, the values per row. */
 size_t sk_skeletonize_workspace_bytes(const int32_t* boxes_host, int n);
 int sk_skeletonize(const int32_t* labels, int X, int Y, int Z, const int32_t* ids, const int32_t* boxes_host, int n,
                    void* workspace, size_t workspace_bytes, int32_t* counts, int32_t* stats, int32_t* error,
                    void* stream);
 int sk_skeletonize_emit(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
                         const int32_t* offsets, int64_t n_points, int32_t* points, void* stream);
+int sk_skeleton_graph_row_values(void);
+int sk_skeleton_graph(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
+                      int64_t* graph, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Validation metrics (skoots/validate/lib.py:190-229 mask_iou): iou (N, M) fp32 of the N

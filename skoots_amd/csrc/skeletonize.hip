@@ -363,6 +363,82 @@ __global__ void __launch_bounds__(kThreads) emit_kernel(const SkelObj* __restric
     }
 }
 
+// The skeleton of object i read as a graph: a link is an unordered pair of skeleton voxels that
+// are 26-neighbours, the degree of a voxel the number of its links.  Row i of `graph`: voxels, voxels of degree 0, 1,
+// 2 and >= 3, then the links by direction class (|dx|, |dy|, |dz|) in the order of kLinkClass.  A link is counted
+// once, from the voxel that sees it among its 13 raster-following neighbours: bits 14 .. 26 of the neighbourhood code.
+constexpr int kGraphValues = 12;
+constexpr int kLinkClasses = 7;
+
+struct LinkMasks {
+    uint32_t m[kLinkClasses];
+};
+constexpr LinkMasks make_link_masks() {
+    // (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), indexed by 4 |dx| + 2 |dy| + |dz|
+    constexpr int kLinkClass[8] = {-1, 2, 1, 5, 0, 4, 3, 6};
+    LinkMasks k{};
+    for (int c = 14; c < 27; ++c) {
+        const int dx = c / 9 - 1, dy = c / 3 % 3 - 1, dz = c % 3 - 1;
+        k.m[kLinkClass[4 * (dx != 0) + 2 * (dy != 0) + (dz != 0)]] |= 1u << c;
+    }
+    return k;
+}
+
+__global__ void __launch_bounds__(kThreads) graph_kernel(const SkelObj* __restrict__ objs,
+                                                         const uint32_t* __restrict__ work,
+                                                         long long* __restrict__ graph) {
+    constexpr LinkMasks kLink = make_link_masks();
+    constexpr int kWaves = kThreads / 64;
+    __shared__ long long part[kWaves][kGraphValues];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const SkelObj o = objs[i];
+    const int PX = o.cx + 2, PY = o.cy + 2, WZ = (o.cz + 2 + 31) >> 5;
+    const int W = PX * PY * WZ;
+    const uint32_t* img = work + o.off;
+    // 64-bit from the first addition on: a crop holds up to 2^30 voxels with 13 forward links each
+    long long acc[kGraphValues];
+#pragma unroll
+    for (int k = 0; k < kGraphValues; ++k) acc[k] = 0;
+    for (int w = tid; w < W; w += kThreads) {
+        const uint32_t cur = img[w];
+        if (!cur) continue;
+        const int wz = w % WZ, t = w / WZ, y = t % PY, x = t / PY;
+        // the pad rows are zero after sk_skeletonize; a plane that is not its result must not send a read outside
+        if (x < 1 || x > o.cx || y < 1 || y > o.cy) continue;
+        uint64_t v[9];
+#pragma unroll
+        for (int r = 0; r < 9; ++r) v[r] = row_bits(img, ((x + r / 3 - 1) * PY + (y + r % 3 - 1)) * WZ, wz, WZ);
+        uint32_t bits = cur;
+        while (bits) {
+            const int b = __builtin_ctz(bits);
+            bits &= bits - 1;
+            const uint32_t n = gather27(v, b);
+            const int degree = __builtin_popcount(n & ~kCentre);
+            acc[0] += 1;
+            acc[1] += degree == 0;
+            acc[2] += degree == 1;
+            acc[3] += degree == 2;
+            acc[4] += degree >= 3;
+#pragma unroll
+            for (int k = 0; k < kLinkClasses; ++k) acc[5 + k] += __builtin_popcount(n & kLink.m[k]);
+        }
+    }
+    // integer sums: wave shuffle, then one LDS row per wave, then one thread per column writes the row
+#pragma unroll
+    for (int k = 0; k < kGraphValues; ++k) {
+        long long a = acc[k];
+        for (int step = 32; step > 0; step >>= 1) a += __shfl_down(a, step, 64);
+        if ((tid & 63) == 0) part[tid >> 6][k] = a;
+    }
+    __syncthreads();
+    if (tid < kGraphValues) {
+        long long a = 0;
+#pragma unroll
+        for (int wv = 0; wv < kWaves; ++wv) a += part[wv][tid];
+        graph[(long long)i * kGraphValues + tid] = a;
+    }
+}
+
 struct Layout {
     std::vector<SkelObj> objs;
     size_t table_bytes = 0;
@@ -448,6 +524,25 @@ int sk_skeletonize_emit(const int32_t* boxes_host, int n, const void* workspace,
     emit_kernel<<<n, kThreads, 0, (hipStream_t)stream>>>((const SkelObj*)workspace,
                                                          (const uint32_t*)((const char*)workspace + L.table_bytes),
                                                          offsets, n_points, points);
+    SK_CHECK_LAUNCH();
+    return SK_OK;
+}
+
+int sk_skeleton_graph_row_values(void) { return kGraphValues; }
+
+int sk_skeleton_graph(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes, int64_t* graph,
+                      void* stream) {
+    SK_CHECK_ARG(boxes_host && workspace && graph && n > 0, "sk_skeleton_graph: bad arguments");
+    Layout L;
+    const int rc = plan(boxes_host, n, 0, 0, 0, L);
+    if (rc != SK_OK) return rc;
+    SK_CHECK_ARG(workspace_bytes >= L.table_bytes + (size_t)L.words * 4,
+                 "sk_skeleton_graph: workspace of %zu bytes, %zu needed", workspace_bytes,
+                 L.table_bytes + (size_t)L.words * 4);
+    SK_CHECK_ARG(((uintptr_t)graph & 7) == 0, "sk_skeleton_graph: graph must be 8-byte aligned");
+    graph_kernel<<<n, kThreads, 0, (hipStream_t)stream>>>((const SkelObj*)workspace,
+                                                          (const uint32_t*)((const char*)workspace + L.table_bytes),
+                                                          (long long*)graph);
     SK_CHECK_LAUNCH();
     return SK_OK;
 }

@@ -1,6 +1,7 @@
 """``skoots.lib.morphology`` dilations on the MI355X
 (reference: skoots/lib/morphology.py:155-175 ``binary_dilation``, :178-199 ``binary_dilation_2d``), and the Lee
-thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skeletonize``, ``thin_objects``)."""
+thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skeletonize``, ``thin_objects``) with the
+skeletons read as graphs (``skeleton_graph``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -41,14 +42,9 @@ def binary_dilation_2d(image: Tensor) -> Tensor:
 THIN_ERRORS = {1: "a re-check round bound was hit", 2: "the pass bound was hit"}
 
 
-def thin_objects(labels: Tensor, ids, boxes) -> Tuple[Tensor, np.ndarray, np.ndarray]:
-    """Lee thinning of every object in its own crop, in one launch (one workgroup per object).
-
-    labels (X, Y, Z) int32 on the GPU; ids: n object ids; boxes (n, 6) ints (x0, y0, z0, x1, y1, z1): object i is
-    thinned in the binary crop ``labels[x0:x1, y0:y1, z0:z1] == ids[i]`` (voxels of other ids are background).
-    Returns (points, counts, stats): points (sum(counts), 3) int32 on the GPU, the skeleton voxels of object 0, 1, ...
-    in raster order of their crop as crop coordinates; counts (n,) int64; stats (n, 2) = passes and the most
-    re-check rounds of one sub-iteration (the kernel's counters)."""
+def _thin(labels: Tensor, ids, boxes):
+    """The ``sk_skeletonize`` launch of ``thin_objects`` and ``skeleton_graph``: ``None`` without a box, else
+    ``(boxes_p, n, work, nbytes, counts)`` and ``stats``, both still on the device, the skeletons in ``work``."""
     if labels.ndim != 3:
         raise ValueError("labels must be (X, Y, Z)")
     _ffi.require_gpu(labels, "labels")
@@ -58,7 +54,7 @@ def thin_objects(labels: Tensor, ids, boxes) -> Tuple[Tensor, np.ndarray, np.nda
     boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 6))
     n = boxes.shape[0]
     if n == 0:
-        return torch.zeros((0, 3), dtype=torch.int32, device=dev), np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
+        return None
     ids_d = torch.as_tensor(np.asarray(ids, dtype=np.int32).reshape(-1), device=dev)
     if ids_d.numel() != n:
         raise ValueError("one id per box")
@@ -71,20 +67,70 @@ def thin_objects(labels: Tensor, ids, boxes) -> Tuple[Tensor, np.ndarray, np.nda
     stats = torch.empty((n, 2), dtype=torch.int32, device=dev)
     err = torch.empty(1, dtype=torch.int32, device=dev)
     X, Y, Z = labels.shape
-    stream = _ffi.stream_ptr(dev)
     _ffi.check(_ffi.lib.sk_skeletonize(_ffi.ptr(labels), X, Y, Z, _ffi.ptr(ids_d), boxes_p, n, _ffi.ptr(work),
-                                       C.c_size_t(nbytes), _ffi.ptr(counts), _ffi.ptr(stats), _ffi.ptr(err), stream))
+                                       C.c_size_t(nbytes), _ffi.ptr(counts), _ffi.ptr(stats), _ffi.ptr(err),
+                                       _ffi.stream_ptr(dev)))
     code = int(err.item())
     if code:
         msg = "; ".join(v for k, v in THIN_ERRORS.items() if code & k)
         raise _ffi.SkootsHipError(f"sk_skeletonize: {msg} (error word {code})")
+    return (boxes, boxes_p, n, work, nbytes, counts), stats    # boxes: boxes_p points into it
+
+
+def _emit(thinned) -> Tensor:
+    """(sum(counts), 3) int32: the skeleton voxels that ``_thin`` left in its workspace, as crop coordinates"""
+    _, boxes_p, n, work, nbytes, counts = thinned
+    dev = work.device
     offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
     torch.cumsum(counts, 0, out=offsets[1:])
     total = int(offsets[-1].item())
     points = torch.empty((total, 3), dtype=torch.int32, device=dev)
     _ffi.check(_ffi.lib.sk_skeletonize_emit(boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes), _ffi.ptr(offsets), total,
-                                            _ffi.ptr(points), stream))
-    return points, counts.cpu().numpy().astype(np.int64), stats.cpu().numpy().astype(np.int64)
+                                            _ffi.ptr(points), _ffi.stream_ptr(dev)))
+    return points
+
+
+def thin_objects(labels: Tensor, ids, boxes) -> Tuple[Tensor, np.ndarray, np.ndarray]:
+    """Lee thinning of every object in its own crop, in one launch (one workgroup per object).
+
+    labels (X, Y, Z) int32 on the GPU; ids: n object ids; boxes (n, 6) ints (x0, y0, z0, x1, y1, z1): object i is
+    thinned in the binary crop ``labels[x0:x1, y0:y1, z0:z1] == ids[i]`` (voxels of other ids are background).
+    Returns (points, counts, stats): points (sum(counts), 3) int32 on the GPU, the skeleton voxels of object 0, 1, ...
+    in raster order of their crop as crop coordinates; counts (n,) int64; stats (n, 2) = passes and the most
+    re-check rounds of one sub-iteration (the kernel's counters)."""
+    done = _thin(labels, ids, boxes)
+    if done is None:
+        return (torch.zeros((0, 3), dtype=torch.int32, device=labels.device), np.zeros(0, np.int64),
+                np.zeros((0, 2), np.int64))
+    thinned, stats = done
+    points = _emit(thinned)
+    return points, thinned[5].cpu().numpy().astype(np.int64), stats.cpu().numpy().astype(np.int64)
+
+
+N_GRAPH = 12    # int64 values per object of sk_skeleton_graph (checked against the library below)
+
+
+def skeleton_graph(labels: Tensor, ids, boxes, want_points: bool = False):
+    """The skeletons of ``thin_objects(labels, ids, boxes)`` read as graphs, on the workspace the thinning leaves them
+    in: ``sk_skeletonize``, then ``sk_skeleton_graph``, then ``sk_skeletonize_emit`` when ``want_points``.
+
+    Returns (graph, counts, points): graph (n, 12) int64 on the GPU -- skeleton voxels, voxels of degree 0 / 1 / 2 /
+    >= 3, and the links (pairs of 26-neighbouring skeleton voxels, each once) by direction class (1,0,0) (0,1,0)
+    (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1); include/skoots_hip.h and DESIGN.md section 22 -- counts (n,) int64 as
+    ``thin_objects`` gives them, and points as ``thin_objects`` gives them or ``None``."""
+    assert _ffi.lib.sk_skeleton_graph_row_values() == N_GRAPH
+    done = _thin(labels, ids, boxes)
+    if done is None:
+        dev = labels.device
+        return (torch.zeros((0, N_GRAPH), dtype=torch.int64, device=dev), np.zeros(0, np.int64),
+                torch.zeros((0, 3), dtype=torch.int32, device=dev) if want_points else None)
+    thinned, _ = done
+    _, boxes_p, n, work, nbytes, counts = thinned
+    graph = torch.empty((n, N_GRAPH), dtype=torch.int64, device=work.device)
+    _ffi.check(_ffi.lib.sk_skeleton_graph(boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes), _ffi.ptr(graph),
+                                          _ffi.stream_ptr(work.device)))
+    points = _emit(thinned) if want_points else None
+    return graph, counts.cpu().numpy().astype(np.int64), points
 
 
 def skeletonize(image: Tensor) -> Tensor:

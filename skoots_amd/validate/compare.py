@@ -11,6 +11,10 @@ on every run.
 surface.  The reference's marching-cubes ``surface_area`` is available with ``surface="open"`` (its
 meaning) or ``"closed"``: a second kernel pass (``sk_instance_mesh_cells``) counts every instance's
 cells per triangle class, integers again, and ``class_areas`` turns the counts into an area on the host.
+
+``skeleton=True`` / ``--skeleton`` adds the centre line: every instance is Lee-thinned in its box and the skeleton is
+read as a graph (``sk_skeleton_graph``) -- voxels, endpoints, junction voxels and the links per direction
+class, integers once more -- and ``skeleton_columns`` turns the links into a length at the voxel spacing.
 """
 from __future__ import annotations
 
@@ -23,13 +27,16 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .lib import check_shape, id_rows, instance_mesh_cells, instance_sums
+from .lib import check_shape, id_rows, instance_mesh_cells, instance_skeleton_graph, instance_sums
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
                "axis_minor")
 SURFACE_COLUMNS = "surface_area,surface_to_volume"       # appended with --surface-area
 SURFACE_MODES = (None, "open", "closed")
+SKELETON_COLUMNS = "skeleton_voxels,skeleton_length,skeleton_endpoints,skeleton_junctions,skeleton_branches"  # --skeleton
+# (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
+LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
 # An eigenvalue of the covariance matrix below this share of the largest one is the round-off of an exactly flat
 # object (a line, a one-voxel-thick sheet) and is set to 0 together with negative round-off: 2 sqrt(5 lambda) would
@@ -124,7 +131,34 @@ def surface_columns(cells: Tensor, volume: Tensor, spacing=(1.0, 1.0, 1.0)) -> D
     return {"surface_area": area, "surface_to_volume": area / volume.cpu().to(torch.float64)}
 
 
-def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None) -> Dict[str, Tensor]:
+def skeleton_columns(graph: Tensor, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor]:
+    """The skeleton columns (host tensors) from the (N, 12) int64 rows of ``sk_skeleton_graph``:
+
+    ``skeleton_voxels``, ``skeleton_endpoints`` (degree 1) and ``skeleton_junctions`` (degree >= 3), int64: the
+    kernel's columns 0, 2 and 4.  ``skeleton_links``, int64: the sum of columns 5 .. 11, every pair of 26-neighbouring
+    skeleton voxels once.  ``skeleton_branches`` = ``skeleton_links`` - column 3, int64: contracting every chain voxel
+    (degree 2) takes one link with it, so this many edges remain between the other voxels; it is half the degree sum
+    of the non-chain voxels.  A rod has 1, a T has 3, and a closed ring made of chain voxels only has 0: it has no
+    voxel for a branch to end at.  ``skeleton_length``, float64: sum over the classes of links times
+    ``sqrt((a sx)^2 + (b sy)^2 + (c sz)^2)``, summed class by class in the table's order as ``mesh_area`` does, so
+    that the dict and the CSV file agree to the last bit; 0.0 for an empty skeleton.
+
+    Known bias: every link counts.  Where three skeleton voxels are pairwise 26-neighbours -- a corner that Lee
+    thinning leaves as a small triangle -- all three sides enter the length and the link count, and the corner voxels
+    reach degree 3, so a path through such a corner is measured a little long and the corner counts as junction
+    voxels."""
+    sx, sy, sz = _spacing(spacing)
+    g = graph.cpu().to(torch.int64)
+    links = g[:, 5:12].sum(dim=1)
+    length = torch.zeros(g.shape[0], dtype=torch.float64)
+    for k, (a, b, c) in enumerate(LINK_CLASSES):
+        length += g[:, 5 + k].to(torch.float64) * math.sqrt((a * sx) ** 2 + (b * sy) ** 2 + (c * sz) ** 2)
+    return {"skeleton_voxels": g[:, 0].clone(), "skeleton_length": length, "skeleton_endpoints": g[:, 2].clone(),
+            "skeleton_junctions": g[:, 4].clone(), "skeleton_links": links, "skeleton_branches": links - g[:, 3]}
+
+
+def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
+                       skeleton: bool = False) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -141,7 +175,12 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     instance touches a face of the volume its surface stays open.  "closed" measures the mask padded with one layer of
     background.  Deliberate difference: an instance that fills the whole volume in open mode, or any instance of a
     volume with an extent below 2, has area 0 here; scikit-image raises there ("No surface found", "must be at least
-    2x2x2"), which would fail the whole mask for one instance (DESIGN.md §21)."""
+    2x2x2"), which would fail the whole mask for one instance.
+
+    ``skeleton=True`` adds ``skeleton_graph`` (N, 12) int64, the rows of ``sk_skeleton_graph`` for every instance
+    thinned in its box (``lib.instance_skeleton_graph``), and the columns of ``skeleton_columns``: ``skeleton_voxels``,
+    ``skeleton_length``, ``skeleton_endpoints``, ``skeleton_junctions``, ``skeleton_links``, ``skeleton_branches``
+    (DESIGN.md §22)."""
     if surface not in SURFACE_MODES:
         raise ValueError(f"surface must be one of {SURFACE_MODES}, got {surface!r}")
     spacing = _spacing(anisotropy)
@@ -157,23 +196,33 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         _, cells = instance_mesh_cells(x, closed=surface == "closed", rows=rows)
         out["mesh_cells"] = cells
         out.update({k: v.to(sums.device) for k, v in surface_columns(cells, out["volume"], spacing).items()})
+    if skeleton:
+        _, graph = instance_skeleton_graph(x, rows, boxes)
+        out["skeleton_graph"] = graph
+        out.update({k: v.to(sums.device) for k, v in skeleton_columns(graph, spacing).items()})
     return out
 
 
 def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=(1.0, 1.0, 1.0),
-               min_voxels: int = 1, mesh_cells: Optional[Tensor] = None) -> str:
+               min_voxels: int = 1, mesh_cells: Optional[Tensor] = None,
+               skeleton_graph: Optional[Tensor] = None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
-    it was before they existed."""
+    it was before they existed.  With ``skeleton_graph`` (the (N, 12) rows of ``instance_skeleton_graph``) the columns
+    ``skeleton_voxels,skeleton_length,skeleton_endpoints,skeleton_junctions,skeleton_branches`` follow those; without,
+    again, nothing changes."""
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
         d.update(surface_columns(mesh_cells, d["volume"], spacing))
+    if skeleton_graph is not None:
+        d.update(skeleton_columns(skeleton_graph, spacing))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
-             CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") + "\n"]
+             CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
+             ("," + SKELETON_COLUMNS if skeleton_graph is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -182,6 +231,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                  *(repr(v) for v in d["axis_lengths"][i])]
         if mesh_cells is not None:
             cells += [repr(d["surface_area"][i]), repr(d["surface_to_volume"][i])]
+        if skeleton_graph is not None:
+            cells += [d["skeleton_voxels"][i], repr(d["skeleton_length"][i]), d["skeleton_endpoints"][i],
+                      d["skeleton_junctions"][i], d["skeleton_branches"][i]]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -189,7 +241,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser = argparse.ArgumentParser(prog="python -m skoots_amd.validate.compare",
                                      description="SKOOTS: volume, box, centroid, face area and axes of every instance, "
-                                                 "and the mesh surface area on request")
+                                                 "and the mesh surface area and the skeleton on request")
     parser.add_argument("mask", type=str, help="Path to an instance mask (.tif or .npy, stored [Z, X, Y])")
     parser.add_argument("--spacing", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("SX", "SY", "SZ"),
                         help="Voxel spacing along x, y and z")
@@ -197,10 +249,18 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--surface-area", type=str, default=None, choices=("open", "closed"),
                         help="Append surface_area,surface_to_volume: the marching-cubes mesh area of every instance, "
                              "left open where the volume's faces cut it (the reference's meaning) or closed there")
+    parser.add_argument("--skeleton", action="store_true",
+                        help="Append " + SKELETON_COLUMNS + ": every instance thinned to its centre line (Lee), the "
+                             "length of its links at the spacing, its endpoints, junction voxels and branches")
+    parser.add_argument("--save-skeletons", action="store_true",
+                        help="Also write <mask>_skeletons.tif, every skeleton voxel carrying its instance id, stored "
+                             "[Z, X, Y] like the mask (implies --skeleton)")
     parser.add_argument("--out", type=str, default=None, help="Output file (default: <mask>_instance_stats.csv)")
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    args.skeleton = args.skeleton or args.save_skeletons
+    return args
 
 
 def main(argv: Optional[Sequence[str]] = None) -> str:
@@ -219,11 +279,24 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
     rows = id_rows(dev_mask)                                # once, for both kernels
     ids, sums, boxes = instance_sums(dev_mask, rows)
     cells = instance_mesh_cells(dev_mask, args.surface_area == "closed", rows)[1] if args.surface_area else None
-    text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells)
+    graph = None
+    if args.skeleton:
+        if args.save_skeletons and ids.numel() and int(ids.max().item()) > 2 ** 31 - 1:
+            raise ValueError(f"--save-skeletons writes int32 labels and {args.mask} has the id {int(ids.max().item())}, "
+                             "which does not fit; renumber the mask, or use --skeleton alone")
+        graph, *volume = instance_skeleton_graph(dev_mask, rows, boxes, want_volume=args.save_skeletons)[1:]
+    text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
     print(f"File Written: {out_path}")
+    if args.save_skeletons:
+        from ..lib import tiff
+        # rows 1 .. N -> ids, 0 stays 0; (X, Y, Z) -> the mask's [Z, X, Y]
+        table = torch.cat((ids.new_zeros(1), ids)).to(torch.int32)
+        skel_path = f"{os.path.splitext(args.mask)[0]}_skeletons.tif"
+        tiff.write_label_stack(skel_path, table[volume[0].long()].permute(2, 0, 1).contiguous())
+        print(f"File Written: {skel_path}")
     return out_path
 
 

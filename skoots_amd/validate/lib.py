@@ -9,11 +9,13 @@ pair; here one kernel pass builds the (gt, pred) contingency tables and a second
 ``instance_sums`` measures every instance of one mask in a single kernel pass; ``mask_to_bbox`` is the
 reference's function of that name on top of it, and ``validate/compare.py`` derives the per-instance statistics.
 ``instance_mesh_cells`` counts every instance's marching-cubes cells per class in one more pass.
+``instance_skeleton_graph`` thins every instance in its box and reads the skeletons as graphs.
 """
 from __future__ import annotations
 
 from typing import Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -257,6 +259,85 @@ def instance_mesh_cells(x: Tensor, closed: bool = False, rows=None) -> Tuple[Ten
     _ffi.check(_ffi.lib.sk_instance_mesh_cells(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(class_of),
                                                n_classes, int(bool(closed)), _ffi.ptr(cells), _ffi.stream_ptr(dev)))
     return ids, cells
+
+
+SKELETON_BUDGET = 1 << 30   # bytes of thinning workspace per batch of instance_skeleton_graph
+N_GRAPH = 12                # int64 values per instance of sk_skeleton_graph (lib/morphology.py checks the library's)
+
+
+def _skeleton_batches(boxes: np.ndarray, budget_bytes: int):
+    """[(first, last + 1)] over the rows of ``boxes`` (N, 6) int32, in row order: each batch is the longest run whose
+    ``sk_skeletonize_workspace_bytes`` stays within ``budget_bytes``, and an instance that alone exceeds the budget is
+    its own batch.  The bytes grow with the run, so the end of a run is found by bisection."""
+    def nbytes(a, b):
+        return int(_ffi.lib.sk_skeletonize_workspace_bytes(boxes[a:b].ctypes.data_as(_ffi.ip), b - a))
+
+    out, a, n = [], 0, boxes.shape[0]
+    while a < n:
+        lo, hi = a + 1, n                                    # the run [a, lo) is taken in any case
+        if nbytes(a, hi) > budget_bytes:
+            while lo < hi:                                   # the largest b in [lo, hi] with nbytes(a, b) <= budget
+                mid = (lo + hi + 1) // 2
+                if nbytes(a, mid) <= budget_bytes:
+                    lo = mid
+                else:
+                    hi = mid - 1
+            hi = lo
+        out.append((a, hi))
+        a = hi
+    return out
+
+
+def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int = SKELETON_BUDGET,
+                            want_volume: bool = False):
+    """(ids (N) int64 ascending, graph (N, 12) int64[, skeleton (X, Y, Z) int32]) of the positive ids of an (X, Y, Z)
+    integer device tensor: every instance is Lee-thinned in its full box ``[x0, x1 + 1) x ...`` with other ids as
+    background -- ``skimage.morphology.skeletonize_3d(x == id)`` of scikit-image 0.18.3 on the whole volume -- and
+    ``sk_skeleton_graph`` reads the skeleton as a graph: its voxels, the voxels of degree 0 / 1 / 2 / >= 3 and the
+    links per direction class (include/skoots_hip.h names the columns).  ``ids`` and the rows are those
+    of ``instance_sums``; ``rows`` is ``id_rows(x)`` and ``boxes`` the (N, 6) inclusive boxes of ``instance_sums`` when
+    the caller already has them.
+
+    The instances are thinned in batches, in row order, of at most ``budget_bytes`` of thinning workspace (an instance
+    that alone needs more is a batch of its own); the result does not depend on the budget.  A box whose crop the
+    library refuses (2^30 voxels or more, or 2^31 / 6 words of padded bit plane) raises ``ValueError`` with the
+    instance's id before anything is launched.  ``want_volume`` adds a volume that is 0 outside the skeletons and the
+    instance's row (1 .. N) on its skeleton voxels."""
+    from ..lib.morphology import skeleton_graph
+    x, rows = id_rows(x) if rows is None else rows
+    check_shape(x.shape)
+    dev = x.device
+    volume = torch.zeros(tuple(x.shape), dtype=torch.int32, device=dev) if want_volume else None
+    if rows is None:
+        out = (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_GRAPH), dtype=torch.int64, device=dev))
+        return out + (volume,) if want_volume else out
+    a, ids, lut, _ = rows
+    N = int(ids.numel())
+    if boxes is None:
+        boxes = instance_sums(x, (x, rows))[2]
+    b = boxes.cpu().numpy().astype(np.int64).reshape(N, N_BOX)
+    b[:, 3:] += 1                                            # inclusive -> [x0, x1 + 1)
+    ext = b[:, 3:] - b[:, :3]
+    words = (ext[:, 0] + 2) * (ext[:, 1] + 2) * ((ext[:, 2] + 2 + 31) >> 5)
+    refused = np.flatnonzero((ext.prod(1) >= 2 ** 30) | (words * 6 >= 2 ** 31))     # the guard of sk_skeletonize
+    if refused.size:
+        i = int(refused[0])
+        raise ValueError(f"instance {int(ids[i].item())} has a box of {tuple(int(v) for v in ext[i])} voxels, too large "
+                         "to thin: a crop must stay below 2^30 voxels (and 2^31 / 6 words of padded bit plane)")
+    b = np.ascontiguousarray(b.astype(np.int32))
+    # the value that `a` holds for row k: the id itself, or the row where _id_rows relabelled the mask
+    values = torch.nonzero(lut)[:, 0].to(torch.int32).cpu().numpy()
+    assert values.shape[0] == N
+    graph = torch.empty((N, N_GRAPH), dtype=torch.int64, device=dev)
+    for first, last in _skeleton_batches(b, int(budget_bytes)):
+        g, counts, points = skeleton_graph(a, values[first:last], b[first:last], want_points=want_volume)
+        graph[first:last] = g
+        if want_volume and points.shape[0]:
+            row = torch.repeat_interleave(torch.arange(first, last, device=dev),
+                                          torch.from_numpy(counts).to(dev))
+            p = points.long() + torch.from_numpy(b[first:last, :3]).to(dev).long()[row - first]
+            volume[p[:, 0], p[:, 1], p[:, 2]] = (row + 1).to(torch.int32)
+    return (ids, graph, volume) if want_volume else (ids, graph)
 
 
 def mask_to_bbox(mask: Tensor) -> Tuple[Tensor, Tensor]:

@@ -8,6 +8,9 @@
 ``mesh_surface_area``, stats.py:30-48) without a mesh: one kernel pass counts the mask's cells per triangle class
 (DESIGN.md §21).  ``get_face_area`` is the area of the exposed voxel faces, exact for what it defines and an
 overestimate of a curved surface.
+
+``get_skeleton_length`` is the length of the mask's Lee skeleton read as a graph, on the path of
+``compare.stats_per_instance(skeleton=True)``.
 """
 from __future__ import annotations
 
@@ -16,8 +19,8 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor
 
-from .compare import _spacing, mesh_area
-from .lib import instance_mesh_cells, instance_sums
+from .compare import _spacing, mesh_area, skeleton_columns
+from .lib import instance_mesh_cells, instance_skeleton_graph, instance_sums
 
 
 def _one_row(x: Tensor) -> Tensor:
@@ -59,3 +62,15 @@ def get_surface_area(x: Tensor, anisotropy_ratio: Union[List[float], Tensor], cl
     _, cells = instance_mesh_cells((x > 0).to(torch.int32), closed=closed)
     area = mesh_area(cells, anisotropy_ratio)            # checks the spacing, also for a mask without foreground
     return (area[0] if area.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
+
+
+def get_skeleton_length(x: Tensor, spacing: Union[List[float], Tensor]) -> Tensor:
+    """The length of the skeleton of ``x > 0`` (one binary object; scikit-image 0.18.3's Lee thinning of the whole
+    volume) at the voxel spacing ``spacing`` (float64, on x's device): every pair of 26-neighbouring skeleton voxels
+    contributes the distance of their centres -- ``compare.skeleton_columns`` states the bias this has at corners.  A
+    mask without foreground, or one that thins to a single voxel, gives 0."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    _, graph = instance_skeleton_graph((x > 0).to(torch.int32))
+    length = skeleton_columns(graph, spacing)["skeleton_length"]      # checks the spacing, also for an empty mask
+    return (length[0] if length.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
