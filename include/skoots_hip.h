@@ -909,6 +909,34 @@ int sk_instance_stats(const int32_t* labels, int X, int Y, int Z, const int32_t*
 int sk_instance_mesh_cells(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
                            const uint8_t* class_of, int n_classes, int closed, int64_t* cells, void* stream);
 
+/* Exact squared Euclidean distance transform of every instance at once (ABI 17).  labels, lut,
+ * max_id and N are those of sk_instance_stats; r(v) is the row of voxel v (1 .. N, 0 for background).  wx, wy, wz are
+ * the squares of the voxel spacing, fl(sx sx) and so on, formed in double by the caller.  For a voxel p with r(p) > 0
+ *   dist2[p] = min over voxels q with r(q) != r(p) of  fl(wx dx^2 + fl(wy dy^2 + wz dz^2)),   dx = px - qx, ...
+ * where every square is an exact integer converted to double and every product and sum is rounded once (no fused
+ * multiply-add; w (d d), never (w d) d); dist2[p] = 0 where r(p) = 0.  Another instance is "not this instance" exactly
+ * like background: a face shared by two instances bounds both.  closed = 0 counts the voxels of the volume only
+ * (scipy.ndimage.distance_transform_edt's meaning), and a voxel whose row is the only value of the whole volume gets
+ * +inf; closed = 1 measures the volume padded with one layer of background on all six sides.  The minimum is nested
+ * and rounding is monotone, so the three passes of the implementation (z, y, x; each a pruned walk along its axis)
+ * give exactly this value at any spacing; at integer-valued spacings sqrt(dist2) equals scipy's result bit for bit.
+ * dist2 and scratch: X Y Z doubles each, distinct; the passes go dist2 -> scratch -> dist2.  row_max (N, may be NULL):
+ * row_max[r - 1] is the bit pattern of the largest dist2 of row r (non-negative doubles order like unsigned integers,
+ * +inf last, so a 64-bit integer atomic max is exact and independent of the order of arrival), 0 for a row without
+ * voxels; the entry point zeroes it itself (stream-ordered).  Nothing accumulates in floating point: the outputs are
+ * the same on every run.  Checked before anything is launched or written: extents, N and max_id not negative, every
+ * extent <= 2^26 (d^2 exact in double), X Y Z < 2^62, closed 0 or 1, the weights finite and > 0, no NULL pointer but
+ * row_max, pointers aligned to their elements, dist2 != scratch.  An empty volume or N == 0 returns SK_OK and writes
+ * nothing.
+ * sk_label_edt_pass is one of the three passes, under the same checks: axis 2 (z; src is not read and may be NULL)
+ * writes dst = the minimum of w dz^2 along z, axis 1 and 0 write dst = min over the axis of fl(w d^2 + src(q)); row_max
+ * (may be NULL) is zeroed and filled from dst.  sk_label_edt is the passes 2, 1, 0 with wz, wy, wx;
+ * tools/bench_edt.py times them one by one. */
+int sk_label_edt_pass(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, int axis,
+                      double w, int closed, const double* src, double* dst, uint64_t* row_max, void* stream);
+int sk_label_edt(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, double wx, double wy,
+                 double wz, int closed, double* dist2, double* scratch, uint64_t* row_max, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * flood_and_stitch (skoots/utils/flood_and_stitch.py)
  * ------------------------------------------------------------------------ */

@@ -1,7 +1,8 @@
 """``skoots.lib.morphology`` dilations on the MI355X
 (reference: skoots/lib/morphology.py:155-175 ``binary_dilation``, :178-199 ``binary_dilation_2d``), and the Lee
 thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skeletonize``, ``thin_objects``) with the
-skeletons read as graphs (``skeleton_graph``)."""
+skeletons read as graphs (``skeleton_graph``); ``label_edt`` is the exact Euclidean distance
+transform of every instance of a label volume, which the reference does not have."""
 from __future__ import annotations
 
 import ctypes as C
@@ -131,6 +132,43 @@ def skeleton_graph(labels: Tensor, ids, boxes, want_points: bool = False):
                                           _ffi.stream_ptr(work.device)))
     points = _emit(thinned) if want_points else None
     return graph, counts.cpu().numpy().astype(np.int64), points
+
+
+def label_edt(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, rows=None) -> Tuple[Tensor, Tensor]:
+    """Exact squared Euclidean distance transform of every instance of an (X, Y, Z) or (1, X, Y, Z) integer device
+    tensor at the voxel spacing ``spacing`` (sx, sy, sz): ``(dist2, row_max)``, both float64 on the device.
+
+    ``dist2`` (X, Y, Z): for a voxel of a positive id, the squared distance between voxel centres to the nearest voxel
+    that is not of that id -- background or another instance alike -- and 0 on the other voxels; ``row_max`` (N): the
+    largest ``dist2`` of every positive id in ascending order, the rows of ``validate.lib.instance_sums``.  The value
+    is ``fl(wx dx^2 + fl(wy dy^2 + wz dz^2))`` with ``wx = sx * sx`` formed in float64 here, minimised exactly
+    (include/skoots_hip.h: sk_label_edt), the same on every run; at integer-valued spacings ``dist2.sqrt()`` equals
+    ``scipy.ndimage.distance_transform_edt(labels == id, sampling=spacing)`` bit for bit on the voxels of every id.
+
+    ``closed=False`` is scipy's meaning: only voxels of the volume count, and an id that is the only value of the whole
+    volume gets ``inf``.  ``closed=True`` measures the volume padded with one layer of background.  ``rows`` is
+    ``validate.lib.id_rows(labels)`` when the caller already has it."""
+    from ..validate.lib import id_rows
+    x, rows = id_rows(labels) if rows is None else rows
+    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
+    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
+        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
+    X, Y, Z = (int(v) for v in x.shape)
+    if max(X, Y, Z) > 2 ** 26 or X * Y * Z >= 2 ** 62:
+        raise ValueError(f"a volume of shape {(X, Y, Z)} is too large for the distance transform: every extent must stay "
+                         "at or below 2^26 and X*Y*Z below 2^62")
+    dev = x.device
+    dist2 = torch.zeros((X, Y, Z), dtype=torch.float64, device=dev)
+    if rows is None or dist2.numel() == 0:
+        return dist2, torch.zeros(0, dtype=torch.float64, device=dev)
+    a, ids, lut, max_id = rows
+    N = int(ids.numel())
+    scratch = torch.empty_like(dist2)
+    row_max = torch.zeros(N, dtype=torch.int64, device=dev)
+    _ffi.check(_ffi.lib.sk_label_edt(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, s[0] * s[0], s[1] * s[1], s[2] * s[2],
+                                     int(bool(closed)), _ffi.ptr(dist2), _ffi.ptr(scratch), _ffi.ptr(row_max),
+                                     _ffi.stream_ptr(dev)))
+    return dist2, row_max.view(torch.float64)
 
 
 def skeletonize(image: Tensor) -> Tensor:

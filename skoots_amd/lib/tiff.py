@@ -315,6 +315,19 @@ def write_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timing
     _write_pages(path, rows, int(pages.shape[1]), int(pages.shape[2]), bits, fmt, budget_bytes, timings, samples=spp)
 
 
+def write_float_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timings=None) -> None:
+    """(Z, H, W) float32 tensor (either device) or array -> multi-page TIFF of 32-bit IEEE samples (SampleFormat 3),
+    laid out like ``write_stack``'s pages: one Adobe-deflate strip and one directory per page.  ``write_stack`` and the
+    readers of this module keep to integer samples; ImageJ / Fiji and tifffile open these pages as 32-bit float."""
+    import torch
+    is_np = isinstance(pages, np.ndarray)
+    if pages.ndim != 3 or pages.dtype != (np.float32 if is_np else torch.float32):
+        raise ValueError(f"write_float_stack takes (Z, H, W) float32, got {tuple(pages.shape)} {pages.dtype}")
+    t = torch.from_numpy(np.ascontiguousarray(pages)) if is_np else pages.contiguous()
+    rows = t.view(torch.uint8).reshape(t.shape[0], -1) if t.numel() else torch.zeros((t.shape[0], 0), dtype=torch.uint8)
+    _write_pages(path, rows, int(t.shape[1]), int(t.shape[2]), 32, 3, budget_bytes, timings)
+
+
 def write_label_stack(path: str, labels_zxy, timings=None) -> None:
     """(Z, X, Y) int32 label tensor -> TIFF, uint16 pages while every label is below 65536, int32 otherwise (the
     narrowing ``eval._write_mask_tif`` applies on the host), without leaving the tensor's device."""

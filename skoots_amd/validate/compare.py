@@ -15,6 +15,10 @@ cells per triangle class, integers again, and ``class_areas`` turns the counts i
 ``skeleton=True`` / ``--skeleton`` adds the centre line: every instance is Lee-thinned in its box and the skeleton is
 read as a graph (``sk_skeleton_graph``) -- voxels, endpoints, junction voxels and the links per direction
 class, integers once more -- and ``skeleton_columns`` turns the links into a length at the voxel spacing.
+
+``thickness="open"`` / ``"closed"`` / ``--thickness`` adds the width: the exact Euclidean distance transform of every
+instance (``sk_label_edt``) and ``inscribed_radius``, the square root of its maximum; together with the
+skeleton, the mean, minimum and maximum radius along the centre line.
 """
 from __future__ import annotations
 
@@ -24,10 +28,12 @@ import math
 import os
 from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
-from .lib import check_shape, id_rows, instance_mesh_cells, instance_skeleton_graph, instance_sums
+from .lib import (check_shape, id_rows, instance_mesh_cells, instance_skeleton_graph, instance_sums,
+                  instance_thickness)
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
@@ -35,6 +41,9 @@ CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_
 SURFACE_COLUMNS = "surface_area,surface_to_volume"       # appended with --surface-area
 SURFACE_MODES = (None, "open", "closed")
 SKELETON_COLUMNS = "skeleton_voxels,skeleton_length,skeleton_endpoints,skeleton_junctions,skeleton_branches"  # --skeleton
+THICKNESS_COLUMNS = "inscribed_radius"                   # appended with --thickness
+SKELETON_RADIUS_COLUMNS = "skeleton_radius_mean,skeleton_radius_min,skeleton_radius_max"  # --thickness with --skeleton
+THICKNESS_MODES = (None, "open", "closed")
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -157,8 +166,30 @@ def skeleton_columns(graph: Tensor, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor
             "skeleton_junctions": g[:, 4].clone(), "skeleton_links": links, "skeleton_branches": links - g[:, 3]}
 
 
+def thickness_columns(max_d2: Tensor, skel_stats: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """The width columns (float64 host tensors) from the (N) largest squared distances of ``instance_thickness`` and,
+    when given, its (N, 3) skeleton statistics:
+
+    ``inscribed_radius`` = ``sqrt(max_d2)``: the largest distance from a voxel centre of the instance to the nearest
+    voxel centre outside it.  Distances run between voxel centres (scipy's convention) and no half-voxel correction is
+    applied: a sheet one voxel thick has a radius of one spacing, a tube k voxels across about (k + 1) / 2 spacings.
+    It is a radius; doubling it is the reader's choice.  Deliberate: an instance that is alone in the volume in open
+    mode has no outside voxel and reports ``inf``.
+
+    ``skeleton_radius_mean``, ``skeleton_radius_min``, ``skeleton_radius_max``: ``sqrt(D2)`` over the instance's
+    skeleton voxels; 0.0 for an empty skeleton."""
+    # numpy's square root is the correctly rounded one at every length of the array (the host library's vectorised
+    # one is not: sqrt(2.0) comes out one unit low), so a row's radius does not depend on the rows computed with it
+    out = {"inscribed_radius": torch.from_numpy(np.sqrt(max_d2.cpu().to(torch.float64).numpy()))}
+    if skel_stats is not None:
+        st = skel_stats.cpu().to(torch.float64).reshape(-1, 3)
+        for k, name in enumerate(SKELETON_RADIUS_COLUMNS.split(",")):
+            out[name] = st[:, k].clone()
+    return out
+
+
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
-                       skeleton: bool = False) -> Dict[str, Tensor]:
+                       skeleton: bool = False, thickness: Optional[str] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -180,9 +211,17 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     ``skeleton=True`` adds ``skeleton_graph`` (N, 12) int64, the rows of ``sk_skeleton_graph`` for every instance
     thinned in its box (``lib.instance_skeleton_graph``), and the columns of ``skeleton_columns``: ``skeleton_voxels``,
     ``skeleton_length``, ``skeleton_endpoints``, ``skeleton_junctions``, ``skeleton_links``, ``skeleton_branches``
-    (DESIGN.md §22)."""
+    (DESIGN.md §22).
+
+    ``thickness="open"`` or ``"closed"`` adds ``dist2`` (X, Y, Z) float64, the exact squared Euclidean distance of every
+    instance voxel to the nearest voxel outside its instance (``lib.instance_thickness``; "open" counts the voxels of
+    the volume only, "closed" pads it with background), ``max_dist2`` (N) float64 and ``inscribed_radius`` =
+    ``sqrt(max_dist2)``; together with ``skeleton=True`` also ``skeleton_radius_mean`` / ``_min`` / ``_max``, the radius
+    sampled on the skeleton voxels (``thickness_columns``)."""
     if surface not in SURFACE_MODES:
         raise ValueError(f"surface must be one of {SURFACE_MODES}, got {surface!r}")
+    if thickness not in THICKNESS_MODES:
+        raise ValueError(f"thickness must be one of {THICKNESS_MODES}, got {thickness!r}")
     spacing = _spacing(anisotropy)
     rows = id_rows(x)                                       # once, for both kernels
     ids, sums, boxes = instance_sums(x, rows)
@@ -196,33 +235,49 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         _, cells = instance_mesh_cells(x, closed=surface == "closed", rows=rows)
         out["mesh_cells"] = cells
         out.update({k: v.to(sums.device) for k, v in surface_columns(cells, out["volume"], spacing).items()})
+    volume = None
     if skeleton:
-        _, graph = instance_skeleton_graph(x, rows, boxes)
+        _, graph, *volume = instance_skeleton_graph(x, rows, boxes, want_volume=thickness is not None)
         out["skeleton_graph"] = graph
         out.update({k: v.to(sums.device) for k, v in skeleton_columns(graph, spacing).items()})
+    if thickness is not None:
+        _, max_d2, dist2, *skel = instance_thickness(x, spacing, thickness == "closed", rows,
+                                                     volume[0] if volume else None)
+        out["max_dist2"], out["dist2"] = max_d2, dist2
+        out.update({k: v.to(sums.device) for k, v in thickness_columns(max_d2, *skel).items()})
     return out
 
 
 def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=(1.0, 1.0, 1.0),
                min_voxels: int = 1, mesh_cells: Optional[Tensor] = None,
-               skeleton_graph: Optional[Tensor] = None) -> str:
+               skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
+               skeleton_radius: Optional[Tensor] = None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
     it was before they existed.  With ``skeleton_graph`` (the (N, 12) rows of ``instance_skeleton_graph``) the columns
     ``skeleton_voxels,skeleton_length,skeleton_endpoints,skeleton_junctions,skeleton_branches`` follow those; without,
-    again, nothing changes."""
+    again, nothing changes.  With ``max_dist2`` (the (N) maxima of ``instance_thickness``) ``inscribed_radius`` follows,
+    and with ``skeleton_radius`` (its (N, 3) skeleton statistics) ``skeleton_radius_mean,skeleton_radius_min,
+    skeleton_radius_max``, in that order behind everything else; an instance alone in the volume in open mode prints
+    ``inf``."""
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
         d.update(surface_columns(mesh_cells, d["volume"], spacing))
     if skeleton_graph is not None:
         d.update(skeleton_columns(skeleton_graph, spacing))
+    if skeleton_radius is not None and max_dist2 is None:
+        raise ValueError("skeleton_radius comes with max_dist2: both are results of instance_thickness")
+    if max_dist2 is not None:
+        d.update(thickness_columns(max_dist2, skeleton_radius))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
-             ("," + SKELETON_COLUMNS if skeleton_graph is not None else "") + "\n"]
+             ("," + SKELETON_COLUMNS if skeleton_graph is not None else "") +
+             ("," + THICKNESS_COLUMNS if max_dist2 is not None else "") +
+             ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -234,6 +289,10 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         if skeleton_graph is not None:
             cells += [d["skeleton_voxels"][i], repr(d["skeleton_length"][i]), d["skeleton_endpoints"][i],
                       d["skeleton_junctions"][i], d["skeleton_branches"][i]]
+        if max_dist2 is not None:
+            cells += [repr(d["inscribed_radius"][i])]
+        if skeleton_radius is not None:
+            cells += [repr(d[k][i]) for k in SKELETON_RADIUS_COLUMNS.split(",")]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -241,7 +300,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser = argparse.ArgumentParser(prog="python -m skoots_amd.validate.compare",
                                      description="SKOOTS: volume, box, centroid, face area and axes of every instance, "
-                                                 "and the mesh surface area and the skeleton on request")
+                                                 "and the mesh surface area, the skeleton and the width on request")
     parser.add_argument("mask", type=str, help="Path to an instance mask (.tif or .npy, stored [Z, X, Y])")
     parser.add_argument("--spacing", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("SX", "SY", "SZ"),
                         help="Voxel spacing along x, y and z")
@@ -255,11 +314,23 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--save-skeletons", action="store_true",
                         help="Also write <mask>_skeletons.tif, every skeleton voxel carrying its instance id, stored "
                              "[Z, X, Y] like the mask (implies --skeleton)")
+    parser.add_argument("--thickness", type=str, default=None, choices=("open", "closed"),
+                        help="Append " + THICKNESS_COLUMNS + ": the largest distance from a voxel of the instance to the "
+                             "nearest voxel outside it, from an exact Euclidean distance transform at the spacing, "
+                             "counting the voxels of the volume only (open: an instance alone in the volume has inf) or "
+                             "the volume padded with background (closed); with --skeleton also " +
+                             SKELETON_RADIUS_COLUMNS + ", the radius along the centre line")
+    parser.add_argument("--save-distance", action="store_true",
+                        help="Also write <mask>_distance.tif, float32, every instance voxel its distance to the nearest "
+                             "voxel outside its instance and background 0, stored [Z, X, Y] like the mask (implies "
+                             "--thickness open when no mode is given)")
     parser.add_argument("--out", type=str, default=None, help="Output file (default: <mask>_instance_stats.csv)")
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
     args = parser.parse_args(argv)
     args.skeleton = args.skeleton or args.save_skeletons
+    if args.save_distance and args.thickness is None:
+        args.thickness = "open"
     return args
 
 
@@ -284,8 +355,15 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         if args.save_skeletons and ids.numel() and int(ids.max().item()) > 2 ** 31 - 1:
             raise ValueError(f"--save-skeletons writes int32 labels and {args.mask} has the id {int(ids.max().item())}, "
                              "which does not fit; renumber the mask, or use --skeleton alone")
-        graph, *volume = instance_skeleton_graph(dev_mask, rows, boxes, want_volume=args.save_skeletons)[1:]
-    text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph)
+        graph, *volume = instance_skeleton_graph(dev_mask, rows, boxes,
+                                                 want_volume=args.save_skeletons or bool(args.thickness))[1:]
+    max_d2 = dist2 = skel_radius = None
+    if args.thickness:
+        max_d2, dist2, *skel = instance_thickness(dev_mask, spacing, args.thickness == "closed", rows,
+                                                  volume[0] if args.skeleton else None)[1:]
+        skel_radius = skel[0] if skel else None
+    text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
+                      max_d2, skel_radius)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
@@ -297,6 +375,12 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         skel_path = f"{os.path.splitext(args.mask)[0]}_skeletons.tif"
         tiff.write_label_stack(skel_path, table[volume[0].long()].permute(2, 0, 1).contiguous())
         print(f"File Written: {skel_path}")
+    if args.save_distance:
+        from ..lib import tiff
+        dist_path = f"{os.path.splitext(args.mask)[0]}_distance.tif"
+        # (X, Y, Z) -> the mask's [Z, X, Y]; inf (an instance alone in the volume, open mode) stays inf in float32
+        tiff.write_float_stack(dist_path, torch.sqrt(dist2).to(torch.float32).permute(2, 0, 1).contiguous())
+        print(f"File Written: {dist_path}")
     return out_path
 
 

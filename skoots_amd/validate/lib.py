@@ -10,6 +10,7 @@ pair; here one kernel pass builds the (gt, pred) contingency tables and a second
 reference's function of that name on top of it, and ``validate/compare.py`` derives the per-instance statistics.
 ``instance_mesh_cells`` counts every instance's marching-cubes cells per class in one more pass.
 ``instance_skeleton_graph`` thins every instance in its box and reads the skeletons as graphs.
+``instance_thickness`` is the exact distance transform of every instance and its maximum per instance.
 """
 from __future__ import annotations
 
@@ -338,6 +339,48 @@ def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int 
             p = points.long() + torch.from_numpy(b[first:last, :3]).to(dev).long()[row - first]
             volume[p[:, 0], p[:, 1], p[:, 2]] = (row + 1).to(torch.int32)
     return (ids, graph, volume) if want_volume else (ids, graph)
+
+
+def instance_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, rows=None, skeleton=None):
+    """(ids (N) int64 ascending, max_d2 (N) float64, dist2 (X, Y, Z) float64[, skeleton_stats (N, 3) float64 on the
+    host]) of the positive ids of an (X, Y, Z) integer device tensor: ``lib.morphology.label_edt`` -- the exact squared
+    distance of every instance voxel to the nearest voxel that is not of its instance, at the voxel spacing -- and its
+    largest value per instance, the squared radius of the largest sphere around a voxel centre that holds voxel centres
+    of the instance only.  ``closed`` and ``rows`` are those of ``label_edt``; in open mode an instance
+    that is alone in the volume has ``inf``.
+
+    ``skeleton`` is the (X, Y, Z) int32 row volume of ``instance_skeleton_graph(..., want_volume=True)``; with it the
+    mean, minimum and maximum of ``sqrt(dist2)`` over every instance's skeleton voxels follow as a host tensor.  The
+    values are gathered on the device in raster order (``nonzero``), copied, and reduced per row in row-then-raster
+    order with numpy, so the mean is the same on every run (a plain left-to-right sum over the count, kept inside
+    [minimum, maximum]); a row without skeleton voxels has 0.0 in all three columns (no real radius is 0)."""
+    from ..lib.morphology import label_edt
+    x, rows = id_rows(x) if rows is None else rows
+    dev = x.device
+    if skeleton is not None and (tuple(skeleton.shape) != tuple(x.shape) or skeleton.device != dev):
+        raise ValueError(f"skeleton must be the {tuple(x.shape)} row volume of instance_skeleton_graph on {dev}, got "
+                         f"shape {tuple(skeleton.shape)} on {skeleton.device}")
+    dist2, max_d2 = label_edt(x, spacing, closed, (x, rows))
+    ids = rows[1] if rows is not None else torch.empty(0, dtype=torch.int64, device=dev)
+    if skeleton is None:
+        return ids, max_d2, dist2
+    N = int(ids.numel())
+    at = torch.nonzero(skeleton.reshape(-1))[:, 0]           # raster order
+    row = skeleton.reshape(-1)[at].cpu().numpy().astype(np.int64)
+    radius = np.sqrt(dist2.reshape(-1)[at].cpu().numpy())
+    order = np.argsort(row, kind="stable")                   # row, then raster
+    row, radius = row[order], radius[order]
+    stats = np.zeros((N, 3), np.float64)
+    first = np.searchsorted(row, np.arange(1, N + 2))
+    for r in range(N):
+        v = radius[first[r]:first[r + 1]]
+        if v.size:
+            total = 0.0
+            for t in v.tolist():                             # a plain left-to-right sum: one order, whatever numpy does
+                total += t
+            # rounding can put the mean of equal values a unit outside them: keep it inside [min, max]
+            stats[r] = (min(max(total / v.size, v.min()), v.max()), v.min(), v.max())
+    return ids, max_d2, dist2, torch.from_numpy(stats)
 
 
 def mask_to_bbox(mask: Tensor) -> Tuple[Tensor, Tensor]:

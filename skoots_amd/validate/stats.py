@@ -11,6 +11,9 @@ overestimate of a curved surface.
 
 ``get_skeleton_length`` is the length of the mask's Lee skeleton read as a graph, on the path of
 ``compare.stats_per_instance(skeleton=True)``.
+
+``get_inscribed_radius`` is the largest value of the mask's exact Euclidean distance transform, on the
+path of ``compare.stats_per_instance(thickness=...)``.
 """
 from __future__ import annotations
 
@@ -19,8 +22,8 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor
 
-from .compare import _spacing, mesh_area, skeleton_columns
-from .lib import instance_mesh_cells, instance_skeleton_graph, instance_sums
+from .compare import _spacing, mesh_area, skeleton_columns, thickness_columns
+from .lib import instance_mesh_cells, instance_skeleton_graph, instance_sums, instance_thickness
 
 
 def _one_row(x: Tensor) -> Tensor:
@@ -74,3 +77,17 @@ def get_skeleton_length(x: Tensor, spacing: Union[List[float], Tensor]) -> Tenso
     _, graph = instance_skeleton_graph((x > 0).to(torch.int32))
     length = skeleton_columns(graph, spacing)["skeleton_length"]      # checks the spacing, also for an empty mask
     return (length[0] if length.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
+
+
+def get_inscribed_radius(x: Tensor, spacing: Union[List[float], Tensor], closed: bool = False) -> Tensor:
+    """The radius of the largest sphere around a voxel centre of ``x > 0`` (one binary object) that holds no centre of a
+    voxel outside it, at the voxel spacing ``spacing`` (float64, on x's device): the maximum of
+    ``scipy.ndimage.distance_transform_edt(x > 0, sampling=spacing)``, computed exactly.  Distances run between voxel
+    centres, without a half-voxel correction (``compare.thickness_columns``).  ``closed=False`` counts the voxels of the
+    volume only, so a mask that fills it gives ``inf``; ``closed=True`` pads the volume with background.  A mask without
+    foreground gives 0."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    _, max_d2, _ = instance_thickness((x > 0).to(torch.int32), _spacing(spacing), closed)
+    radius = thickness_columns(max_d2)["inscribed_radius"]
+    return (radius[0] if radius.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
