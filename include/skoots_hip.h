@@ -389,7 +389,9 @@ int sk_heads_split(const void* x, const float* affine, const float* weight, cons
 /* fp32 precision mode (parity reference of the fast path): the same layers with fp32 activations
  * (B, x, y, z, C) and torch-layout fp32 weights (cout, cin, k, k, k) on the exact-fp32 matrix
  * instruction.  Same source / upsample / concat semantics and GroupNorm partial layout as
- * sk_conv3d (sources must be activated: affine == NULL); any cout when gn_partial is NULL. */
+ * sk_conv3d (sources must be activated: affine == NULL); any cout when gn_partial is NULL.
+ * B and every output extent must be >= 1 (SK_ERR_ARG otherwise, as for every other bad argument:
+ * nothing is launched). */
 int sk_conv3d_f32(const sk_conv_src* srcs, int n_src, const float* weight, const float* bias,
                   float* out, int B, int ox, int oy, int oz, int cout, int ksize,
                   float* gn_partial, void* stream);

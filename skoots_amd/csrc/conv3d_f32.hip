@@ -573,6 +573,7 @@ int sk_conv3d_f32(const sk_conv_src* srcs, int n_src, const float* weight, const
     SK_CHECK_ARG(ksize == 1 || ksize == 2 || ksize == 3, "sk_conv3d_f32: ksize must be 1, 2 or 3");
     SK_CHECK_ARG(cout >= 1 && (gn_partial == nullptr || cout % 32 == 0),
                  "sk_conv3d_f32: GroupNorm partials need cout %% 32 == 0");
+    SK_CHECK_ARG(B >= 1 && ox >= 1 && oy >= 1 && oz >= 1, "sk_conv3d_f32: bad extents");
     ConvF32Args a{};
     a.nsrc = n_src;
     for (int i = 0; i < n_src; ++i) {
