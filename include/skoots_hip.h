@@ -911,6 +911,33 @@ int sk_instance_stats(const int32_t* labels, int X, int Y, int Z, const int32_t*
 int sk_instance_mesh_cells(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
                            const uint8_t* class_of, int n_classes, int closed, int64_t* cells, void* stream);
 
+/* The marching-cubes mesh of every instance (ABI 18): the triangles whose area section 21 measures,
+ * written out.  labels, lut, max_id, N, closed, the cells and "a cell shared by k instances belongs to each of them" are
+ * those of sk_instance_mesh_cells.  tri_table: 256 uint64 in device memory, one per configuration: bits 60 .. 63 the
+ * number of triangles (more than 5 counts as 5), bits 4 i .. 4 i + 3 edge number i % 3 of triangle i / 3
+ * (skoots_amd/validate/mc_triangles.py; edge e = 4 axis + k starts at the k-th corner, ascending, whose bit `axis` is
+ * clear).  The voxel key of (x, y, z) is its linear index in the volume padded by one layer,
+ * ((x + 1) (Y + 2) + y + 1) (Z + 2) + z + 1.  A vertex of row a is a cell edge (an axis-neighbour voxel pair inside
+ * the corner range of the cells) whose two voxels have exactly one of row a; its edge key is the voxel key of its low
+ * voxel x 3 + axis, and its position the midpoint of the two voxels.
+ * sk_instance_mesh_count: counts[(a - 1) * 2] = vertices and counts[(a - 1) * 2 + 1] = triangles of row a (int64; the
+ * entry point zeroes counts itself, stream-ordered).
+ * sk_instance_mesh_emit: one record of 2 int64 per vertex, (row, edge key), and one of 5 int64 per triangle,
+ * (row, edge key of its three vertices in scikit-image's winding, order key = voxel key of the cell's low corner x 8 +
+ * the triangle's position in its configuration), in no particular order, at slots taken with one global atomic per
+ * workgroup tile and kind.  A record whose slot is at or beyond its capacity (in records) is not written;
+ * produced[0] / produced[1] (zeroed by the entry point) are the vertex / triangle records the volume has, whatever the
+ * capacities, so a caller compares them with the count pass.  vertices / triangles may be NULL at capacity 0.
+ * Integer atomics only: the SET of records is the same on every run.  Checked before anything is launched or written:
+ * extents, N, max_id and capacities not negative, X Y Z < 2^62 and (X + 2) (Y + 2) (Z + 2) < 2^60 (the keys stay in
+ * int64), capacities < 2^58, closed 0 or 1, no NULL pointer, pointers aligned to their elements.  An empty volume or
+ * N == 0 returns SK_OK and writes nothing; an extent of 1 in open mode has no cell: zeros. */
+int sk_instance_mesh_count(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                           const uint64_t* tri_table, int closed, int64_t* counts, void* stream);
+int sk_instance_mesh_emit(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                          const uint64_t* tri_table, int closed, int64_t* vertices, int64_t vertex_capacity,
+                          int64_t* triangles, int64_t triangle_capacity, int64_t* produced, void* stream);
+
 /* Exact squared Euclidean distance transform of every instance at once (ABI 17).  labels, lut,
  * max_id and N are those of sk_instance_stats; r(v) is the row of voxel v (1 .. N, 0 for background).  wx, wy, wz are
  * the squares of the voxel spacing, fl(sx sx) and so on, formed in double by the caller.  For a voxel p with r(p) > 0

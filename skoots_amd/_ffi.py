@@ -187,6 +187,8 @@ _SIGS = {
     "sk_instance_stats_row_values": (i32, [i32]),
     "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "sk_instance_mesh_cells": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp]),
+    "sk_instance_mesh_count": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp]),
+    "sk_instance_mesh_emit": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, i64, vp, i64, vp, vp]),
     "sk_label_edt_pass": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, C.c_double, i32, vp, vp, vp, vp]),
     "sk_label_edt": (i32, [vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, i32, vp, vp, vp, vp]),
     "sk_label_planes_workspace_bytes": (sz, [i32, i32, i32]),

@@ -19,6 +19,10 @@ class, integers once more -- and ``skeleton_columns`` turns the links into a len
 ``thickness="open"`` / ``"closed"`` / ``--thickness`` adds the width: the exact Euclidean distance transform of every
 instance (``sk_label_edt``) and ``inscribed_radius``, the square root of its maximum; together with the
 skeleton, the mean, minimum and maximum radius along the centre line.
+
+``mesh="open"`` / ``"closed"`` / ``--mesh`` adds the size of the marching-cubes mesh itself -- vertices, triangles and,
+closed, the Euler characteristic (``sk_instance_mesh_count``) -- and ``--save-meshes`` writes the
+meshes of ``lib.instance_meshes`` into one PLY file.
 """
 from __future__ import annotations
 
@@ -32,8 +36,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .lib import (check_shape, id_rows, instance_mesh_cells, instance_skeleton_graph, instance_sums,
-                  instance_thickness)
+from .lib import (check_shape, id_rows, instance_mesh_cells, instance_mesh_counts, instance_meshes,
+                  instance_skeleton_graph, instance_sums, instance_thickness)
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
@@ -44,6 +48,9 @@ SKELETON_COLUMNS = "skeleton_voxels,skeleton_length,skeleton_endpoints,skeleton_
 THICKNESS_COLUMNS = "inscribed_radius"                   # appended with --thickness
 SKELETON_RADIUS_COLUMNS = "skeleton_radius_mean,skeleton_radius_min,skeleton_radius_max"  # --thickness with --skeleton
 THICKNESS_MODES = (None, "open", "closed")
+MESH_COLUMNS = "mesh_vertices,mesh_triangles"            # appended with --mesh
+MESH_CLOSED_COLUMNS = "euler_characteristic"             # ... and behind them with --mesh closed
+MESH_MODES = (None, "open", "closed")
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -188,8 +195,24 @@ def thickness_columns(max_d2: Tensor, skel_stats: Optional[Tensor] = None) -> Di
     return out
 
 
+def mesh_columns(counts: Tensor, closed: bool) -> Dict[str, Tensor]:
+    """The mesh columns (int64 host tensors) from the (N, 2) counts of ``instance_mesh_counts``: ``mesh_vertices`` and
+    ``mesh_triangles``, and for a closed mesh ``euler_characteristic`` = V - E + F = V - F / 2.  A closed mesh is
+    edge-manifold -- every edge has two triangles, E = 3 F / 2 -- so the value is an integer: 2 per surface component
+    less twice its handles (a ball 2, a ball with a cavity 4, a torus 0).  Two parts of an instance that meet in a voxel
+    edge or corner only are separate surfaces.  An open mesh has boundary edges and no such identity: no column."""
+    c = counts.cpu().to(torch.int64).reshape(-1, 2)
+    out = {"mesh_vertices": c[:, 0].clone(), "mesh_triangles": c[:, 1].clone()}
+    if closed:
+        if bool((c[:, 1] % 2 != 0).any()):
+            raise RuntimeError("a closed mesh with an odd number of triangles: the counts are not those of closed mode")
+        out["euler_characteristic"] = c[:, 0] - c[:, 1] // 2
+    return out
+
+
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
-                       skeleton: bool = False, thickness: Optional[str] = None) -> Dict[str, Tensor]:
+                       skeleton: bool = False, thickness: Optional[str] = None,
+                       mesh: Optional[str] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -217,7 +240,13 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     instance voxel to the nearest voxel outside its instance (``lib.instance_thickness``; "open" counts the voxels of
     the volume only, "closed" pads it with background), ``max_dist2`` (N) float64 and ``inscribed_radius`` =
     ``sqrt(max_dist2)``; together with ``skeleton=True`` also ``skeleton_radius_mean`` / ``_min`` / ``_max``, the radius
-    sampled on the skeleton voxels (``thickness_columns``)."""
+    sampled on the skeleton voxels (``thickness_columns``).
+
+    ``mesh="open"`` or ``"closed"`` adds ``mesh_vertices`` and ``mesh_triangles`` (int64), the size of the mesh that
+    ``lib.instance_meshes`` would return, from its count pass, and in closed mode ``euler_characteristic`` (int64;
+    ``mesh_columns``)."""
+    if mesh not in MESH_MODES:
+        raise ValueError(f"mesh must be one of {MESH_MODES}, got {mesh!r}")
     if surface not in SURFACE_MODES:
         raise ValueError(f"surface must be one of {SURFACE_MODES}, got {surface!r}")
     if thickness not in THICKNESS_MODES:
@@ -245,13 +274,17 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
                                                      volume[0] if volume else None)
         out["max_dist2"], out["dist2"] = max_d2, dist2
         out.update({k: v.to(sums.device) for k, v in thickness_columns(max_d2, *skel).items()})
+    if mesh is not None:
+        _, counts = instance_mesh_counts(x, mesh == "closed", rows)
+        out.update({k: v.to(sums.device) for k, v in mesh_columns(counts, mesh == "closed").items()})
     return out
 
 
 def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=(1.0, 1.0, 1.0),
                min_voxels: int = 1, mesh_cells: Optional[Tensor] = None,
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
-               skeleton_radius: Optional[Tensor] = None) -> str:
+               skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
+               mesh_closed: bool = False) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -260,7 +293,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     again, nothing changes.  With ``max_dist2`` (the (N) maxima of ``instance_thickness``) ``inscribed_radius`` follows,
     and with ``skeleton_radius`` (its (N, 3) skeleton statistics) ``skeleton_radius_mean,skeleton_radius_min,
     skeleton_radius_max``, in that order behind everything else; an instance alone in the volume in open mode prints
-    ``inf``."""
+    ``inf``.  With ``mesh_counts`` (the (N, 2) counts of ``instance_mesh_counts``) ``mesh_vertices,mesh_triangles``
+    follow behind all of those, and ``euler_characteristic`` behind them when ``mesh_closed`` says the counts are those
+    of closed mode."""
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
@@ -271,13 +306,18 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         raise ValueError("skeleton_radius comes with max_dist2: both are results of instance_thickness")
     if max_dist2 is not None:
         d.update(thickness_columns(max_dist2, skeleton_radius))
+    mesh_names = []
+    if mesh_counts is not None:
+        d.update(mesh_columns(mesh_counts, bool(mesh_closed)))
+        mesh_names = (MESH_COLUMNS + ("," + MESH_CLOSED_COLUMNS if mesh_closed else "")).split(",")
     d = {k: v.cpu().tolist() for k, v in d.items()}
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
              ("," + SKELETON_COLUMNS if skeleton_graph is not None else "") +
              ("," + THICKNESS_COLUMNS if max_dist2 is not None else "") +
-             ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") + "\n"]
+             ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") +
+             "".join("," + k for k in mesh_names) + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -293,6 +333,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
             cells += [repr(d["inscribed_radius"][i])]
         if skeleton_radius is not None:
             cells += [repr(d[k][i]) for k in SKELETON_RADIUS_COLUMNS.split(",")]
+        cells += [d[k][i] for k in mesh_names]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -324,6 +365,17 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                         help="Also write <mask>_distance.tif, float32, every instance voxel its distance to the nearest "
                              "voxel outside its instance and background 0, stored [Z, X, Y] like the mask (implies "
                              "--thickness open when no mode is given)")
+    parser.add_argument("--mesh", type=str, default=None, choices=("open", "closed"),
+                        help="Append " + MESH_COLUMNS + ": the size of every instance's marching-cubes mesh, left open "
+                             "where the volume's faces cut it or closed there; closed also appends " +
+                             MESH_CLOSED_COLUMNS + " = vertices - triangles / 2")
+    parser.add_argument("--save-meshes", action="store_true",
+                        help="Also write <mask>_meshes.ply: the meshes of the instances the CSV file lists (--min-voxels "
+                             "applies), one binary PLY, coordinates in physical units x, y, z, the instance id as a "
+                             "property of vertices and faces, normals pointing out (implies --mesh closed when no mode is "
+                             "given)")
+    parser.add_argument("--mesh-ids", type=int, nargs="+", default=None, metavar="ID",
+                        help="With --save-meshes: write only these instances")
     parser.add_argument("--out", type=str, default=None, help="Output file (default: <mask>_instance_stats.csv)")
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
@@ -331,6 +383,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args.skeleton = args.skeleton or args.save_skeletons
     if args.save_distance and args.thickness is None:
         args.thickness = "open"
+    if args.save_meshes and args.mesh is None:
+        args.mesh = "closed"
+    if args.mesh_ids is not None and not args.save_meshes:
+        parser.error("--mesh-ids selects the instances of --save-meshes")
     return args
 
 
@@ -362,8 +418,9 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         max_d2, dist2, *skel = instance_thickness(dev_mask, spacing, args.thickness == "closed", rows,
                                                   volume[0] if args.skeleton else None)[1:]
         skel_radius = skel[0] if skel else None
+    mesh_counts = instance_mesh_counts(dev_mask, args.mesh == "closed", rows)[1] if args.mesh else None
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
-                      max_d2, skel_radius)
+                      max_d2, skel_radius, mesh_counts, args.mesh == "closed")
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
@@ -381,6 +438,21 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         # (X, Y, Z) -> the mask's [Z, X, Y]; inf (an instance alone in the volume, open mode) stays inf in float32
         tiff.write_float_stack(dist_path, torch.sqrt(dist2).to(torch.float32).permute(2, 0, 1).contiguous())
         print(f"File Written: {dist_path}")
+    if args.save_meshes:
+        from ..lib.ply import write_ply
+        keep = ids[sums[:, 0] >= args.min_voxels]
+        if args.mesh_ids is not None:
+            missing = sorted(set(args.mesh_ids) - set(keep.tolist()))
+            if missing:
+                raise ValueError(f"--mesh-ids {missing}: not among the instances of {args.mask} with at least "
+                                 f"{args.min_voxels} voxels")
+            keep = torch.tensor(sorted(set(args.mesh_ids)), dtype=torch.int64)
+        m = instance_meshes(dev_mask, args.mesh == "closed", rows, ids=keep)
+        mesh_path = f"{os.path.splitext(args.mask)[0]}_meshes.ply"
+        name = os.path.basename(args.mask).encode("ascii", "replace").decode("ascii")     # a PLY header is ASCII
+        write_ply(mesh_path, m["ids"], m["vertices"], m["faces"], m["vertex_offsets"], m["face_offsets"], spacing,
+                  comment=f"skoots_amd marching-cubes meshes ({args.mesh}) of {name}")
+        print(f"File Written: {mesh_path}")
     return out_path
 
 

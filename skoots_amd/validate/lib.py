@@ -9,12 +9,14 @@ pair; here one kernel pass builds the (gt, pred) contingency tables and a second
 ``instance_sums`` measures every instance of one mask in a single kernel pass; ``mask_to_bbox`` is the
 reference's function of that name on top of it, and ``validate/compare.py`` derives the per-instance statistics.
 ``instance_mesh_cells`` counts every instance's marching-cubes cells per class in one more pass.
+``instance_meshes`` writes those meshes out: vertices and faces of every instance from a count and an emit pass
+(DESIGN.md §24).
 ``instance_skeleton_graph`` thins every instance in its box and reads the skeletons as graphs.
 ``instance_thickness`` is the exact distance transform of every instance and its maximum per instance.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Dict, Tuple
 
 import numpy as np
 import torch
@@ -260,6 +262,147 @@ def instance_mesh_cells(x: Tensor, closed: bool = False, rows=None) -> Tuple[Ten
     _ffi.check(_ffi.lib.sk_instance_mesh_cells(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(class_of),
                                                n_classes, int(bool(closed)), _ffi.ptr(cells), _ffi.stream_ptr(dev)))
     return ids, cells
+
+
+MESH_BUDGET = 4 << 30          # bytes of vertex and triangle records instance_meshes may ask for
+_VERTEX_BYTES, _TRIANGLE_BYTES = 16, 40       # a record of sk_instance_mesh_emit: 2 and 5 int64
+
+
+def packed_triangle_table() -> np.ndarray:
+    """(256) uint64: ``mc_triangles.TRIANGLES`` as ``sk_instance_mesh_count`` / ``_emit`` read it -- bits 4 i .. 4 i + 3
+    hold edge number i % 3 of triangle i / 3, bits 60 .. 63 the number of triangles."""
+    from .mc_triangles import TRIANGLES
+    out = np.zeros(256, np.uint64)
+    for c, tris in enumerate(TRIANGLES):
+        v = len(tris) << 60
+        for j, t in enumerate(tris):
+            for i, e in enumerate(t):
+                v |= e << (4 * (3 * j + i))
+        out[c] = v
+    return out
+
+
+def _mesh_prologue(x: Tensor, rows, ids):
+    """(x, rows, (X, Y, Z)) for the mesh kernels, the shape checked; with ``ids`` the look-up table of ``rows`` is
+    replaced by one in which every other instance is background and the chosen ones are the rows 1..len(ids), ascending."""
+    x, rows = id_rows(x) if rows is None else rows
+    X, Y, Z = (int(v) for v in x.shape)
+    if X * Y * Z >= 2 ** 62 or (X + 2) * (Y + 2) * (Z + 2) >= 2 ** 60:
+        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to mesh: X*Y*Z must stay below 2^62 and "
+                         "(X+2)*(Y+2)*(Z+2) below 2^60")
+    if ids is not None:
+        want = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+        want = torch.unique(want).to(x.device)               # ascending
+        if want.numel() == 0:
+            return x, None, (X, Y, Z)
+        have = rows[1] if rows is not None else want.new_empty(0)
+        at = torch.searchsorted(have, want).clamp_(max=max(int(have.numel()) - 1, 0))
+        if have.numel() == 0 or not bool((have[at] == want).all()):
+            missing = want.tolist() if have.numel() == 0 else want[have[at] != want].tolist()
+            raise ValueError(f"ids {missing} are not in the mask")
+        a, _, lut, max_id = rows
+        # the value that `a` holds for each wanted instance: the id itself, or the row where _id_rows relabelled
+        values = torch.nonzero(lut)[:, 0][at]
+        sub = torch.zeros_like(lut)
+        sub[values] = torch.arange(1, want.numel() + 1, dtype=torch.int32, device=x.device)
+        rows = (a, want, sub, max_id)
+    return x, rows, (X, Y, Z)
+
+
+def instance_mesh_counts(x: Tensor, closed: bool = True, rows=None, ids=None) -> Tuple[Tensor, Tensor]:
+    """(ids (N) int64 ascending, counts (N, 2) int64): vertices and triangles of the marching-cubes mesh of every
+    instance, from one ``sk_instance_mesh_count`` launch.  The arguments are ``instance_meshes``'."""
+    x, rows, (X, Y, Z) = _mesh_prologue(x, rows, ids)
+    dev = x.device
+    if rows is None:
+        return torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, 2), dtype=torch.int64, device=dev)
+    a, ids, lut, max_id = rows
+    N = int(ids.numel())
+    counts = torch.zeros((N, 2), dtype=torch.int64, device=dev)
+    table = torch.from_numpy(packed_triangle_table().view(np.int64)).to(dev)
+    _ffi.check(_ffi.lib.sk_instance_mesh_count(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(table),
+                                               int(bool(closed)), _ffi.ptr(counts), _ffi.stream_ptr(dev)))
+    return ids, counts
+
+
+def instance_meshes(x: Tensor, closed: bool = True, rows=None, ids=None,
+                    budget_bytes: int = MESH_BUDGET) -> Dict[str, Tensor]:
+    """The marching-cubes mesh of every instance of an (X, Y, Z) integer device tensor -- what scikit-image's
+    ``marching_cubes((x == id) * 255)`` gives each id, vertices welded -- from two kernel passes over the mask
+    (``sk_instance_mesh_count``, ``sk_instance_mesh_emit``).  Device tensors:
+
+    ``ids`` (N) int64 ascending; ``vertices`` (V, 3) int32 in DOUBLED index coordinates (every vertex is the midpoint
+    of two neighbouring voxels: twice its x, y, z are integers, and -1 occurs in closed mode); ``faces`` (F, 3) int32,
+    indices LOCAL to the instance; ``vertex_offsets`` and ``face_offsets`` (N + 1) int64: instance k owns
+    ``vertices[vertex_offsets[k]:vertex_offsets[k + 1]]`` and likewise its faces.
+
+    Canonical order, the same on every run: instances ascending by id; within one, vertices ascending by edge key (x,
+    then y, then z of the edge's low voxel, then the axis) and faces ascending by order key (x, y, z of the cell, then
+    the triangle's place in ``mc_triangles.TRIANGLES``); each face keeps scikit-image's vertex order, whose right-hand
+    normal points INTO the object.
+
+    ``closed=True`` meshes the mask padded with one layer of background, so every surface is closed; ``closed=False``
+    is the reference's meaning (``instance_mesh_cells``).  ``rows`` is ``id_rows(x)`` when the caller has it.  ``ids``
+    meshes only those instances: the others are background to the kernels, and each result equals that instance's
+    slice of the full result.  The kernels emit records that carry edge keys; the sort by (row, key) and the
+    look-up that turns keys into local indices are torch calls on the device.
+
+    Raises ``ValueError`` before anything is allocated when the count pass shows that the records would exceed
+    ``budget_bytes`` (16 bytes per vertex, 40 per triangle; sorting needs about as much again), or when
+    N * 8 * (X+2)(Y+2)(Z+2) reaches 2^63 and the sort keys would leave int64."""
+    x, rows, (X, Y, Z) = _mesh_prologue(x, rows, ids)
+    dev = x.device
+    N = int(rows[1].numel()) if rows is not None else 0
+    padded = (X + 2) * (Y + 2) * (Z + 2)
+    if N * 8 * padded >= 2 ** 63:
+        raise ValueError(f"{N} instances in a mask of shape {(X, Y, Z)}: N * 8 * (X+2)(Y+2)(Z+2) = {N * 8 * padded} "
+                         "must stay below 2^63 for the sort keys; mesh fewer instances at a time with ids=[...]")
+    ids_out, counts = instance_mesh_counts(x, closed, (x, rows))
+    out = {"ids": ids_out}
+    V, F = (int(v) for v in counts.sum(0).tolist()) if N else (0, 0)
+    need = V * _VERTEX_BYTES + F * _TRIANGLE_BYTES
+    if need > int(budget_bytes):
+        raise ValueError(f"the meshes have {V} vertices and {F} triangles: {need} bytes of records, more than "
+                         f"budget_bytes = {int(budget_bytes)}; mesh fewer instances at a time with ids=[...], or raise "
+                         "the budget")
+    if V >= 2 ** 31:
+        raise ValueError(f"the meshes have {V} vertices; indices are int32: mesh fewer instances at a time with "
+                         "ids=[...]")
+    zeros = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    if V == 0:
+        out.update(vertices=torch.empty((0, 3), dtype=torch.int32, device=dev),
+                   faces=torch.empty((0, 3), dtype=torch.int32, device=dev), vertex_offsets=zeros,
+                   face_offsets=zeros.clone())
+        return out
+    a, _, lut, max_id = rows
+    vrec = torch.empty((V, 2), dtype=torch.int64, device=dev)
+    trec = torch.empty((F, 5), dtype=torch.int64, device=dev)
+    produced = torch.zeros(2, dtype=torch.int64, device=dev)
+    table = torch.from_numpy(packed_triangle_table().view(np.int64)).to(dev)
+    _ffi.check(_ffi.lib.sk_instance_mesh_emit(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(table),
+                                              int(bool(closed)), _ffi.ptr(vrec), V, _ffi.ptr(trec), F,
+                                              _ffi.ptr(produced), _ffi.stream_ptr(dev)))
+    if produced.tolist() != [V, F]:
+        raise RuntimeError(f"sk_instance_mesh_emit produced {produced.tolist()} records where the count pass gave "
+                           f"{[V, F]}")
+    # canonical order: (row, edge key) and (row, order key) as one int64 each
+    vkey = torch.sort((vrec[:, 0] - 1) * (3 * padded) + vrec[:, 1])[0]
+    torder = torch.argsort((trec[:, 0] - 1) * (8 * padded) + trec[:, 4])
+    trec = trec[torder]
+    voff = torch.cat((zeros[:1], torch.cumsum(counts[:, 0], 0)))
+    foff = torch.cat((zeros[:1], torch.cumsum(counts[:, 1], 0)))
+    trow = trec[:, 0] - 1
+    glob = torch.searchsorted(vkey, (trow[:, None] * (3 * padded) + trec[:, 1:4]).contiguous())
+    if not bool((vkey[glob.clamp(max=V - 1)] == trow[:, None] * (3 * padded) + trec[:, 1:4]).all()):
+        raise RuntimeError("sk_instance_mesh_emit: a triangle names a vertex that was not emitted")
+    faces = (glob - voff[trow][:, None]).to(torch.int32)
+    key = vkey % (3 * padded)
+    axis, vox = key % 3, key // 3
+    px, py, pz = vox // ((Y + 2) * (Z + 2)), vox // (Z + 2) % (Y + 2), vox % (Z + 2)
+    vertices = torch.stack((px, py, pz), 1) * 2 - 2           # the padded index is the coordinate + 1
+    vertices[torch.arange(V, device=dev), axis] += 1
+    out.update(vertices=vertices.to(torch.int32), faces=faces, vertex_offsets=voff, face_offsets=foff)
+    return out
 
 
 SKELETON_BUDGET = 1 << 30   # bytes of thinning workspace per batch of instance_skeleton_graph

@@ -9,6 +9,8 @@
 (DESIGN.md §21).  ``get_face_area`` is the area of the exposed voxel faces, exact for what it defines and an
 overestimate of a curved surface.
 
+``get_mesh`` is that mesh itself, vertices and faces, for one binary mask.
+
 ``get_skeleton_length`` is the length of the mask's Lee skeleton read as a graph, on the path of
 ``compare.stats_per_instance(skeleton=True)``.
 
@@ -23,7 +25,7 @@ import torch
 from torch import Tensor
 
 from .compare import _spacing, mesh_area, skeleton_columns, thickness_columns
-from .lib import instance_mesh_cells, instance_skeleton_graph, instance_sums, instance_thickness
+from .lib import instance_mesh_cells, instance_meshes, instance_skeleton_graph, instance_sums, instance_thickness
 
 
 def _one_row(x: Tensor) -> Tensor:
@@ -65,6 +67,19 @@ def get_surface_area(x: Tensor, anisotropy_ratio: Union[List[float], Tensor], cl
     _, cells = instance_mesh_cells((x > 0).to(torch.int32), closed=closed)
     area = mesh_area(cells, anisotropy_ratio)            # checks the spacing, also for a mask without foreground
     return (area[0] if area.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
+
+
+def get_mesh(x: Tensor, anisotropy_ratio: Union[List[float], Tensor], closed: bool = False):
+    """(verts (V, 3) float64 in physical units, faces (F, 3) int64), on x's device: the marching-cubes mesh of ``x > 0``
+    at the voxel spacing ``anisotropy_ratio`` -- the mesh whose area ``get_surface_area`` returns, which the reference
+    builds with ``skimage.measure.marching_cubes`` and throws away (stats.py:30-48).  Vertices are welded and in the
+    canonical order of ``lib.instance_meshes``; faces keep scikit-image's vertex order.  ``closed`` is
+    ``get_surface_area``'s.  A mask without surface gives (0, 3) arrays where scikit-image raises."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    s = torch.tensor(_spacing(anisotropy_ratio), dtype=torch.float64, device=x.device)
+    m = instance_meshes((x > 0).to(torch.int32), closed=closed)
+    return m["vertices"].to(torch.float64) * s / 2.0, m["faces"].to(torch.int64)
 
 
 def get_skeleton_length(x: Tensor, spacing: Union[List[float], Tensor]) -> Tensor:
