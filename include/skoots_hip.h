@@ -966,6 +966,54 @@ int sk_label_edt_pass(const int32_t* labels, int X, int Y, int Z, const int32_t*
 int sk_label_edt(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, double wx, double wy,
                  double wz, int closed, double* dist2, double* scratch, uint64_t* row_max, void* stream);
 
+/* Surface voxels of every instance, and exact distances between surface voxel sets (ABI 19): what
+ * validate/compare.py: compare() is made of.  labels, lut, max_id and N are those of sk_instance_stats; r(v) is the row
+ * of voxel v, 1 .. N, and 0 for background, unlisted ids and every position outside the volume.
+ * A surface voxel of row a is a voxel v with r(v) = a of whose six face neighbours at least one has a row != a; outside
+ * counts as row 0, so no instance has an empty surface (scipy: m & ~binary_erosion(m), default structure,
+ * border_value 0).  Its surface key is (a - 1) X Y Z + ((x Y + y) Z + z), int64: sorted ascending, the keys of a row are
+ * one contiguous segment in x-major order, and key mod X Y Z is the voxel.
+ * sk_instance_surface_count: counts[a - 1] = surface voxels of row a (int64; zeroed by the entry point, stream-ordered).
+ * sk_instance_surface_emit: the surface keys, in no particular order, at slots taken with one global atomic per
+ * workgroup and tile.  A key whose slot is at or beyond `capacity` is not written; produced[0] (zeroed by the entry
+ * point) is the number of surface voxels the volume has, whatever the capacity.  keys may be NULL at capacity 0.
+ * Integer atomics only: the SET of keys is the same on every run.  Checked before anything is launched or written:
+ * extents, N, max_id and capacity not negative, every extent <= 2^26, N X Y Z < 2^63 (the keys stay in int64),
+ * capacity < 2^60, no NULL pointer, pointers aligned to their elements.  An empty volume or N == 0 returns SK_OK and
+ * writes nothing.
+ *
+ * sk_surface_distances: q_keys / t_keys are keys as above (only key mod X Y Z is used), cut into q_segments / t_segments
+ * segments by q_offsets / t_offsets (segments + 1 int64 each: segment s is [offsets[s], offsets[s + 1])).  pairs: P x 2
+ * int32, the query segment and the target segment of pair k, 0-based; a segment may appear in any number of pairs.
+ * out_offsets: P + 1 int64, out_offsets[0] = 0 and out_offsets[k + 1] - out_offsets[k] = the queries of pair k.  With
+ * (wx, wy, wz) = (fl(sx sx), fl(sy sy), fl(sz sz)) formed in double by the caller, for the i-th key q of the query
+ * segment of pair k and its target segment T
+ *   d2[out_offsets[k] + i] = min over t in T of  fl(wx dx^2 + fl(wy dy^2 + wz dz^2)),   dx = qx - tx, ...
+ * where every square is an exact integer converted to double and every product and sum is rounded once (no fused
+ * multiply-add; w (d d), never (w d) d), as in sk_label_edt; +inf when T is empty.  A minimum does not depend on the
+ * order, and the pruning of the implementation skips only candidates that cannot be smaller (rounding is monotone), so
+ * the value is exactly this at any spacing and for keys in any order; sorted keys make the pruning effective.  At
+ * integer-valued spacings sqrt(d2) equals scipy.ndimage.distance_transform_edt(~T, sampling) at q bit for bit.  Every
+ * output has one writer and nothing accumulates: the same bits on every run.  All arrays are device memory.  Checked
+ * before anything is launched or written: extents, P and segment counts not negative, every extent <= 2^26, the weights
+ * finite and > 0, pointers aligned to their elements, no NULL pointer (keys and d2 may be NULL where they have no
+ * element); then the offsets and pairs are read back (the call synchronises the stream) and checked: offsets not
+ * negative and monotone, every pair inside the segment counts, out_offsets as stated.  That q_keys / t_keys hold
+ * q_offsets[q_segments] / t_offsets[t_segments] elements and d2 out_offsets[P] is the caller's to ensure: the lengths
+ * are not arguments (validate/lib.py: surface_distances checks them).  SK_ERR_CAPACITY when the host copies of the
+ * tables cannot be allocated.  P == 0 or no query returns SK_OK and writes nothing.  The work is sum over pairs of queries x targets at most and has no other bound: the caller
+ * limits a call (validate/lib.py: LAUNCH_BUDGET).  sk_surface_distance_tile(): the target voxels per LDS tile (1024),
+ * for tests that place their sizes around it. */
+int sk_surface_distance_tile(void);
+int sk_instance_surface_count(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                              int64_t* counts, void* stream);
+int sk_instance_surface_emit(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                             int64_t capacity, int64_t* keys, int64_t* produced, void* stream);
+int sk_surface_distances(const int64_t* q_keys, const int64_t* q_offsets, int q_segments, const int64_t* t_keys,
+                         const int64_t* t_offsets, int t_segments, const int32_t* pairs, int P,
+                         const int64_t* out_offsets, int X, int Y, int Z, double wx, double wy, double wz, double* d2,
+                         void* stream);
+
 /* ------------------------------------------------------------------------ *
  * flood_and_stitch (skoots/utils/flood_and_stitch.py)
  * ------------------------------------------------------------------------ */

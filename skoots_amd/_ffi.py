@@ -191,6 +191,11 @@ _SIGS = {
     "sk_instance_mesh_emit": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, i64, vp, i64, vp, vp]),
     "sk_label_edt_pass": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, C.c_double, i32, vp, vp, vp, vp]),
     "sk_label_edt": (i32, [vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, i32, vp, vp, vp, vp]),
+    "sk_surface_distance_tile": (i32, []),
+    "sk_instance_surface_count": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp]),
+    "sk_instance_surface_emit": (i32, [vp, i32, i32, i32, vp, i32, i32, i64, vp, vp, vp]),
+    "sk_surface_distances": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, C.c_double, C.c_double,
+                                   C.c_double, vp, vp]),
     "sk_label_planes_workspace_bytes": (sz, [i32, i32, i32]),
     "sk_label_planes": (i32, [vp, i32, i32, i32, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
     "sk_plane_overlaps_workspace_bytes": (sz, [i32]),

@@ -13,6 +13,10 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 (DESIGN.md §24).
 ``instance_skeleton_graph`` thins every instance in its box and reads the skeletons as graphs.
 ``instance_thickness`` is the exact distance transform of every instance and its maximum per instance.
+``instance_surfaces``, ``surface_distances``, ``match_instances`` and ``pair_summaries`` are the parts of
+``validate/compare.py: compare()``: every instance's surface voxels as sorted keys, the exact squared distance from
+every surface voxel of one instance to the surface of another for many pairs at once, the matching rule, and the
+reduction to Hausdorff / ASSD / surface Dice.
 """
 from __future__ import annotations
 
@@ -524,6 +528,211 @@ def instance_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False,
             # rounding can put the mean of equal values a unit outside them: keep it inside [min, max]
             stats[r] = (min(max(total / v.size, v.min()), v.max()), v.min(), v.max())
     return ids, max_d2, dist2, torch.from_numpy(stats)
+
+
+# ---- compare(): surfaces, matching and surface distances ----
+
+# Pair evaluations (queries x targets, before pruning) one ``sk_surface_distances`` launch may be asked for.  The work
+# of a call has no bound of its own -- one instance with 10^7 surface voxels against its twin is 10^14 evaluations --
+# so ``surface_distances`` splits the pair list, and the queries of a very large pair, into launches of at most this
+# many.  The value is meant to keep a launch well under a second.  It was chosen on an estimate of 1e12 evaluations
+# per second and has since been held against one measurement (tools/bench_compare.py on one MI355X,
+# profiles/compare_bench.json): a pair of 2^19 x 2^19 voxels in which no tile can be pruned, four launches of 2^36, ran
+# at 1.86e12 evaluations per second, 37 ms a launch; that is the worst case, and pruning only shortens it.  The value stays; the result
+# does not depend on it.
+LAUNCH_BUDGET = 1 << 36
+_MAX_EXTENT = 1 << 26
+
+
+def _require_device(t, name: str, dtype) -> Tensor:
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU "
+                         "fallback")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    return t.contiguous()
+
+
+def instance_surfaces(x: Tensor, rows=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(ids (N) int64 ascending, offsets (N + 1) int64, keys int64) of the positive ids of an (X, Y, Z) integer device
+    tensor: the surface voxels of every instance -- the voxels of the instance with a face neighbour that is not,
+    outside the volume included (scipy: ``m & ~binary_erosion(m)``) -- as surface keys
+    ``row * X Y Z + ((x Y + y) Z + z)``, row 0-based, sorted ascending: instance k owns
+    ``keys[offsets[k]:offsets[k + 1]]``, its voxels in x-major order.  One count pass, one emit pass
+    (``sk_instance_surface_count``, ``sk_instance_surface_emit``) and one ``torch.sort``.  ``rows`` is ``id_rows(x)``
+    when the caller already has it."""
+    x, rows = id_rows(x) if rows is None else rows
+    X, Y, Z = (int(v) for v in x.shape)
+    dev = x.device
+    if rows is None:
+        return (torch.empty(0, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev))
+    a, ids, lut, max_id = rows
+    N = int(ids.numel())
+    if max(X, Y, Z) > _MAX_EXTENT or N * X * Y * Z >= 2 ** 63:
+        raise ValueError(f"{N} instances in a mask of shape {(X, Y, Z)}: every extent must stay within 2^26 and "
+                         "N*X*Y*Z below 2^63, or the surface keys leave int64")
+    counts = torch.zeros(N, dtype=torch.int64, device=dev)
+    _ffi.check(_ffi.lib.sk_instance_surface_count(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(counts),
+                                                  _ffi.stream_ptr(dev)))
+    total = int(counts.sum().item())
+    keys = torch.empty(total, dtype=torch.int64, device=dev)
+    produced = torch.zeros(1, dtype=torch.int64, device=dev)
+    _ffi.check(_ffi.lib.sk_instance_surface_emit(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, total, _ffi.ptr(keys),
+                                                 _ffi.ptr(produced), _ffi.stream_ptr(dev)))
+    if int(produced.item()) != total:
+        raise RuntimeError(f"sk_instance_surface_emit produced {int(produced.item())} keys where the count pass gave "
+                           f"{total}")
+    keys = torch.sort(keys)[0]
+    offsets = torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))
+    return ids, offsets, keys
+
+
+def _launches(qo: np.ndarray, to: np.ndarray, pairs: np.ndarray, budget: int):
+    """The launches of ``surface_distances``: a list of (q_begin, q_end, target segment) int64 arrays, in output order.
+    A pair of more than ``budget`` evaluations is cut into runs of ``budget // targets`` queries (at least one); the
+    items are then packed greedily, in order, into launches of at most ``budget`` evaluations (an item that alone
+    exceeds it -- one query against more than ``budget`` targets -- is a launch of its own).
+
+    A query segment may appear in several pairs -- a prediction that several ground-truth instances chose -- and be cut
+    differently in each, or not at all.  The query segments of a launch are the offsets refined by ALL its cuts, so
+    every item of a launch is finally split at every cut of that launch that falls inside it: each item is then exactly
+    one of the launch's segments.  Splitting an item changes neither the evaluations nor the order of the outputs."""
+    items = []
+    for qs, ts in pairs.tolist():
+        qb, qe, nt = int(qo[qs]), int(qo[qs + 1]), max(int(to[ts + 1] - to[ts]), 1)
+        per = qe - qb if (qe - qb) * nt <= budget else max(1, budget // nt)
+        for b in range(qb, qe, max(per, 1)):
+            items.append((b, min(b + per, qe), ts, (min(b + per, qe) - b) * nt))
+    out, cur, cost = [], [], 0
+    for it in items:
+        if cur and cost + it[3] > budget:
+            out.append(cur)
+            cur, cost = [], 0
+        cur.append(it)
+        cost += it[3]
+    if cur:
+        out.append(cur)
+    launches = []
+    for launch in out:
+        cuts = np.unique(np.array([v for it in launch for v in it[:2]], np.int64))
+        qb, qe, ts = [], [], []
+        for b, e, t, _ in launch:
+            at = [b, *cuts[np.searchsorted(cuts, b, "right"):np.searchsorted(cuts, e, "left")].tolist(), e]
+            qb += at[:-1]
+            qe += at[1:]
+            ts += [t] * (len(at) - 1)
+        launches.append(tuple(np.array(v, np.int64) for v in (qb, qe, ts)))
+    return launches
+
+
+def surface_distances(query, target, pairs, shape, spacing=(1.0, 1.0, 1.0)) -> Tuple[Tensor, Tensor]:
+    """(out_offsets (P + 1) int64, d2 float64), device tensors: for pair k = (query segment, target segment) of
+    ``pairs`` ((P, 2) integers, 0-based), ``d2[out_offsets[k] + i]`` is the exact squared distance, at the voxel
+    ``spacing``, from the i-th voxel of the query segment to the nearest voxel of the target segment (``inf`` for an
+    empty one) -- ``sk_surface_distances``, DESIGN.md §25.  ``query`` and ``target`` are results of
+    ``instance_surfaces`` of masks of ``shape`` (X, Y, Z), or their ``(offsets, keys)``.  The pairs, and the queries
+    of a very large pair, are split into launches of at most ``LAUNCH_BUDGET`` evaluations; the result does not depend
+    on the split."""
+    q_off, q_keys = (_require_device(t, f"query[{k - 2}]", torch.int64) for k, t in enumerate(query[-2:]))
+    t_off, t_keys = (_require_device(t, f"target[{k - 2}]", torch.int64) for k, t in enumerate(target[-2:]))
+    dev = q_keys.device
+    X, Y, Z = (int(v) for v in shape)
+    sx, sy, sz = (float(v) for v in spacing)
+    if not all(np.isfinite(v) and v > 0 for v in (sx, sy, sz)):
+        raise ValueError(f"spacing must be three positive numbers (x, y, z), got {spacing}")
+    w = (sx * sx, sy * sy, sz * sz)
+    p = torch.as_tensor(pairs).cpu().to(torch.int64).reshape(-1, 2).numpy()
+    qo, to = q_off.cpu().numpy(), t_off.cpu().numpy()
+    if qo.size < 1 or to.size < 1 or np.any(np.diff(qo) < 0) or np.any(np.diff(to) < 0) or qo[0] < 0 or to[0] < 0:
+        raise ValueError("offsets must be non-negative, monotone and have one entry more than segments")
+    if qo[-1] > q_keys.numel() or to[-1] > t_keys.numel():
+        raise ValueError("offsets reach beyond the keys")
+    if p.size and (p.min() < 0 or p[:, 0].max() >= qo.size - 1 or p[:, 1].max() >= to.size - 1):
+        raise ValueError(f"pairs must name segments in [0, {qo.size - 1}) x [0, {to.size - 1})")
+    n_q = qo[p[:, 0] + 1] - qo[p[:, 0]] if p.size else np.zeros(0, np.int64)
+    out = np.concatenate((np.zeros(1, np.int64), np.cumsum(n_q, dtype=np.int64)))
+    d2 = torch.empty(int(out[-1]), dtype=torch.float64, device=dev)
+    done = 0
+    for qb, qe, ts in _launches(qo, to, p, int(LAUNCH_BUDGET)):
+        # the launch's own query segments: the offsets refined by the cuts, so that they stay monotone
+        breaks = np.unique(np.concatenate((qo, qb, qe)))
+        seg = np.searchsorted(breaks, qb)
+        if not np.array_equal(breaks[seg + 1], qe):
+            raise RuntimeError("surface_distances: an item of a launch is not one of the launch's query segments")
+        lp = torch.from_numpy(np.stack((seg, ts), 1).astype(np.int32)).to(dev)
+        lo = np.concatenate((np.zeros(1, np.int64), np.cumsum(qe - qb, dtype=np.int64)))
+        lq, lo_dev, part = torch.from_numpy(breaks).to(dev), torch.from_numpy(lo).to(dev), d2[done:]   # alive over the call
+        _ffi.check(_ffi.lib.sk_surface_distances(
+            _ffi.ptr(q_keys), _ffi.ptr(lq), int(breaks.size - 1), _ffi.ptr(t_keys), _ffi.ptr(t_off), int(to.size - 1),
+            _ffi.ptr(lp), int(lp.shape[0]), _ffi.ptr(lo_dev), X, Y, Z, *w, _ffi.ptr(part), _ffi.stream_ptr(dev)))
+        done += int(lo[-1])
+    if done != int(out[-1]):
+        raise RuntimeError(f"surface_distances: the launches wrote {done} of {int(out[-1])} distances")
+    return torch.from_numpy(out).to(dev), d2
+
+
+def match_instances(iou: Tensor, iou_threshold: float = 0.1) -> Tensor:
+    """(N) int64, on the matrix's device: for every row of the (N, M) IoU matrix the column with the largest value when
+    that value is > ``iou_threshold`` (strictly, as ``accuracies_from_iou``), the lowest such column on a tie, and -1
+    otherwise.  Several rows may name one column: an under-segmentation shows as such.  A pure function of the matrix;
+    N or M may be 0."""
+    iou = torch.as_tensor(iou)
+    n, m = (int(v) for v in iou.shape)
+    if n == 0 or m == 0:
+        return torch.full((n,), -1, dtype=torch.int64, device=iou.device)
+    best = iou.max(dim=1)[0]
+    cols = torch.arange(m, dtype=torch.int64, device=iou.device)
+    first = torch.where(iou == best[:, None], cols[None, :], cols.new_tensor(m)).min(dim=1)[0]
+    return torch.where(best > iou_threshold, first, first.new_tensor(-1))
+
+
+def nearest_rank(n: int, percent: int = 95) -> int:
+    """0-based index of the nearest-rank percentile of n ascending values: ceil(percent n / 100) - 1, in integers"""
+    return (percent * n + 99) // 100 - 1
+
+
+def pair_summaries(out_offsets: Tensor, d2: Tensor, n_g: int, tolerance2: float) -> Dict[str, Tensor]:
+    """The surface-distance columns of ``n_g`` matched pairs (host tensors) from the squared distances of both
+    directions: ``out_offsets`` (2 n_g + 1) and ``d2`` hold the ground-truth -> prediction distances of the pairs as
+    segments 0 .. n_g - 1 and the prediction -> ground-truth ones as segments n_g .. 2 n_g - 1.  With dg / dp the
+    ASCENDING ``sqrt`` of a pair's two segments:
+
+    ``hausdorff`` = max(dg[-1], dp[-1]); ``hausdorff95`` = max of the nearest-rank 95th percentiles,
+    ``d[ceil(0.95 n) - 1]``, one of the values themselves; ``assd`` = (sum dg + sum dp) / (|dg| + |dp|), each sum taken
+    left to right over the ascending values in float64, so it is the same on every run; ``nsd`` = the share of the
+    |dg| + |dp| squared distances that are <= ``tolerance2``, from integer counts; ``gt_surface_voxels`` and
+    ``pred_surface_voxels`` (int64) = |dg| and |dp|.  An empty segment makes the pair's floats ``nan``.
+
+    The segmented sort is two stable ``torch.sort`` calls on the tensors' device (by value, then by segment); the sums
+    are numpy's ``cumsum`` on the host, which adds strictly left to right."""
+    n_g = int(n_g)
+    off = out_offsets.cpu().to(torch.int64)
+    if off.numel() != 2 * n_g + 1:
+        raise ValueError(f"out_offsets has {off.numel()} entries, {n_g} pairs in two directions need {2 * n_g + 1}")
+    counts = off.diff().to(d2.device)
+    seg = torch.repeat_interleave(torch.arange(2 * n_g, device=d2.device), counts)
+    within = torch.bincount(seg[d2 <= tolerance2], minlength=2 * n_g).cpu().numpy() if n_g else np.zeros(0, np.int64)
+    v, order = torch.sort(d2, stable=True)
+    v = v[torch.sort(seg[order], stable=True)[1]]            # ascending inside every segment
+    # numpy's square root is the correctly rounded one at every length of the array (compare.thickness_columns)
+    d = np.sqrt(v.cpu().numpy())
+    off = off.numpy()
+    n = np.diff(off)
+    out = {k: np.full(n_g, np.nan) for k in ("hausdorff", "hausdorff95", "assd", "nsd")}
+    for k in range(n_g):
+        ng, npr = int(n[k]), int(n[n_g + k])
+        if ng == 0 or npr == 0:
+            continue
+        dg, dp = d[off[k]:off[k + 1]], d[off[n_g + k]:off[n_g + k + 1]]
+        out["hausdorff"][k] = max(dg[-1], dp[-1])
+        out["hausdorff95"][k] = max(dg[nearest_rank(ng)], dp[nearest_rank(npr)])
+        out["assd"][k] = (np.cumsum(dg)[-1] + np.cumsum(dp)[-1]) / (ng + npr)
+        out["nsd"][k] = int(within[k] + within[n_g + k]) / (ng + npr)
+    res = {k: torch.from_numpy(a) for k, a in out.items()}
+    res["gt_surface_voxels"] = torch.from_numpy(n[:n_g].astype(np.int64))
+    res["pred_surface_voxels"] = torch.from_numpy(n[n_g:].astype(np.int64))
+    return res
 
 
 def mask_to_bbox(mask: Tensor) -> Tuple[Tensor, Tensor]:
