@@ -1054,6 +1054,42 @@ int sk_stitch_walk_host(const int32_t* offsets_host, int n_planes, const int32_t
                         int32_t* max_label_host);
 
 /* ------------------------------------------------------------------------ *
+ * Connected pieces of a label volume (ABI 20; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* sk_label_components: the connected pieces of every value of an (X, Y, Z) int32 volume at once.  Two voxels are joined
+ * when they are neighbours and hold the same value.  which = 1 labels the positive values at `connectivity` 6, 18 or 26
+ * (the 3, 9 or 13 backward neighbours of a voxel); which = 0 labels the zero voxels, always 6-connected (connectivity
+ * must still be one of the three).  Voxels of the other kind -- and negative values in either mode -- get piece 0.
+ * ranks: X Y Z int32, the piece of every voxel, 1 .. P in the raster (C) order of the pieces' first voxels over the
+ * whole volume: for a one-value mask scipy.ndimage.label's numbering.  *n_components = P (device).  parent: X Y Z int32
+ * of scratch that ends as the voxel index of the first voxel of every voxel's piece, -1 for the other kind.  workspace:
+ * the query's bytes (0 for extents the entry point refuses).  Extents must be positive and X Y Z < 2^31: parents are
+ * int32 voxel indices.  Stream-ordered, no allocation, no workgroup waits for another; the result is the same on every
+ * run. */
+size_t sk_label_components_workspace_bytes(int X, int Y, int Z);
+int sk_label_components(const int32_t* labels, int X, int Y, int Z, int connectivity, int which, int32_t* parent,
+                        int32_t* ranks, int32_t* n_components, void* workspace, size_t workspace_bytes, void* stream);
+
+/* sk_component_table: one int64 row per piece of `piece` (the ranks above, pieces 1 .. P; other values are skipped) from
+ * one pass with integer atomics only, so the rows are the same on every run.  rows: P x sk_component_table_row_values()
+ * (= 6), written whole by the entry point:
+ *   [0] value             the value of `labels` the piece's voxels hold (0 for a zero piece)
+ *   [1] voxels            [2] first_voxel  the smallest voxel index (x Y + y) Z + z; -1 for a row no voxel names
+ *   [3] border_bits       bit 0 / 1: a voxel at x = 0 / X - 1, bit 2 / 3: y = 0 / Y - 1, bit 4 / 5: z = 0 / Z - 1
+ *   [4] min_neighbour_id  [5] max_neighbour_id  zero pieces only: the smallest and the largest positive value among the
+ *                         6-neighbours of the piece's voxels, both 0 when there is none; equal when the pocket touches
+ *                         exactly one id.  0 for the pieces of positive values.
+ * P == 0 returns SK_OK and writes nothing. */
+int sk_component_table_row_values(void);
+int sk_component_table(const int32_t* labels, const int32_t* piece, int X, int Y, int Z, int P, int64_t* rows, void* stream);
+
+/* out[v] = lut[piece[v]] for n voxels (0 where piece[v] is outside [0, n_lut)); with only_pieces != 0 only the voxels
+ * with piece[v] > 0 are written and the others keep what `out` holds: the fill step of a clean-up. */
+int sk_apply_piece_lut(const int32_t* piece, const int32_t* lut, int n_lut, int32_t* out, int64_t n, int only_pieces,
+                       void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

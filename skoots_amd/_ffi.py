@@ -201,6 +201,11 @@ _SIGS = {
     "sk_plane_overlaps_workspace_bytes": (sz, [i32]),
     "sk_plane_overlaps": (i32, [vp, i32, i32, i32, i64, i64, i64, vp, i32, vp, vp, sz, vp]),
     "sk_stitch_walk_host": (i32, [ip, i32, ip, i64, ip, ip]),
+    "sk_label_components_workspace_bytes": (sz, [i32, i32, i32]),
+    "sk_label_components": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "sk_component_table_row_values": (i32, []),
+    "sk_component_table": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "sk_apply_piece_lut": (i32, [vp, vp, i32, vp, i64, i32, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

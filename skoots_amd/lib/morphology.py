@@ -2,7 +2,9 @@
 (reference: skoots/lib/morphology.py:155-175 ``binary_dilation``, :178-199 ``binary_dilation_2d``), and the Lee
 thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skeletonize``, ``thin_objects``) with the
 skeletons read as graphs (``skeleton_graph``); ``label_edt`` is the exact Euclidean distance
-transform of every instance of a label volume, which the reference does not have."""
+transform of every instance of a label volume, which the reference does not have, and
+``label_components`` the connected pieces of every instance at once, which it does not have
+either."""
 from __future__ import annotations
 
 import ctypes as C
@@ -169,6 +171,87 @@ def label_edt(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, row
                                      int(bool(closed)), _ffi.ptr(dist2), _ffi.ptr(scratch), _ffi.ptr(row_max),
                                      _ffi.stream_ptr(dev)))
     return dist2, row_max.view(torch.float64)
+
+
+N_PIECE_COLS = 6            # int64 values per piece of sk_component_table (checked against the library below)
+PIECE_COLUMNS = ("value", "voxels", "first_voxel", "border_bits", "min_neighbour_id", "max_neighbour_id")
+CONNECTIVITIES = (6, 18, 26)
+MAX_PIECE_VOXELS = 2 ** 31  # sk_label_components: parents are int32 voxel indices
+
+
+def check_piece_shape(shape) -> None:
+    """The library's guard, applied before anything touches the device."""
+    X, Y, Z = (int(v) for v in shape)
+    if X * Y * Z >= MAX_PIECE_VOXELS:
+        raise ValueError(f"a volume of shape {(X, Y, Z)} is too large to label: X*Y*Z must stay below 2^31, the parents "
+                         "of the labelling are int32 voxel indices")
+
+
+def _label_pieces(a: Tensor, connectivity: int, which: int) -> Tuple[Tensor, Tensor]:
+    """``sk_label_components`` + ``sk_component_table`` on the contiguous int32 device volume ``a``: (piece map, rows)."""
+    assert _ffi.lib.sk_component_table_row_values() == N_PIECE_COLS
+    X, Y, Z = (int(v) for v in a.shape)
+    dev = a.device
+    piece = torch.zeros((X, Y, Z), dtype=torch.int32, device=dev)
+    if piece.numel() == 0:
+        return piece, torch.zeros((0, N_PIECE_COLS), dtype=torch.int64, device=dev)
+    parent = torch.empty_like(piece)
+    nbytes = int(_ffi.lib.sk_label_components_workspace_bytes(X, Y, Z))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    _ffi.check(_ffi.lib.sk_label_components(_ffi.ptr(a), X, Y, Z, connectivity, which, _ffi.ptr(parent), _ffi.ptr(piece),
+                                            _ffi.ptr(count), _ffi.ptr(work), C.c_size_t(nbytes), _ffi.stream_ptr(dev)))
+    P = int(count.item())
+    table = torch.empty((P, N_PIECE_COLS), dtype=torch.int64, device=dev)
+    _ffi.check(_ffi.lib.sk_component_table(_ffi.ptr(a), _ffi.ptr(piece), X, Y, Z, P, _ffi.ptr(table),
+                                           _ffi.stream_ptr(dev)))
+    return piece, table
+
+
+def label_components(labels: Tensor, connectivity: int = 6, background: bool = False, rows=None) -> Tuple[Tensor, Tensor]:
+    """The connected pieces of every instance of an (X, Y, Z) or (1, X, Y, Z) integer device tensor at once:
+    ``(piece_map, table)``, both on the device (the reference has no counterpart).
+
+    Two voxels belong to one piece when a chain of neighbours of the same id joins them, at ``connectivity`` 6, 18 or 26.
+    ``piece_map`` (X, Y, Z) int32 numbers the pieces of all ids together, 1..P by their first voxel in C order over the
+    whole volume, and is 0 on the background: for a mask of one id it is ``scipy.ndimage.label(mask,
+    generate_binary_structure(3, k))[0]``.  ``table`` (P, 6) int64 has one row per piece, ``PIECE_COLUMNS``: the id, its
+    voxels, its first voxel ``(x Y + y) Z + z``, six bits for the faces of the volume it touches (x low, x high, y low,
+    y high, z low, z high) and two zeros.
+
+    ``background=True`` labels the zero voxels instead, always 6-connected whatever ``connectivity`` says (as
+    ``scipy.ndimage.binary_fill_holes`` sees the background); the last two columns are then the smallest and the largest
+    positive id among the 6-neighbours of the piece's voxels, both 0 without one: a piece that touches no face and has
+    ``min == max`` is a hole of that id.
+
+    The numbers are exact and the same on every run.  Negative values raise ``ValueError``; ``X*Y*Z`` must stay below
+    2^31.  ``rows`` is ``validate.lib.id_rows(labels)`` when the caller already has it; sparse or huge ids go through its
+    relabelled volume, and the ``value`` column still names the ids themselves."""
+    from ..validate.lib import _as_volume, _id_rows
+    if connectivity not in CONNECTIVITIES or isinstance(connectivity, bool):
+        raise ValueError(f"connectivity must be one of {CONNECTIVITIES}, got {connectivity!r}")
+    if rows is None:
+        x = _as_volume(labels, "labels")
+        check_piece_shape(x.shape)
+        if x.numel() and int(x.min().item()) < 0:
+            raise ValueError(f"labels holds the negative value {int(x.min().item())}: instance ids are positive and 0 is "
+                             "the background")
+        rows = _id_rows(x)
+    else:
+        x, rows = rows
+        check_piece_shape(x.shape)
+    dev = x.device
+    if rows is None:                                         # no positive id: one call on the zeros themselves
+        a, ids, max_id = torch.zeros(tuple(x.shape), dtype=torch.int32, device=dev), None, 0
+    else:
+        a, ids, _, max_id = rows
+    piece, table = _label_pieces(a, int(connectivity), 0 if background else 1)
+    if ids is not None and int(ids[-1].item()) != max_id and table.shape[0]:
+        # _id_rows relabelled the mask: `a` holds the rows 1..N, and the columns that name ids hold rows
+        back = torch.cat((ids.new_zeros(1), ids))
+        for col in (0, 4, 5):
+            table[:, col] = back[table[:, col]]
+    return piece, table
 
 
 def skeletonize(image: Tensor) -> Tensor:

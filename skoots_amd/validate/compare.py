@@ -56,6 +56,8 @@ THICKNESS_MODES = (None, "open", "closed")
 MESH_COLUMNS = "mesh_vertices,mesh_triangles"            # appended with --mesh
 MESH_CLOSED_COLUMNS = "euler_characteristic"             # ... and behind them with --mesh closed
 MESH_MODES = (None, "open", "closed")
+PIECES_COLUMNS = "pieces,largest_piece_voxels"           # appended with --pieces
+PIECES_MODES = (None, 6, 18, 26)
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -215,9 +217,26 @@ def mesh_columns(counts: Tensor, closed: bool) -> Dict[str, Tensor]:
     return out
 
 
+def pieces_columns(table: Tensor, ids) -> Dict[str, Tensor]:
+    """The piece columns (int64 host tensors, one row per id of ``ids``, ascending) from the (P, 6) table of
+    ``lib.morphology.label_components``: ``pieces``, the connected pieces the id is in, and ``largest_piece_voxels``,
+    the voxels of the largest of them.  An id with ``pieces > 1`` is not one body, and what the other columns say of
+    its skeleton, radius or surface distances describes no physical object."""
+    t = table.cpu().numpy().astype(np.int64).reshape(-1, 6)
+    ids = np.asarray(ids.cpu() if isinstance(ids, Tensor) else ids, dtype=np.int64).reshape(-1)
+    row = np.searchsorted(ids, t[:, 0])
+    if t.shape[0] and (row.max(initial=0) >= ids.size or not np.array_equal(ids[row], t[:, 0])):
+        raise ValueError("the table names an id that is not among ids")
+    count = np.zeros(ids.size, np.int64)
+    largest = np.zeros(ids.size, np.int64)
+    np.add.at(count, row, 1)
+    np.maximum.at(largest, row, t[:, 1])
+    return {"pieces": torch.from_numpy(count), "largest_piece_voxels": torch.from_numpy(largest)}
+
+
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
                        skeleton: bool = False, thickness: Optional[str] = None,
-                       mesh: Optional[str] = None) -> Dict[str, Tensor]:
+                       mesh: Optional[str] = None, pieces: Optional[int] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -249,7 +268,13 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
 
     ``mesh="open"`` or ``"closed"`` adds ``mesh_vertices`` and ``mesh_triangles`` (int64), the size of the mesh that
     ``lib.instance_meshes`` would return, from its count pass, and in closed mode ``euler_characteristic`` (int64;
-    ``mesh_columns``)."""
+    ``mesh_columns``).
+
+    ``pieces=6``, ``18`` or ``26`` adds ``pieces`` and ``largest_piece_voxels`` (int64): the connected pieces of every
+    id at that connectivity and the size of the largest, from ``lib.morphology.label_components`` (``pieces_columns``,
+    DESIGN.md §26)."""
+    if pieces not in PIECES_MODES or isinstance(pieces, bool):
+        raise ValueError(f"pieces must be one of {PIECES_MODES}, got {pieces!r}")
     if mesh not in MESH_MODES:
         raise ValueError(f"mesh must be one of {MESH_MODES}, got {mesh!r}")
     if surface not in SURFACE_MODES:
@@ -282,6 +307,9 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     if mesh is not None:
         _, counts = instance_mesh_counts(x, mesh == "closed", rows)
         out.update({k: v.to(sums.device) for k, v in mesh_columns(counts, mesh == "closed").items()})
+    if pieces is not None:
+        from ..lib.morphology import label_components
+        out.update({k: v.to(sums.device) for k, v in pieces_columns(label_components(x, pieces, rows=rows)[1], ids).items()})
     return out
 
 
@@ -415,7 +443,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                min_voxels: int = 1, mesh_cells: Optional[Tensor] = None,
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
-               mesh_closed: bool = False) -> str:
+               mesh_closed: bool = False, piece_table: Optional[Tensor] = None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -426,7 +454,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     skeleton_radius_max``, in that order behind everything else; an instance alone in the volume in open mode prints
     ``inf``.  With ``mesh_counts`` (the (N, 2) counts of ``instance_mesh_counts``) ``mesh_vertices,mesh_triangles``
     follow behind all of those, and ``euler_characteristic`` behind them when ``mesh_closed`` says the counts are those
-    of closed mode."""
+    of closed mode.  With ``piece_table`` (the (P, 6) table of ``label_components``) ``pieces,largest_piece_voxels``
+    follow behind everything else; without it the text is byte for byte what it was before they existed."""
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
@@ -441,6 +470,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     if mesh_counts is not None:
         d.update(mesh_columns(mesh_counts, bool(mesh_closed)))
         mesh_names = (MESH_COLUMNS + ("," + MESH_CLOSED_COLUMNS if mesh_closed else "")).split(",")
+    if piece_table is not None:
+        d.update(pieces_columns(piece_table, ids))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
@@ -448,7 +479,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + SKELETON_COLUMNS if skeleton_graph is not None else "") +
              ("," + THICKNESS_COLUMNS if max_dist2 is not None else "") +
              ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") +
-             "".join("," + k for k in mesh_names) + "\n"]
+             "".join("," + k for k in mesh_names) + ("," + PIECES_COLUMNS if piece_table is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -465,6 +496,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         if skeleton_radius is not None:
             cells += [repr(d[k][i]) for k in SKELETON_RADIUS_COLUMNS.split(",")]
         cells += [d[k][i] for k in mesh_names]
+        if piece_table is not None:
+            cells += [d[k][i] for k in PIECES_COLUMNS.split(",")]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -507,6 +540,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                              "given)")
     parser.add_argument("--mesh-ids", type=int, nargs="+", default=None, metavar="ID",
                         help="With --save-meshes: write only these instances")
+    parser.add_argument("--pieces", type=int, default=None, choices=(6, 18, 26),
+                        help="Append " + PIECES_COLUMNS + ": the connected pieces of every id at this connectivity and "
+                             "the voxels of the largest (an id in several pieces is not one body)")
     parser.add_argument("--ground-truth", type=str, default=None, metavar="GT",
                         help="Also write <mask>_compare.csv: the mask is a prediction and GT (.tif or .npy of the same "
                              "shape) the ground truth; one row per ground-truth instance with the predicted instance it "
@@ -564,8 +600,12 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
                                                   volume[0] if args.skeleton else None)[1:]
         skel_radius = skel[0] if skel else None
     mesh_counts = instance_mesh_counts(dev_mask, args.mesh == "closed", rows)[1] if args.mesh else None
+    piece_table = None
+    if args.pieces:
+        from ..lib.morphology import label_components
+        piece_table = label_components(dev_mask, args.pieces, rows=rows)[1]
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
-                      max_d2, skel_radius, mesh_counts, args.mesh == "closed")
+                      max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
