@@ -199,8 +199,11 @@ typedef struct sk_conv_src {
  * second optionally nearest-upsampled x2 (torch.cat([skip, interpolate(x)]) never
  * materialised).  ksize 2: stride 2, no pad.  ksize 1: pointwise.  weight: packed by
  * sk_conv3d_pack_weight_host; bias (cout) fp32; out (B, ox, oy, oz, cout) fp16 raw.
- * gn_partial: (B, sk_conv3d_num_blocks, cout/4, 2) fp32 per-block (sum, sumsq) of
- * the fp32 accumulators per channel quad, or NULL.  zero_page: 4 KiB; bytes [0, 1024) must
+ * gn_partial: (B, sk_conv3d_num_blocks, cout/4, 2) fp32 per-block (sum, sumsq) per channel quad, or NULL.  What is
+ * summed: ksize 3 (conv3_px_kernel, conv3_m16_kernel, conv3_kernel) the values as STORED, i.e. the results rounded to 16
+ * bits -- the statistics of the tensor the GroupNorm pass reads; ksize 1 / 2 (gather_gemm_kernel, down2_act_kernel) the
+ * fp32 accumulators; sk_conv3d_split, sk_conv3d_box_split, sk_conv3d_mix8 and the split / mix8 down convs the fp32
+ * accumulators for every ksize (tests/test_hip_conv16_exact.py tells the two apart).  zero_page: 4 KiB; bytes [0, 1024) must
  * be zero and stay zero (source of the halo / padding lanes of the LDS-DMA), bytes
  * [2048, 3072) are write-only scratch for the ksize-3 kernel's masked store lanes.  Required for ksize 3 and for
  * the LDS-staged ksize-2 kernel ((cin, cout) = (32, 64) | (64, 128)).  A RAW source (affine != NULL) is activated

@@ -27,8 +27,8 @@
 //     upsampled tensors is two chunks from two sources, never materialised);
 //   * the epilogue adds the bias, stores fp16 raw outputs (transposed through a per-wave LDS
 //     pad into whole 64-byte voxel lines, 16 B per lane) and
-//     accumulates per-channel-quad (sum, sumsq) of the fp32 accumulators for the
-//     GroupNorm that follows; per-block partials are reduced in a fixed order by
+//     accumulates per-channel-quad (sum, sumsq) for the GroupNorm that follows (fp16 3x3x3 kernels: of the values as stored,
+//     16 bits; split / mix8 forms and the ksize 1 / 2 kernels: of the fp32 accumulators); per-block partials are reduced in a fixed order by
 //     sk_groupnorm_finalize (deterministic, no float atomics).
 #include <stdlib.h>
 
