@@ -1093,6 +1093,46 @@ int sk_apply_piece_lut(const int32_t* piece, const int32_t* lut, int n_lut, int3
                        void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Nearest-instance transform (ABI 21; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* sk_nearest_label: for every voxel of an (X, Y, Z) int32 volume, the squared distance to the nearest voxel of any
+ * instance and that instance's row: what utils/grow.py grows instances with.  labels, lut, max_id, N and wx, wy, wz are
+ * those of sk_label_edt; r(v) is the row of voxel v (1 .. N, 0 for background and unlisted ids) and a site is a voxel
+ * with r > 0.  For a voxel p and a site q
+ *   value(p, q) = fl(wx dx^2 + fl(wy dy^2 + wz dz^2)),   dx = px - qx, ...
+ * every square an exact integer in double, every product and sum rounded once (no fused multiply-add; w (d d)), and
+ *   D2(p) = min over sites q of value(p, q).
+ * nearest(p) is the row of the site the nested minimum chooses when it is taken as three passes, along z, then y, then
+ * x: each pass minimises fl(w d^2 + g_prev(q)) along its axis (g_prev = 0 on a site and +inf elsewhere before the z
+ * pass) and, where several positions give the same value, keeps the smallest coordinate.  A site has D2 = 0 and
+ * nearest = r(p).  Rounding is monotone, so the passes give D2 bit for bit; the implementation walks outward from the
+ * voxel and stops where nothing farther can win or tie.
+ * limit2 (+inf allowed) bounds the search: where D2(p) <= limit2 the outputs are dist2[p] = D2(p) and nearest[p];
+ * elsewhere -- and where no site exists, or D2 is not finite -- dist2[p] = +inf and nearest[p] = 0.  A pass reads at
+ * most 2 floor(sqrt(limit2 / w)) positions per voxel; with limit2 = +inf it is O(extent) per voxel, the price of
+ * exactness without a lower envelope.  where (X Y Z bytes, or NULL = every voxel): a voxel with where = 0 that is not a
+ * site gets +inf and 0 without a search.  where never restricts which sites count: distances are Euclidean, through
+ * anything, not geodesic.
+ * dist2, scratch_d2: X Y Z doubles each; nearest, scratch_row: X Y Z int32 each; four distinct buffers.  The passes go
+ * (dist2, nearest) -> (scratch_d2, scratch_row) -> (dist2, nearest).  Checked before anything is launched or written:
+ * extents, N and max_id not negative, every extent <= 2^26, X Y Z < 2^62, the weights finite and > 0, limit2 not NaN
+ * and >= 0, no NULL pointer but where, pointers aligned to their elements, the four buffers distinct.  An empty volume
+ * returns SK_OK and writes nothing; N == 0 fills dist2 with +inf and nearest with 0.  The outputs are the same on every
+ * run.
+ * sk_nearest_label_pass is one of the three passes, under the same checks: axis 2 (z; the sources are not read and may
+ * be NULL) writes the nearest site along z of every voxel; axis 1 and 0 minimise fl(w d^2 + src_d2(q)) along the axis
+ * and carry src_row of the chosen position, a site keeping (0, r(p)).  Every pass bounds its walk by limit2; only axis
+ * 0 reads where and turns values above limit2 into (+inf, 0).  sk_nearest_label is the passes 2, 1, 0 with wz, wy, wx;
+ * tools/bench_grow.py times them one by one. */
+int sk_nearest_label_pass(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, int axis,
+                          double w, double limit2, const double* src_d2, const int32_t* src_row, const uint8_t* where,
+                          double* dst_d2, int32_t* dst_row, void* stream);
+int sk_nearest_label(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, double wx,
+                     double wy, double wz, double limit2, const uint8_t* where, double* dist2, int32_t* nearest,
+                     double* scratch_d2, int32_t* scratch_row, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

@@ -206,6 +206,9 @@ _SIGS = {
     "sk_component_table_row_values": (i32, []),
     "sk_component_table": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "sk_apply_piece_lut": (i32, [vp, vp, i32, vp, i64, i32, vp]),
+    "sk_nearest_label_pass": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "sk_nearest_label": (i32, [vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp,
+                               vp, vp, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

@@ -4,7 +4,7 @@ thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skel
 skeletons read as graphs (``skeleton_graph``); ``label_edt`` is the exact Euclidean distance
 transform of every instance of a label volume, which the reference does not have, and
 ``label_components`` the connected pieces of every instance at once, which it does not have
-either."""
+either, nor ``nearest_label``, the nearest instance of every voxel and its distance."""
 from __future__ import annotations
 
 import ctypes as C
@@ -171,6 +171,68 @@ def label_edt(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, row
                                      int(bool(closed)), _ffi.ptr(dist2), _ffi.ptr(scratch), _ffi.ptr(row_max),
                                      _ffi.stream_ptr(dev)))
     return dist2, row_max.view(torch.float64)
+
+
+def nearest_label(labels: Tensor, spacing=(1.0, 1.0, 1.0), max_distance=None, where=None, rows=None) -> Tuple[Tensor, Tensor]:
+    """The nearest instance of every voxel of an (X, Y, Z) or (1, X, Y, Z) integer device tensor at the voxel spacing
+    ``spacing`` (sx, sy, sz): ``(nearest_id (X, Y, Z) int64, dist2 (X, Y, Z) float64)``, both on the device (DESIGN.md
+    section 27; the reference has no counterpart).
+
+    ``dist2`` is the squared distance between voxel centres to the nearest voxel of a positive id, 0 on such a voxel
+    itself, and ``nearest_id`` that voxel's id.  The value is ``fl(wx dx^2 + fl(wy dy^2 + wz dz^2))`` with
+    ``wx = sx * sx`` formed in float64 here, minimised exactly (include/skoots_hip.h: sk_nearest_label); among voxels at
+    the same value the one the three passes z, y, x reach with the smallest coordinate wins, so the result is the same on
+    every run.  At integer-valued spacings ``dist2.sqrt()`` equals ``scipy.ndimage.distance_transform_edt(labels == 0,
+    sampling=spacing)`` bit for bit; scipy's nearest voxel lies at the same distance but need not be the same voxel.
+
+    ``max_distance`` (``None`` = no limit, or a non-negative finite float d) bounds the search at ``dist2 <= fl(d d)``:
+    beyond it, and in a volume without a positive id, ``dist2`` is ``inf`` and ``nearest_id`` 0.  Without a limit a voxel
+    costs as many reads as the volume is long, with one about ``2 d / spacing`` per axis.  ``where`` (bool or integer
+    tensor of the volume's shape on the same device, non-zero = wanted) restricts which voxels are answered: the others
+    get ``inf`` and 0 unless they hold an id themselves.  It never restricts which voxels count as nearest: distances
+    are Euclidean, through anything, not geodesic.  ``rows`` is ``validate.lib.id_rows(labels)`` when the caller
+    already has it; sparse or huge ids go through its relabelled volume, and ``nearest_id`` still names the ids."""
+    from ..validate.lib import id_rows
+    x, rows = id_rows(labels) if rows is None else rows
+    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
+    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
+        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
+    limit2 = max_distance_squared(max_distance)
+    X, Y, Z = (int(v) for v in x.shape)
+    if max(X, Y, Z) > 2 ** 26 or X * Y * Z >= 2 ** 62:
+        raise ValueError(f"a volume of shape {(X, Y, Z)} is too large for the nearest-instance transform: every extent "
+                         "must stay at or below 2^26 and X*Y*Z below 2^62")
+    dev = x.device
+    if where is not None:
+        if not isinstance(where, Tensor) or where.device != dev or where.is_floating_point() or where.is_complex():
+            raise ValueError("where must be a bool or integer tensor on the device of labels")
+        where = where[0] if where.ndim == 4 and where.shape[0] == 1 else where
+        if tuple(where.shape) != (X, Y, Z):
+            raise ValueError(f"where must have the volume's shape {(X, Y, Z)}, got {tuple(where.shape)}")
+        where = (where != 0).to(torch.uint8).contiguous()
+    dist2 = torch.full((X, Y, Z), float("inf"), dtype=torch.float64, device=dev)
+    if rows is None or dist2.numel() == 0:
+        return torch.zeros((X, Y, Z), dtype=torch.int64, device=dev), dist2
+    a, ids, lut, max_id = rows
+    N = int(ids.numel())
+    nearest = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
+    scratch_d2, scratch_row = torch.empty_like(dist2), torch.empty_like(nearest)
+    _ffi.check(_ffi.lib.sk_nearest_label(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, s[0] * s[0], s[1] * s[1],
+                                         s[2] * s[2], limit2, _ffi.ptr(where), _ffi.ptr(dist2), _ffi.ptr(nearest),
+                                         _ffi.ptr(scratch_d2), _ffi.ptr(scratch_row), _ffi.stream_ptr(dev)))
+    return torch.cat((ids.new_zeros(1), ids))[nearest.long()], dist2
+
+
+def max_distance_squared(max_distance) -> float:
+    """``limit2`` of ``sk_nearest_label``: ``inf`` for ``None``, else ``fl(d d)`` of a non-negative finite number."""
+    if max_distance is None:
+        return float("inf")
+    if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
+        raise ValueError(f"max_distance must be None or a non-negative finite number, got {max_distance!r}")
+    d = float(max_distance)
+    if not 0 <= d < float("inf"):
+        raise ValueError(f"max_distance must be None or a non-negative finite number, got {max_distance!r}")
+    return d * d
 
 
 N_PIECE_COLS = 6            # int64 values per piece of sk_component_table (checked against the library below)
