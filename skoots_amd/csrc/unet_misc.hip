@@ -19,7 +19,9 @@ typedef t16 half8 __attribute__((ext_vector_type(8)));
 // run twice (statistics, then apply): see stem_kernel.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef t16 half4v __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int kStemMaxB = 64;   // tiles per launch (the pipeline runs 64: +1 % end to end over 32) (origins travel by value in the kernel arguments)
 
@@ -72,8 +74,11 @@ __global__ void __launch_bounds__(256) stem_norm_kernel(StemArgs a) {
 // Weights are split w = hi + lo (two fp16 values, 22 significant bits) and the input is exactly
 // fp16, so the products are exact and the sums match an fp32 conv to ~1e-7 relative.
 // y rows of one x plane per workgroup: up to 150, within 40 KiB of LDS for the three staged planes.  The per-block
-// prologue (weight split, tap offsets, staging latency) is amortised over rows*Zt/32 tiles; statistics pass per 8
-// tiles of 300x300x20, rocprofv3: 60 rows 189 us, 100: 165, 150: 151, 300: 149 (apply pass 332 / 327 / 324 / 338).
+// prologue (weight split, operand offsets and selectors, staging latency) is amortised over rows*Zt/32 tiles; statistics
+// pass per 8 tiles of 300x300x20, rocprofv3: 60 rows 189 us, 100: 165, 150: 151, 300: 149 (apply pass 332 / 327 / 324 / 338).
+// (Those four timings are from before the operand was built from dword reads -- since then 0.97 -> 0.68 and 1.64 -> 1.31 ms
+// per 64 tiles at 150 rows; the other row counts have not been measured again, and the grid is part of the ABI through
+// sk_conv3d_stem_num_blocks.)
 static int stem_rows(int Yt, int Zt) {
     int r = (40 * 1024) / (3 * (Zt + 2) * (int)sizeof(t16)) - 2;
     if (r > 150) r = 150;
@@ -97,7 +102,7 @@ static int stem_rows(int Yt, int Zt) {
 // activation is stored as a split pair [hi (32) | lo (32)] per voxel (value = hi + lo, precision "split"); 4: as 3, but the
 // line is [hi fp16 (32) | x8 (32) | lo8 (32)] -- e4m3(16 x) and e4m3(2^15 (x - hi)) -- for a precision "mix8" consumer
 template <int MODE>
-__global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
+__global__ void __launch_bounds__(256, 2) stem_kernel(StemArgs a) {
     constexpr bool STATS = MODE == 0 || MODE == 2;
     constexpr int kOutC = (MODE == 3 || MODE == 4) ? 64 : 32;   // halves per output voxel line
     __shared__ float red[4 * 16];
@@ -149,11 +154,9 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
         }
     }
     __syncthreads();
-    const t16* ls = reinterpret_cast<const t16*>(stem_lds);
 
     // A operands: lane holds W[cout = l&31][tap = 16m + 8h + j], j = 0..7, m = 0,1 (tap >= 27: 0)
     half8 whi[2], wlo[2];
-    int toff[2][8];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -163,9 +166,47 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
             t16 hi = (t16)wv;
             whi[m][j] = hi;
             wlo[m][j] = (t16)(wv - (float)hi);
-            int tt = tap < 27 ? tap : 0;  // any valid address: its weight is zero
-            toff[m][j] = (tt / 9) * seg_halves + ((tt / 3) % 3) * pz + tt % 3;
         }
+    // B operands (the patch): taps 8h' .. 8h'+7 of a lane are a run of the nine (dx, dy) rows' halves z, z+1, z+2.  Every
+    // staged row starts on a dword (the pitch pz and the plane pitch are even -- check_stem_tile requires Zt even -- and so is
+    // the static LDS in front), and the voxel index 32 t + col has the parity of z (Zt is even): with ze = z - (col & 1) the
+    // three halves lie in the two ALIGNED dwords [ze, ze+2), [ze+2, ze+4) of the row, at half p = (col & 1) + dz.  Operand
+    // dword k (taps 2k, 2k+1 of the run) then comes from two of those dwords: both of one row (dz 0,1: "P01"; dz 1,2: "P12"),
+    // or the upper dword of one row and the lower of the next (dz 2 | dz 0: "C") -- one v_perm_b32 whose byte selector is a
+    // per-lane constant (h, col & 1).  The dwords are read where both lane halves can name them by the same register:
+    //   m = 0   reg   h = 0 (taps 0..7)   h = 1 (taps 8..15)       operand dword: sources     h = 0   h = 1
+    //           R0    row0.lo             row2.hi                  k = 0: (R0, R1)            P01     C
+    //           R1    row0.hi             row3.lo                  k = 1: (R1, R2)            C       P12
+    //           R2    row1.lo             row3.hi                  k = 2: (R3, R4)            P12     P01
+    //           R3,R4 row1.lo, .hi        row4.lo, .hi  (one read) k = 3: (R5, R6)            P01     C
+    //           R5    row2.lo             row4.hi
+    //           R6    row2.hi             row5.lo
+    //   m = 1   Q0,Q1,Q2 = rows 5, 6, 7 (h = 0, taps 16..23) | row 8 three times (h = 1, taps 24..26; 27..31 carry zero weights
+    //           and read staged, finite data); k = 0: Q0 (P12 | P01), 1: Q1 (P01 | dz 2 twice), 2: (Q1.hi, Q2.lo) C, 3: Q2 P12.
+    // 9 LDS reads (4 of them two-dword) and 8 v_perm_b32 per 32-voxel tile, against 16 two-byte gathers and their packing.
+    const int par = col & 1;
+    const auto rowB = [&](int r) { return 2 * ((r / 3) * seg_halves + (r % 3) * pz); };   // byte offset of row (dx, dy) = divmod(r, 3)
+    const auto sel2 = [](int b0, int b1) { return (unsigned)(b0 | ((b0 + 1) << 8) | (b1 << 16) | ((b1 + 1) << 24)); };
+    const unsigned sP01 = sel2(2 * par, 2 * par + 2), sP12 = sel2(2 * par + 2, 2 * par + 4), sC = sel2(2 * par, 2 * par + 4);
+    int aoff[6], qoff[3];      // byte offsets of R0, R1, R2, R3|R4, R5, R6 and Q0..Q2 from the tile dword of tap (0,0,0)
+    aoff[0] = h ? rowB(2) + 4 : rowB(0);
+    aoff[1] = h ? rowB(3) : rowB(0) + 4;
+    aoff[2] = h ? rowB(3) + 4 : rowB(1);
+    aoff[3] = h ? rowB(4) : rowB(1);
+    aoff[4] = h ? rowB(4) + 4 : rowB(2);
+    aoff[5] = h ? rowB(5) : rowB(2) + 4;
+    qoff[0] = h ? rowB(8) : rowB(5);
+    qoff[1] = h ? rowB(8) : rowB(6);
+    qoff[2] = h ? rowB(8) : rowB(7);
+    unsigned psel[2][4];
+    psel[0][0] = h ? sC : sP01;
+    psel[0][1] = h ? sP12 : sC;
+    psel[0][2] = h ? sP01 : sP12;
+    psel[0][3] = h ? sC : sP01;
+    psel[1][0] = h ? sP01 : sP12;
+    psel[1][1] = h ? sel2(2 * par + 4, 2 * par + 4) : sP01;
+    psel[1][2] = sC;
+    psel[1][3] = sP12;
     f32x16 binit;
     float ga[16], gb[16];
 #pragma unroll
@@ -180,27 +221,55 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
             }
         }
     }
-    float gsum[4] = {0, 0, 0, 0}, gsq[4] = {0, 0, 0, 0};
+    f32x2v gacc[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};   // per channel quad 8q + 4h: (sum y, sum y^2)
     const int nloc = rows * a.Zt;                 // voxels of this workgroup
     const int ntile = (nloc + 31) / 32;
     // statistics pass: two tiles per iteration with independent accumulators -- the four MFMAs of a tile form one
     // dependent chain, and a lone chain leaves the matrix pipe waiting on itself
     constexpr int U = MODE == 0 ? 2 : 1;
+    // a wave's tiles advance by 4 U tiles = 128 U voxels: (row, z) and the byte address of the lane's tile dword are carried
+    // forward -- one division per lane and tile slot here, none in the loop
+    const int adv_y = (128 * U) / a.Zt, adv_z = (128 * U) - adv_y * a.Zt;
+    const int adv_b = 2 * (adv_y * pz + adv_z);
+    int zc[U], wb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = (w + 4 * u) * 32 + col;
+        const int yl = i / a.Zt;
+        zc[u] = i - yl * a.Zt;
+        wb[u] = 2 * (yl * pz + zc[u] - par);
+    }
+    const char* lsb = reinterpret_cast<const char*>(stem_lds);
+    const auto ldw = [&](int off) { return *reinterpret_cast<const unsigned int*>(lsb + off); };
     for (int t0 = w; t0 < ntile; t0 += 4 * U) {
         half8 b0[U], b1[U];
         bool oku[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int i = (t0 + 4 * u) * 32 + col;
-            oku[u] = i < nloc;
-            const int ii = oku[u] ? i : 0;
-            const int yl = ii / a.Zt, z = ii - yl * a.Zt;
-            const t16* p = ls + yl * pz + z;       // tap (0,0,0) in the staged planes
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                b0[u][j] = p[toff[0][j]];
-                b1[u][j] = p[toff[1][j]];
-            }
+            oku[u] = col < nloc - (t0 + 4 * u) * 32;
+            const int base = oku[u] ? wb[u] : 0;   // lanes past nloc read the first voxel's (staged) patch
+            const unsigned r0 = ldw(base + aoff[0]), r1 = ldw(base + aoff[1]), r2 = ldw(base + aoff[2]);
+            const unsigned r3 = ldw(base + aoff[3]), r4 = ldw(base + aoff[3] + 4);
+            const unsigned r5 = ldw(base + aoff[4]), r6 = ldw(base + aoff[5]);
+            const unsigned q0l = ldw(base + qoff[0]), q0h = ldw(base + qoff[0] + 4);
+            const unsigned q1l = ldw(base + qoff[1]), q1h = ldw(base + qoff[1] + 4);
+            const unsigned q2l = ldw(base + qoff[2]), q2h = ldw(base + qoff[2] + 4);
+            u32x4v o0, o1;       // v_perm_b32: selector bytes 0..3 name the SECOND source, 4..7 the first
+            o0[0] = __builtin_amdgcn_perm(r1, r0, psel[0][0]);
+            o0[1] = __builtin_amdgcn_perm(r2, r1, psel[0][1]);
+            o0[2] = __builtin_amdgcn_perm(r4, r3, psel[0][2]);
+            o0[3] = __builtin_amdgcn_perm(r6, r5, psel[0][3]);
+            o1[0] = __builtin_amdgcn_perm(q0h, q0l, psel[1][0]);
+            o1[1] = __builtin_amdgcn_perm(q1h, q1l, psel[1][1]);
+            o1[2] = __builtin_amdgcn_perm(q2l, q1h, psel[1][2]);
+            o1[3] = __builtin_amdgcn_perm(q2h, q2l, psel[1][3]);
+            b0[u] = __builtin_bit_cast(half8, o0);
+            b1[u] = __builtin_bit_cast(half8, o1);
+            // next tile of this slot: z wraps at most once per row step (adv_z < Zt); a wrap skips the row's two frame halves
+            const int zn = zc[u] + adv_z;
+            const bool wrap = zn >= a.Zt;
+            zc[u] = wrap ? zn - a.Zt : zn;
+            wb[u] += wrap ? adv_b + 4 : adv_b;
         }
         f32x16 accu[U];
 #pragma unroll
@@ -217,9 +286,18 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
                 if (oku[u]) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        float v0 = accu[u][4 * q], v1 = accu[u][4 * q + 1], v2 = accu[u][4 * q + 2], v3 = accu[u][4 * q + 3];
-                        gsum[q] += (v0 + v1) + (v2 + v3);
-                        gsq[q] += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
+                        // the scalar form's association (v0 + v1) + (v2 + v3), (v0^2 + v1^2) + (v2^2 + v3^2), bit for bit, in 8
+                        // instructions per quad instead of 12: squares two per instruction (v_pk_mul_f32 on the accumulator's
+                        // own register pairs), four scalar adds, then (sum, sum of squares) as one pair through the last two
+                        // additions.  The empty asm only pins the four scalar sums: without it the compiler packs THEM too and
+                        // pays three v_mov per v_pk_add to line the operands up (statistics pass 0.755 ms per 64 tiles against
+                        // 0.679 in this form)
+                        const f32x2v p01 = {accu[u][4 * q], accu[u][4 * q + 1]}, p23 = {accu[u][4 * q + 2], accu[u][4 * q + 3]};
+                        const f32x2v s01 = p01 * p01, s23 = p23 * p23;
+                        float s_lo = p01[0] + p01[1], q_lo = s01[0] + s01[1], s_hi = p23[0] + p23[1], q_hi = s23[0] + s23[1];
+                        asm("" : "+v"(s_lo), "+v"(q_lo), "+v"(s_hi), "+v"(q_hi));
+                        const f32x2v lo = {s_lo, q_lo}, hi = {s_hi, q_hi};
+                        gacc[q] += lo + hi;
                     }
                 }
         }
@@ -304,7 +382,7 @@ __global__ void __launch_bounds__(256) stem_kernel(StemArgs a) {
     if (STATS) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            float s = gsum[q], ss = gsq[q];
+            float s = gacc[q][0], ss = gacc[q][1];
 #pragma unroll
             for (int m = 16; m > 0; m >>= 1) {
                 s += __shfl_xor(s, m);
