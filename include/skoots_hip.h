@@ -1133,6 +1133,35 @@ int sk_nearest_label(const int32_t* labels, int X, int Y, int Z, const int32_t* 
                      double* scratch_d2, int32_t* scratch_row, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Local thickness (ABI 22; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* sk_local_thickness_paint: the sphere-painting transform behind the local thickness of every instance.  dist2 is the
+ * output D2 of sk_label_edt on an (X, Y, Z) volume (either mode), wx, wy, wz the same weights.  With
+ *   d2(p, c) = fl(wx dx^2 + fl(wy dy^2 + wz dz^2)),   dx = px - cx, ...
+ * every square an exact integer in double, every product and sum rounded once (no fused multiply-add; w (d d)), the
+ * local thickness of a voxel p of an instance is
+ *   T2(p) = max over voxels c of the volume with d2(p, c) < D2(c) of D2(c),
+ * the squared radius of the largest open ball around a voxel centre that holds voxels of p's instance only and holds
+ * p; T2 = 0 on the background.  The inequality is strict: the nearest outside voxel of c lies at D2(c) exactly and is
+ * not in the ball.  D2(c) is the minimum of the same rounded expression over the voxels of other rows, so a ball never
+ * reaches another row and no labels are read; c = p qualifies, so T2 >= D2, and per row max T2 = max D2.
+ * thick2 (X Y Z doubles) must hold a copy of dist2 on entry.  centres holds n_centres flat voxel indices
+ * (x Y + y) Z + z, in any order, repeats allowed; the caller guarantees 0 <= centres[i] < X Y Z (they are not checked
+ * on the device).  For every centre c with finite dist2[c] > 0 the call raises thick2[p] to dist2[c] at every voxel p
+ * with d2(p, c) < dist2[c]; a centre with dist2[c] = +inf (an instance alone in the volume, open mode) or 0 paints
+ * nothing.  After a call, or any sequence of calls, whose centres together cover every voxel with
+ * dist2 > min(wx, wy, wz) -- a smaller ball holds its own centre only -- thick2 is T2.  The maximum is taken with
+ * integer atomics on the bit pattern and does not depend on the order: the same on every run, however the centres are
+ * split over calls.  The work is the sum of the centres' bounding boxes and has no bound of its own; the caller splits
+ * the list (lib/morphology.py: PAINT_BUDGET).
+ * Checked before anything is launched or written: extents not negative and <= 2^26, X Y Z < 2^62, the weights finite
+ * and > 0, n_centres >= 0, no NULL pointer, pointers aligned to 8 bytes, thick2 != dist2.  n_centres == 0 or an empty
+ * volume returns SK_OK and writes nothing. */
+int sk_local_thickness_paint(const double* dist2, int X, int Y, int Z, double wx, double wy, double wz,
+                             const int64_t* centres, int64_t n_centres, double* thick2, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

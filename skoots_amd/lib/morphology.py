@@ -4,7 +4,8 @@ thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skel
 skeletons read as graphs (``skeleton_graph``); ``label_edt`` is the exact Euclidean distance
 transform of every instance of a label volume, which the reference does not have, and
 ``label_components`` the connected pieces of every instance at once, which it does not have
-either, nor ``nearest_label``, the nearest instance of every voxel and its distance."""
+either, nor ``nearest_label``, the nearest instance of every voxel and its distance, nor
+``local_thickness``, the radius of the largest ball inside the instance that holds the voxel."""
 from __future__ import annotations
 
 import ctypes as C
@@ -221,6 +222,88 @@ def nearest_label(labels: Tensor, spacing=(1.0, 1.0, 1.0), max_distance=None, wh
                                          s[2] * s[2], limit2, _ffi.ptr(where), _ffi.ptr(dist2), _ffi.ptr(nearest),
                                          _ffi.ptr(scratch_d2), _ffi.ptr(scratch_row), _ffi.stream_ptr(dev)))
     return torch.cat((ids.new_zeros(1), ids))[nearest.long()], dist2
+
+
+# Box voxels (d2 tests, before the comparison decides) one ``sk_local_thickness_paint`` launch may be asked for.  The
+# work of a call has no bound of its own -- every voxel of a solid 300^3 block is a centre and the block is about 10^12
+# tests -- so ``local_thickness`` splits the centre list into launches of at most this many.  The value is meant to
+# keep a launch well under a second on a device that others share.  It was chosen on an estimate of 3e11 tests per
+# second (a test is a multiply, an add, a compare and an 8-byte load that mostly hits the cache: a tenth of the vector
+# rate) and has since been held against one measurement (tools/bench_local_thickness.py on one MI355X,
+# profiles/local_thickness_bench.json): 3.3e11 box voxels per second on a mask of 1 000 blobs and 2.2e11 on one of
+# 8 192 small balls, both in one launch (5.9 and 26 ms).  The list is split by the upper estimate of the boxes, about
+# twice their exact sum, so a full launch is 25 to 40 ms of such work.  The value stays; the result does not depend on it.
+PAINT_BUDGET = 1 << 34
+
+
+def paint_centres(dist2: Tensor, w) -> Tuple[Tensor, Tensor]:
+    """``(centres, boxes)`` of ``local_thickness``: the flat indices (int64, raster order) of the voxels whose ball
+    holds more than its own centre -- ``dist2`` finite and above ``min(w)`` -- and an upper estimate of each one's
+    clipped bounding box in voxels (int64), which is used for splitting the list only."""
+    X, Y, Z = (int(v) for v in dist2.shape)
+    flat = dist2.reshape(-1)
+    centres = torch.nonzero(torch.isfinite(flat) & (flat > min(w)))[:, 0]
+    D = flat[centres]
+    boxes = torch.ones_like(centres)
+    for wk, E in zip(w, (X, Y, Z)):
+        h = torch.sqrt(D / wk).floor().clamp_(max=float(E)).to(torch.int64) + 1     # never below the exact half-extent
+        boxes *= (2 * h + 1).clamp_(max=E)
+    return centres, boxes
+
+
+def local_thickness(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, rows=None, dist2=None,
+                    budget: int = PAINT_BUDGET) -> Tuple[Tensor, Tensor, Tensor]:
+    """Local thickness of every instance of an (X, Y, Z) or (1, X, Y, Z) integer device tensor at the voxel spacing
+    ``spacing``: ``(thick2 (X, Y, Z), dist2 (X, Y, Z), row_max (N))``, all float64 on the device (DESIGN.md section 28;
+    the reference has no counterpart).
+
+    ``thick2`` is, for a voxel of a positive id, the squared radius of the largest open ball around a voxel centre that
+    holds voxels of that id only and holds the voxel: ``max D2(c)`` over the voxels c with ``d2(p, c) < D2(c)``, where
+    ``D2`` is ``label_edt``'s ``dist2`` and ``d2 = fl(wx dx^2 + fl(wy dy^2 + wz dz^2))`` (include/skoots_hip.h:
+    sk_local_thickness_paint); 0 on the other voxels.  It is a radius between voxel centres, not a diameter, with no
+    half-voxel correction, exact and the same on every run.  ``thick2 >= dist2`` everywhere and, per id, its maximum is
+    ``row_max``.  In open mode an id that is alone in the volume has ``inf``, as in ``label_edt``.
+
+    ``closed`` and ``rows`` are those of ``label_edt``.  ``dist2`` is ``label_edt``'s pair ``(dist2, row_max)`` when the
+    caller already has it, in the same mode and at the same spacing; it is not modified.  Every voxel whose ball holds
+    more than itself is a centre, and a centre costs its bounding box: a compact object of radius R voxels costs about
+    R^6 tests, so the centre list is painted in consecutive launches of at most ``budget`` box voxels each (a centre
+    whose own box is larger goes alone).  The result does not depend on ``budget``."""
+    from ..validate.lib import id_rows
+    budget = int(budget)
+    if budget < 1:
+        raise ValueError(f"budget must be a positive number of box voxels, got {budget}")
+    if dist2 is None:
+        x, rows = id_rows(labels) if rows is None else rows
+        dist2, row_max = label_edt(x, spacing, closed, (x, rows))
+    else:
+        dist2, row_max = dist2
+        if not isinstance(dist2, Tensor) or not dist2.is_cuda or dist2.dtype != torch.float64 or dist2.ndim != 3:
+            raise ValueError("dist2 must be label_edt's pair (dist2 (X, Y, Z) float64 on the device, row_max)")
+        dist2 = dist2.contiguous()
+    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
+    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
+        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
+    w = (s[0] * s[0], s[1] * s[1], s[2] * s[2])
+    X, Y, Z = (int(v) for v in dist2.shape)
+    thick2 = dist2.clone()
+    if thick2.numel() == 0:
+        return thick2, dist2, row_max
+    centres, boxes = paint_centres(dist2, w)
+    n = int(centres.numel())
+    if n == 0:
+        return thick2, dist2, row_max
+    dev = dist2.device
+    ends = torch.cumsum(boxes, 0)                            # boxes <= X Y Z < 2^62 each; int64 holds any real list
+    first, done = 0, 0                                       # done: the box voxels of the launches so far
+    while first < n:
+        last = int(torch.searchsorted(ends, done + budget, right=True).item())
+        last = max(last, first + 1)                          # a centre whose own box exceeds the budget goes alone
+        _ffi.check(_ffi.lib.sk_local_thickness_paint(_ffi.ptr(dist2), X, Y, Z, w[0], w[1], w[2],
+                                                     _ffi.ptr(centres[first:last]), last - first,
+                                                     _ffi.ptr(thick2), _ffi.stream_ptr(dev)))
+        done, first = int(ends[last - 1].item()), last
+    return thick2, dist2, row_max
 
 
 def max_distance_squared(max_distance) -> float:

@@ -20,6 +20,10 @@ class, integers once more -- and ``skeleton_columns`` turns the links into a len
 instance (``sk_label_edt``) and ``inscribed_radius``, the square root of its maximum; together with the
 skeleton, the mean, minimum and maximum radius along the centre line.
 
+``local_thickness="open"`` / ``"closed"`` / ``--local-thickness`` adds the width everywhere: for every voxel the radius
+of the largest ball inside its instance that holds it (``sk_local_thickness_paint`` on the distance transform, DESIGN.md
+§28), and per instance its mean, spread and thinnest place; ``--save-thickness`` writes the map.
+
 ``mesh="open"`` / ``"closed"`` / ``--mesh`` adds the size of the marching-cubes mesh itself -- vertices, triangles and,
 closed, the Euler characteristic (``sk_instance_mesh_count``) -- and ``--save-meshes`` writes the
 meshes of ``lib.instance_meshes`` into one PLY file.
@@ -41,8 +45,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .lib import (check_shape, id_rows, instance_mesh_cells, instance_mesh_counts, instance_meshes,
-                  instance_skeleton_graph, instance_sums, instance_thickness)
+from .lib import (check_shape, id_rows, instance_local_thickness, instance_mesh_cells, instance_mesh_counts,
+                  instance_meshes, instance_skeleton_graph, instance_sums, instance_thickness)
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
@@ -58,6 +62,7 @@ MESH_CLOSED_COLUMNS = "euler_characteristic"             # ... and behind them w
 MESH_MODES = (None, "open", "closed")
 PIECES_COLUMNS = "pieces,largest_piece_voxels"           # appended with --pieces
 PIECES_MODES = (None, 6, 18, 26)
+LOCAL_THICKNESS_COLUMNS = "local_radius_mean,local_radius_std,local_radius_min"  # appended with --local-thickness
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -202,6 +207,42 @@ def thickness_columns(max_d2: Tensor, skel_stats: Optional[Tensor] = None) -> Di
     return out
 
 
+def local_thickness_columns(table, N: int) -> Dict[str, Tensor]:
+    """The local-thickness columns (float64 host tensors, N rows) from the (K, 3) table of
+    ``lib.instance_local_thickness`` -- ``(row 1..N, T2 bit pattern, voxels)``, sorted by row and then value:
+
+    ``local_radius_mean``: the mean of ``sqrt(T2)`` over the instance's voxels, a plain left-to-right sum of
+    ``voxels * sqrt(value)`` in ascending order of the values over the voxel count, kept inside [minimum, maximum]
+    (rounding can put the mean of equal values a unit outside them); ``local_radius_std``: the population standard
+    deviation around that mean, accumulated in the same order, 0.0 for a single value; ``local_radius_min``: the
+    thinnest place.  The maximum is ``inscribed_radius`` (per instance ``max T2 = max D2``).  The radii follow
+    ``thickness_columns``' conventions: between voxel centres, a radius and not a diameter, no half-voxel correction.
+    An instance alone in the volume in open mode has ``inf`` everywhere and reports ``inf, 0.0, inf``; a row without
+    voxels reports 0.0 in all three (no real radius is 0)."""
+    t = np.asarray(table.cpu() if isinstance(table, Tensor) else table, dtype=np.int64).reshape(-1, 3)
+    # numpy's square root is the correctly rounded one at every length of the array (thickness_columns)
+    radius = np.sqrt(np.ascontiguousarray(t[:, 1]).view(np.float64))
+    first = np.searchsorted(t[:, 0], np.arange(1, int(N) + 2))
+    out = np.zeros((int(N), 3), np.float64)
+    for r in range(int(N)):
+        v, c = radius[first[r]:first[r + 1]].tolist(), t[first[r]:first[r + 1], 2].tolist()
+        if not v:
+            continue
+        if v[0] == float("inf"):                             # ascending: every value of the row is inf
+            out[r] = (float("inf"), 0.0, float("inf"))
+            continue
+        n, total = 0, 0.0
+        for value, count in zip(v, c):                       # one order, whatever numpy does
+            n += count
+            total += count * value
+        mean = min(max(total / n, v[0]), v[-1])
+        spread = 0.0
+        for value, count in zip(v, c):
+            spread += count * ((value - mean) * (value - mean))
+        out[r] = (mean, float(np.sqrt(np.float64(spread / n))) if len(v) > 1 else 0.0, v[0])
+    return {name: torch.from_numpy(out[:, k].copy()) for k, name in enumerate(LOCAL_THICKNESS_COLUMNS.split(","))}
+
+
 def mesh_columns(counts: Tensor, closed: bool) -> Dict[str, Tensor]:
     """The mesh columns (int64 host tensors) from the (N, 2) counts of ``instance_mesh_counts``: ``mesh_vertices`` and
     ``mesh_triangles``, and for a closed mesh ``euler_characteristic`` = V - E + F = V - F / 2.  A closed mesh is
@@ -236,7 +277,8 @@ def pieces_columns(table: Tensor, ids) -> Dict[str, Tensor]:
 
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
                        skeleton: bool = False, thickness: Optional[str] = None,
-                       mesh: Optional[str] = None, pieces: Optional[int] = None) -> Dict[str, Tensor]:
+                       mesh: Optional[str] = None, pieces: Optional[int] = None,
+                       local_thickness: Optional[str] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -272,7 +314,15 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
 
     ``pieces=6``, ``18`` or ``26`` adds ``pieces`` and ``largest_piece_voxels`` (int64): the connected pieces of every
     id at that connectivity and the size of the largest, from ``lib.morphology.label_components`` (``pieces_columns``,
-    DESIGN.md §26)."""
+    DESIGN.md §26).
+
+    ``local_thickness="open"`` or ``"closed"`` adds ``thick2`` (X, Y, Z) float64, for every instance voxel the squared
+    radius of the largest ball inside its instance that holds it (``lib.instance_local_thickness``; the modes are those
+    of ``thickness``, and when both name the same mode the distance transform runs once), ``max_dist2`` if ``thickness``
+    did not add it, and ``local_radius_mean``, ``local_radius_std``, ``local_radius_min`` (``local_thickness_columns``,
+    DESIGN.md §28)."""
+    if local_thickness not in THICKNESS_MODES:
+        raise ValueError(f"local_thickness must be one of {THICKNESS_MODES}, got {local_thickness!r}")
     if pieces not in PIECES_MODES or isinstance(pieces, bool):
         raise ValueError(f"pieces must be one of {PIECES_MODES}, got {pieces!r}")
     if mesh not in MESH_MODES:
@@ -310,6 +360,12 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     if pieces is not None:
         from ..lib.morphology import label_components
         out.update({k: v.to(sums.device) for k, v in pieces_columns(label_components(x, pieces, rows=rows)[1], ids).items()})
+    if local_thickness is not None:
+        have = (out["dist2"], out["max_dist2"]) if thickness == local_thickness else None
+        _, table, thick2, max_d2 = instance_local_thickness(x, spacing, local_thickness == "closed", rows, have)
+        out["thick2"] = thick2
+        out.setdefault("max_dist2", max_d2)
+        out.update({k: v.to(sums.device) for k, v in local_thickness_columns(table, int(ids.numel())).items()})
     return out
 
 
@@ -443,7 +499,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                min_voxels: int = 1, mesh_cells: Optional[Tensor] = None,
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
-               mesh_closed: bool = False, piece_table: Optional[Tensor] = None) -> str:
+               mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -455,7 +511,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     ``inf``.  With ``mesh_counts`` (the (N, 2) counts of ``instance_mesh_counts``) ``mesh_vertices,mesh_triangles``
     follow behind all of those, and ``euler_characteristic`` behind them when ``mesh_closed`` says the counts are those
     of closed mode.  With ``piece_table`` (the (P, 6) table of ``label_components``) ``pieces,largest_piece_voxels``
-    follow behind everything else; without it the text is byte for byte what it was before they existed."""
+    follow behind everything else; without it the text is byte for byte what it was before they existed.  With
+    ``thickness_table`` (the (K, 3) table of ``instance_local_thickness``) ``local_radius_mean,local_radius_std,
+    local_radius_min`` follow behind all of that, under the same rule."""
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
@@ -472,14 +530,17 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         mesh_names = (MESH_COLUMNS + ("," + MESH_CLOSED_COLUMNS if mesh_closed else "")).split(",")
     if piece_table is not None:
         d.update(pieces_columns(piece_table, ids))
-    d = {k: v.cpu().tolist() for k, v in d.items()}
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
+    if thickness_table is not None:
+        d.update(local_thickness_columns(thickness_table, len(ids)))
+    d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
              ("," + SKELETON_COLUMNS if skeleton_graph is not None else "") +
              ("," + THICKNESS_COLUMNS if max_dist2 is not None else "") +
              ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") +
-             "".join("," + k for k in mesh_names) + ("," + PIECES_COLUMNS if piece_table is not None else "") + "\n"]
+             "".join("," + k for k in mesh_names) + ("," + PIECES_COLUMNS if piece_table is not None else "") +
+             ("," + LOCAL_THICKNESS_COLUMNS if thickness_table is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -498,6 +559,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         cells += [d[k][i] for k in mesh_names]
         if piece_table is not None:
             cells += [d[k][i] for k in PIECES_COLUMNS.split(",")]
+        if thickness_table is not None:
+            cells += [repr(d[k][i]) for k in LOCAL_THICKNESS_COLUMNS.split(",")]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -529,6 +592,16 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                         help="Also write <mask>_distance.tif, float32, every instance voxel its distance to the nearest "
                              "voxel outside its instance and background 0, stored [Z, X, Y] like the mask (implies "
                              "--thickness open when no mode is given)")
+    parser.add_argument("--local-thickness", type=str, default=None, choices=("open", "closed"),
+                        help="Append " + LOCAL_THICKNESS_COLUMNS + ": for every voxel the radius of the largest ball "
+                             "inside its instance that holds it (the local thickness, as a radius between voxel "
+                             "centres), and per instance its mean, standard deviation and smallest value, the thinnest "
+                             "place; open and closed as for --thickness.  Every voxel paints its ball: a compact object "
+                             "many tens of voxels across takes long")
+    parser.add_argument("--save-thickness", action="store_true",
+                        help="Also write <mask>_thickness.tif, float32, every instance voxel its local radius and "
+                             "background 0, stored [Z, X, Y] like the mask (implies --local-thickness open when no mode "
+                             "is given)")
     parser.add_argument("--mesh", type=str, default=None, choices=("open", "closed"),
                         help="Append " + MESH_COLUMNS + ": the size of every instance's marching-cubes mesh, left open "
                              "where the volume's faces cut it or closed there; closed also appends " +
@@ -560,6 +633,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args.skeleton = args.skeleton or args.save_skeletons
     if args.save_distance and args.thickness is None:
         args.thickness = "open"
+    if args.save_thickness and args.local_thickness is None:
+        args.local_thickness = "open"
     if args.save_meshes and args.mesh is None:
         args.mesh = "closed"
     if args.mesh_ids is not None and not args.save_meshes:
@@ -604,8 +679,13 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
     if args.pieces:
         from ..lib.morphology import label_components
         piece_table = label_components(dev_mask, args.pieces, rows=rows)[1]
+    thickness_table = thick2 = None
+    if args.local_thickness:
+        have = (dist2, max_d2) if args.thickness == args.local_thickness else None
+        thickness_table, thick2 = instance_local_thickness(dev_mask, spacing, args.local_thickness == "closed", rows,
+                                                           have)[1:3]
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
-                      max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table)
+                      max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
@@ -623,6 +703,12 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         # (X, Y, Z) -> the mask's [Z, X, Y]; inf (an instance alone in the volume, open mode) stays inf in float32
         tiff.write_float_stack(dist_path, torch.sqrt(dist2).to(torch.float32).permute(2, 0, 1).contiguous())
         print(f"File Written: {dist_path}")
+    if args.save_thickness:
+        from ..lib import tiff
+        thick_path = f"{os.path.splitext(args.mask)[0]}_thickness.tif"
+        # (X, Y, Z) -> the mask's [Z, X, Y]; inf (an instance alone in the volume, open mode) stays inf in float32
+        tiff.write_float_stack(thick_path, torch.sqrt(thick2).to(torch.float32).permute(2, 0, 1).contiguous())
+        print(f"File Written: {thick_path}")
     if args.save_meshes:
         from ..lib.ply import write_ply
         keep = ids[sums[:, 0] >= args.min_voxels]

@@ -13,6 +13,8 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 (DESIGN.md §24).
 ``instance_skeleton_graph`` thins every instance in its box and reads the skeletons as graphs.
 ``instance_thickness`` is the exact distance transform of every instance and its maximum per instance.
+``instance_local_thickness`` is the local thickness of every instance voxel and its distribution per instance
+(DESIGN.md §28).
 ``instance_surfaces``, ``surface_distances``, ``match_instances`` and ``pair_summaries`` are the parts of
 ``validate/compare.py: compare()``: every instance's surface voxels as sorted keys, the exact squared distance from
 every surface voxel of one instance to the surface of another for many pairs at once, the matching rule, and the
@@ -528,6 +530,35 @@ def instance_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False,
             # rounding can put the mean of equal values a unit outside them: keep it inside [min, max]
             stats[r] = (min(max(total / v.size, v.min()), v.max()), v.min(), v.max())
     return ids, max_d2, dist2, torch.from_numpy(stats)
+
+
+def instance_local_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, rows=None, dist2=None):
+    """(ids (N) int64 ascending, table (K, 3) int64 on the host, thick2 (X, Y, Z) float64, max_d2 (N) float64) of the
+    positive ids of an (X, Y, Z) integer device tensor: ``lib.morphology.local_thickness`` -- for every instance voxel
+    the squared radius of the largest ball inside its instance that holds it -- and its distribution per
+    instance.  ``closed`` and ``rows`` are those of ``label_edt``; ``dist2`` is the pair ``(dist2, max_d2)`` of
+    ``label_edt`` / ``instance_thickness`` in the same mode when the caller already has it.
+
+    ``table`` has one row per (instance, distinct value): ``(row 1..N, the value's float64 bit pattern, voxels)``, sorted
+    by row and then by value (non-negative doubles order like their bit patterns).  It is built on the device from
+    integers only -- ``unique`` of the foreground bit patterns with the inverse, then ``unique`` with counts of
+    ``row * n_values + inverse`` -- so it is exact and the same on every run; ``compare.local_thickness_columns`` turns
+    it into the columns on the host."""
+    from ..lib.morphology import local_thickness
+    x, rows = id_rows(x) if rows is None else rows
+    dev = x.device
+    thick2, _, max_d2 = local_thickness(x, spacing, closed, (x, rows), dist2)
+    if rows is None:
+        return torch.empty(0, dtype=torch.int64, device=dev), np.zeros((0, 3), np.int64), thick2, max_d2
+    a, ids, lut, _ = rows
+    row = lut[a.reshape(-1).long().clamp_(min=0)].long()     # 1..N, 0 for the background and for negative values
+    fg = torch.nonzero(row)[:, 0]
+    values, inverse = torch.unique(thick2.reshape(-1)[fg].view(torch.int64), return_inverse=True)
+    n_values = int(values.numel())
+    keys, counts = torch.unique(row[fg] * n_values + inverse, return_counts=True)
+    table = torch.stack((torch.div(keys, max(n_values, 1), rounding_mode="floor"), values[keys % max(n_values, 1)],
+                         counts), 1)
+    return ids, table.cpu().numpy().astype(np.int64), thick2, max_d2
 
 
 # ---- compare(): surfaces, matching and surface distances (DESIGN.md §25) ----

@@ -16,6 +16,9 @@ overestimate of a curved surface.
 
 ``get_inscribed_radius`` is the largest value of the mask's exact Euclidean distance transform, on the
 path of ``compare.stats_per_instance(thickness=...)``.
+
+``get_local_thickness`` is the mask's local-thickness map, the radius of the largest ball inside the mask that holds the
+voxel, on the path of ``compare.stats_per_instance(local_thickness=...)``.
 """
 from __future__ import annotations
 
@@ -25,7 +28,8 @@ import torch
 from torch import Tensor
 
 from .compare import _spacing, mesh_area, skeleton_columns, thickness_columns
-from .lib import instance_mesh_cells, instance_meshes, instance_skeleton_graph, instance_sums, instance_thickness
+from .lib import (instance_local_thickness, instance_mesh_cells, instance_meshes, instance_skeleton_graph, instance_sums,
+                  instance_thickness)
 
 
 def _one_row(x: Tensor) -> Tensor:
@@ -106,3 +110,15 @@ def get_inscribed_radius(x: Tensor, spacing: Union[List[float], Tensor], closed:
     _, max_d2, _ = instance_thickness((x > 0).to(torch.int32), _spacing(spacing), closed)
     radius = thickness_columns(max_d2)["inscribed_radius"]
     return (radius[0] if radius.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
+
+
+def get_local_thickness(x: Tensor, spacing: Union[List[float], Tensor], closed: bool = False) -> Tensor:
+    """The local-thickness map of ``x > 0`` (one binary object) at the voxel spacing ``spacing``: (X, Y, Z) float64 on
+    x's device, for every voxel of the mask the radius of the largest open ball around a voxel centre that holds voxels
+    of the mask only and holds the voxel, and 0 elsewhere (Hildebrand and Ruegsegger's local thickness as a radius;
+    ``lib.morphology.local_thickness`` gives the exact squared values).  Distances run between voxel centres, without a
+    half-voxel correction; ``closed`` is ``get_inscribed_radius``'s, and a mask that fills the volume in open mode is
+    ``inf`` everywhere.  The largest value of the map is ``get_inscribed_radius``."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    return torch.sqrt(instance_local_thickness((x > 0).to(torch.int32), _spacing(spacing), closed)[2])
