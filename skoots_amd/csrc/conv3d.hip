@@ -2226,6 +2226,160 @@ __global__ void __launch_bounds__(256, 2) down2_act_kernel(DownArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// 1x1x1 conv (channel reducers 64 -> 32, 128 -> 64), LDS-staged (round 7).
+//
+// The 256 input voxels of a gather_gemm_kernel workgroup are, for a 1x1x1 conv, ONE contiguous run of 256 CIN 2
+// bytes: nothing has to be gathered.  The run is staged by LDS-DMA in whole lines exactly as a down2_act_kernel
+// stage (rows of RB = 2 CIN = 128 | 256 bytes, chunk c of row n at slot c ^ g(n), swizzle on the source side; thread
+// tid owns slots tid + 256 j, all of one chunk index), a RAW input is activated in place by the thread that staged
+// the slot (nothing is written back: this kernel is the tensor's only consumer), and the B fragments are read
+// from LDS.  The weight fragments (8 | 16 KiB) are loaded once per wave into registers.  Everything that decides a
+// result bit is gather_gemm_kernel<COUT, 2, *>'s: wave w owns voxels [256 blk + 64 w, + 64) as two column tiles, the
+// K steps run in order, the epilogue and the partial sums are its code.  Rows behind the tensor's end stage voxel 0
+// (any valid line: they are neither stored nor summed).
+// ------------------------------------------------------------------------------------------
+template <int COUT, int CIN>
+__global__ void __launch_bounds__(256) pointwise_lds_kernel(GatherArgs a) {
+    constexpr int NT = COUT / 32, PV = 2, NKS = CIN / 16;
+    constexpr int RB = 2 * CIN;                // bytes per staged row: one voxel
+    constexpr int CPR = RB / 16;               // 16-byte chunks per row (8 | 16)
+    constexpr int NP = 256 * RB / 4096;        // 1-KiB pieces per wave (8 | 16)
+    static_assert(CIN == 64 || CIN == 128, "rows of 128 or 256 bytes");
+    extern __shared__ __attribute__((aligned(16))) char plds[];   // [256 rows][RB] + 4 epilogue pads
+    __shared__ float red[4 * NT * 16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int col = lane & 31, h = lane >> 5;
+    const int b = blockIdx.x / a.nblk;
+    const int blk = blockIdx.x % a.nblk;
+    const long long nvox = (long long)a.Xo * a.Yo * a.Zo;
+    const long long v0 = (long long)blk * 256;
+    auto gsw = [](int n) { return CPR == 8 ? ((n >> 1) & 7) : (n & 15); };   // down2_act_kernel's
+    const int csrc = (tid % CPR) ^ gsw(tid / CPR);   // source chunk: rows tid / CPR + (256 / CPR) j share the swizzle term
+
+    // weight fragments of all K steps, then the whole input run
+    half8 afr[NKS][NT];
+#pragma unroll
+    for (int k = 0; k < NKS; ++k)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+            afr[k][nt] = *reinterpret_cast<const half8*>(a.wpk + (k * NT + nt) * 1024 + lane * 16);
+    const char* inb = a.in + (long long)b * nvox * RB;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const long long v = v0 + tid / CPR + (256 / CPR) * j;
+        dma16(inb + (v < nvox ? v : 0) * RB + csrc * 16, plds + (w + 4 * j) * 1024);
+    }
+
+    f32x16 acc[PV][NT];
+    bool ok[PV];
+#pragma unroll
+    for (int p = 0; p < PV; ++p) {
+        ok[p] = v0 + w * (32 * PV) + p * 32 + col < nvox;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + 32 * nt + 8 * q + 4 * h);
+                acc[p][nt][4 * q] = bv[0];
+                acc[p][nt][4 * q + 1] = bv[1];
+                acc[p][nt][4 * q + 2] = bv[2];
+                acc[p][nt][4 * q + 3] = bv[3];
+            }
+        }
+    }
+    if (a.affine) {   // RAW input: this thread's chunk is channels [8 csrc, 8 csrc + 8) in every slot it staged
+        float ga[8], gb[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            ga[e] = a.affine[(long long)b * 2 * CIN + 8 * csrc + e];
+            gb[e] = a.affine[(long long)b * 2 * CIN + CIN + 8 * csrc + e];
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            half8* lp = reinterpret_cast<half8*>(plds + (tid + 256 * j) * 16);
+            const half8 v = *lp;
+            half8 r;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) r[e] = sk::silu_affine_t16(ga[e], (float)v[e], gb[e]);
+            *lp = r;
+        }
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NKS; ++k) {
+#pragma unroll
+        for (int p = 0; p < PV; ++p) {
+            const int n = w * (32 * PV) + p * 32 + col;
+            const half8 bfr = *reinterpret_cast<const half8*>(plds + n * RB + (((2 * k + h) ^ gsw(n)) * 16));
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                acc[p][nt] = SK_MFMA_32x32x16_T16(afr[k][nt], bfr, acc[p][nt], 0, 0, 0);
+        }
+    }
+
+    // ---- epilogue: transposed 16-byte stores + GroupNorm partials (gather_gemm_kernel's) ---------------------
+    float gsum[NT][4], gsq[NT][4];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gsum[nt][q] = gsq[nt][q] = 0.0f;
+    char* outb = a.out + (long long)b * nvox * (COUT * 2);
+    char* pad = plds + 256 * RB + w * kPadBytes;
+    const int rv = lane >> 2, rc = lane & 3;
+    const long long vbase = v0 + w * (32 * PV);   // first voxel of this wave
+#pragma unroll
+    for (int p = 0; p < PV; ++p) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float x0 = acc[p][nt][4 * q], x1 = acc[p][nt][4 * q + 1];
+                float x2 = acc[p][nt][4 * q + 2], x3 = acc[p][nt][4 * q + 3];
+                half4 hv = {(t16)x0, (t16)x1, (t16)x2, (t16)x3};
+                *reinterpret_cast<half4*>(pad + col * kPadStride + ((q ^ ((col >> 1) & 3)) * 16) + 8 * h) = hv;
+                if (ok[p]) {
+                    gsum[nt][q] += (x0 + x1) + (x2 + x3);
+                    gsq[nt][q] += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
+                }
+            }
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const int vv = rv + 16 * hh;
+                const half8 line = *reinterpret_cast<const half8*>(pad + vv * kPadStride + ((rc ^ ((vv >> 1) & 3)) * 16));
+                const long long v = vbase + p * 32 + vv;
+                if (v < nvox) *reinterpret_cast<half8*>(outb + v * (COUT * 2) + nt * 64 + rc * 16) = line;
+            }
+        }
+    }
+    if (a.partial) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float s = gsum[nt][q], ss = gsq[nt][q];
+#pragma unroll
+                for (int m = 16; m > 0; m >>= 1) {
+                    s += __shfl_xor(s, m);
+                    ss += __shfl_xor(ss, m);
+                }
+                if (col == 0) {
+                    int quad = 8 * nt + 2 * q + h;
+                    red[(w * (NT * 8) + quad) * 2 + 0] = s;
+                    red[(w * (NT * 8) + quad) * 2 + 1] = ss;
+                }
+            }
+        __syncthreads();
+        if (tid < NT * 16) {
+            float t = red[tid] + red[NT * 16 + tid] + red[2 * NT * 16 + tid] + red[3 * NT * 16 + tid];
+            a.partial[((long long)b * a.nblk + blk) * (NT * 16) + tid] = t;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // down2_act_split_kernel (round 4): down2_act_kernel for precision = "split".
 //
 // Tensors hold [hi (C) | lo (C)] fp16 pairs per voxel line (value = hi + lo), the weight comes as all hi fragments
@@ -2879,6 +3033,10 @@ static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, c
     SK_CHECK_ARG(g.Cin <= 128 && nsteps % 2 == 0, "sk_conv3d: ksize %d needs 32 <= cin <= 128 (got %d)", ksize, g.Cin);
     const bool deep = nsteps % 4 == 0;  // pipeline depth 4 (2 only for the 32-channel pointwise case)
     void (*kern)(GatherArgs);
+    if (!split && ksize == 1 && ((g.Cin == 64 && cout == 32) || (g.Cin == 128 && cout == 64))) {   // the channel reducers: nothing to gather
+        kern = cout == 32 ? pointwise_lds_kernel<32, 64> : pointwise_lds_kernel<64, 128>;
+        return launch(kern, (unsigned)(g.nblk * B), (size_t)256 * 2 * g.Cin + 4 * kPadBytes, g, stream);
+    }
     if (split)   // depth 2: twice the fragments in flight per step
         kern = cout == 32 ? gather_gemm_kernel<32, 2, 2, true> : cout == 64 ? gather_gemm_kernel<64, 2, 2, true> : gather_gemm_kernel<128, 1, 2, true>;
     else if (cout == 32)

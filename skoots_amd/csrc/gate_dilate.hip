@@ -142,6 +142,201 @@ gate_dilate_scatter_kernel(const T* __restrict__ out5_all, GateGeom g, uint2* __
     }
 }
 
+// ---- d <= 32: one 32-bit mask word per staged column --------------------------------------------
+// A column (x, y) of the tile has at most 32 voxels, so its mask is one word: bit z = voxel z.  The z
+// dilation is two shifts, the y and x dilations are ORs of 7 neighbouring words, and the per-voxel
+// phases of the kernel above (each with its own % and /) become per-column phases.  Work is handed out
+// in quads: four z-neighbours that start at a multiple of 4, which is 8 aligned bytes of an fp16 row.
+constexpr int PX = 16, PY = 16;                      // interior patch of a block
+constexpr int SXW = PX + 2 * RX, SYW = PY + 2 * RY;  // staged columns
+
+// Four fp16 values held in 8 bytes, as floats.
+__device__ __forceinline__ void unpack_quad(uint2 r, float v[4]) {
+    __half2 a = *reinterpret_cast<__half2*>(&r.x), b = *reinterpret_cast<__half2*>(&r.y);
+    v[0] = __low2float(a);
+    v[1] = __high2float(a);
+    v[2] = __low2float(b);
+    v[3] = __high2float(b);
+}
+// Four z-neighbours of one plane as floats.  VEC: one 8-byte load (fp16 rows whose quads are 8-byte
+// aligned and whole); otherwise n <= 4 scalar loads, the rest reads as 0.
+template <typename T, bool VEC>
+__device__ __forceinline__ void load_quad(const T* p, int n, float v[4]) {
+    if constexpr (VEC) {
+        unpack_quad(*reinterpret_cast<const uint2*>(p), v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = k < n ? ld(p, k) : 0.0f;
+    }
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256)
+gate_dilate_scatter_words_kernel(const T* __restrict__ out5_all, GateGeom g, uint2* __restrict__ vec4,
+                                 __half* __restrict__ vec_planar, uint8_t* __restrict__ skeleton) {
+    __shared__ unsigned w0[SXW * SYW];  // gate mask of every staged column
+    __shared__ unsigned w1[SXW * PY];   // after the y dilation
+    const TileGeom tg = g.t[blockIdx.y];
+    if ((int)blockIdx.x >= tg.nblocks) return;  // grid.x is sized for the largest write box
+    const T* out5 = out5_all + tg.off;
+    const int bx = blockIdx.x % tg.nbx, by = blockIdx.x / tg.nbx;
+    const int x0 = tg.lx + bx * PX, y0 = tg.ly + by * PY;  // tile-local patch origin
+    const int d = g.d;
+    const long long plane = g.sc;
+    const int tid = threadIdx.x, nth = blockDim.x;   // nth = PX * PY: thread tid scatters items tid + nth k, k < nq3
+
+    // What phase 3 reads does not depend on the mask.  With 8-byte quads the first kPre items of a thread are
+    // requested here, ahead of phase 1, so that a block waits for memory once and not twice.
+    constexpr int kPre = VEC ? 3 : 0;
+    const int q3 = tg.lz >> 2, nq3 = ((tg.hz + 3) >> 2) - q3;   // the quads that hold planes [lz, hz)
+    uint2 pre[kPre ? kPre : 1][4];
+    if constexpr (VEC) {
+#pragma unroll
+        for (int k = 0; k < kPre; ++k) {
+            const int i = tid + k * (PX * PY);
+            const int c = i / nq3;
+            const int tx = x0 + c / PY, ty = y0 + c % PY;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pre[k][j] = make_uint2(0, 0);
+            if (k < nq3 && tx < tg.hx && ty < tg.hy) {
+                const T* p = out5 + (long long)tx * g.sx + (long long)ty * g.sy + 4 * (q3 + i % nq3);
+                pre[k][0] = *reinterpret_cast<const uint2*>(p);
+                pre[k][1] = *reinterpret_cast<const uint2*>(p + plane);
+                pre[k][2] = *reinterpret_cast<const uint2*>(p + 2 * plane);
+                pre[k][3] = *reinterpret_cast<const uint2*>(p + 4 * plane);
+            }
+        }
+    }
+
+    for (int i = tid; i < SXW * SYW; i += nth) w0[i] = 0;
+    __syncthreads();
+    // phase 1: bit z of a column = skel > skel_thr && prob > prob_thr; columns outside the tile stay 0.
+    // The written planes [lz, hz) see bits lz-1 .. hz only, so only the quads that hold those are read.
+    {
+        const int q0 = max(tg.lz - 1, 0) >> 2, nq = ((min(tg.hz + 1, d) + 3) >> 2) - q0;
+        for (int i = tid; i < SXW * SYW * nq; i += nth) {
+            int q = q0 + i % nq;
+            int c = i / nq;
+            int ly = c % SYW, lx = c / SYW;
+            int tx = x0 - RX + lx, ty = y0 - RY + ly;
+            if (tx < 0 || tx >= g.w || ty < 0 || ty >= g.h) continue;
+            long long o = (long long)tx * g.sx + (long long)ty * g.sy + 4 * q;
+            float skel[4], prob[4];
+            load_quad<T, VEC>(out5 + 3 * plane + o, d - 4 * q, skel);
+            load_quad<T, VEC>(out5 + 4 * plane + o, d - 4 * q, prob);
+            unsigned bits = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * q + k < d && prob[k] > g.prob_thr && skel[k] > g.skel_thr) bits |= 1u << k;
+            if (bits) atomicOr(&w0[c], bits << (4 * q));
+        }
+    }
+    __syncthreads();
+    // phase 2: y dilation (radius 3) for the columns the x pass needs -> w1[SXW][PY]
+    for (int i = tid; i < SXW * PY; i += nth) {
+        int ly = i % PY, lx = i / PY;
+        unsigned m = 0;
+#pragma unroll
+        for (int k = 0; k <= 2 * RY; ++k) m |= w0[lx * SYW + ly + k];
+        w1[i] = m;
+    }
+    __syncthreads();
+    // phase 3: x dilation (radius 3), z dilation (radius 1, zero padded at the tile faces: bits shifted
+    // out of [0, d) are dropped) and the scatter of the interior, one quad of one column per thread
+    const unsigned dmask = d >= 32 ? 0xffffffffu : (1u << d) - 1u;
+    const long long nv = (long long)g.X * g.Y * g.Z;
+    auto scatter_item = [&](int i, const uint2* raw) {   // raw: the item's four quads as requested above, or NULL
+        int q = q3 + i % nq3;
+        int c = i / nq3;
+        int ly = c % PY, lx = c / PY;
+        int tx = x0 + lx, ty = y0 + ly, z0 = 4 * q;
+        if (tx >= tg.hx || ty >= tg.hy) return;
+        unsigned m = 0;
+#pragma unroll
+        for (int k = 0; k <= 2 * RX; ++k) m |= w1[(lx + k) * PY + ly];
+        m = (m | (m << 1) | (m >> 1)) & dmask;
+        // vectors: vec * (prob > thr), stored fp16 (eval.py:149,175)
+        long long o = (long long)tx * g.sx + (long long)ty * g.sy + z0;
+        float v0[4], v1[4], v2[4], prob[4];
+        if (raw) {
+            unpack_quad(raw[0], v0);
+            unpack_quad(raw[1], v1);
+            unpack_quad(raw[2], v2);
+            unpack_quad(raw[3], prob);
+        } else {
+            load_quad<T, VEC>(out5 + o, d - z0, v0);
+            load_quad<T, VEC>(out5 + plane + o, d - z0, v1);
+            load_quad<T, VEC>(out5 + 2 * plane + o, d - z0, v2);
+            load_quad<T, VEC>(out5 + 4 * plane + o, d - z0, prob);
+        }
+        bool ok[4];
+        unsigned short h[3][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            ok[k] = z0 + k >= tg.lz && z0 + k < tg.hz;
+            bool gate = prob[k] > g.prob_thr;
+            h[0][k] = __half_as_ushort(__float2half_rn(gate ? v0[k] : copysignf(0.0f, v0[k])));
+            h[1][k] = __half_as_ushort(__float2half_rn(gate ? v1[k] : copysignf(0.0f, v1[k])));
+            h[2][k] = __half_as_ushort(__float2half_rn(gate ? v2[k] : copysignf(0.0f, v2[k])));
+        }
+        const bool all = ok[0] && ok[1] && ok[2] && ok[3];
+        const long long vo = ((long long)(tg.ox + tx) * g.Y + (tg.oy + ty)) * g.Z + (tg.oz + z0);
+        // every run below is contiguous in z: the widest store its address allows, else one per voxel
+        uint8_t* sp = skeleton + vo;
+        if (all && (reinterpret_cast<uintptr_t>(sp) & 3) == 0) {
+            *reinterpret_cast<unsigned*>(sp) = ((m >> z0) & 1u) | ((m >> (z0 + 1)) & 1u) << 8 |
+                                               ((m >> (z0 + 2)) & 1u) << 16 | ((m >> (z0 + 3)) & 1u) << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ok[k]) sp[k] = (m >> (z0 + k)) & 1u;
+        }
+        if (vec4) {
+            uint2* vp = vec4 + vo;
+            uint2 r[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = make_uint2(h[0][k] | (unsigned)h[1][k] << 16, h[2][k]);
+            auto one = [&](int k) {
+                if (ok[k]) vp[k] = r[k];
+            };
+            auto two = [&](int k) {  // vp + k is 16-byte aligned
+                if (ok[k] && ok[k + 1])
+                    *reinterpret_cast<uint4*>(vp + k) = make_uint4(r[k].x, r[k].y, r[k + 1].x, r[k + 1].y);
+                else {
+                    one(k);
+                    one(k + 1);
+                }
+            };
+            if ((reinterpret_cast<uintptr_t>(vp) & 15) == 0) {
+                two(0);
+                two(2);
+            } else {
+                one(0);
+                two(1);
+                one(3);
+            }
+        }
+        if (vec_planar) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                __half* pp = vec_planar + vo + ch * nv;
+                if (all && (reinterpret_cast<uintptr_t>(pp) & 7) == 0) {
+                    *reinterpret_cast<uint2*>(pp) = make_uint2(h[ch][0] | (unsigned)h[ch][1] << 16,
+                                                               h[ch][2] | (unsigned)h[ch][3] << 16);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (ok[k]) pp[k] = __ushort_as_half(h[ch][k]);
+                }
+            }
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < kPre; ++k)
+        if (k < nq3) scatter_item(tid + k * (PX * PY), pre[k]);
+    for (int k = kPre; k < nq3; ++k) scatter_item(tid + k * (PX * PY), nullptr);
+}
+
 // Library max filter (binary_dilation / binary_dilation_2d on arbitrary fp32 maps).
 __global__ void __launch_bounds__(256) max_filter_kernel(const float* __restrict__ in,
                                                          float* __restrict__ out, int w, int h,
@@ -240,7 +435,21 @@ int sk_gate_dilate_scatter(const void* out5, int out_dtype, int n_tiles, const i
         if (t.nblocks > max_blocks) max_blocks = t.nblocks;
     }
     dim3 grid(max_blocks, n_tiles);
-    if (out_dtype == SK_F16) {
+    if (d <= 32) {  // mask words; px = py = 16 holds here (lds above is at most 31 KiB)
+        // 8-byte quad loads need fp16 rows made of whole, 8-byte aligned quads
+        bool vec = out_dtype == SK_F16 && d % 4 == 0 && stride_c % 4 == 0 && stride_x % 4 == 0 &&
+                   stride_y % 4 == 0 && reinterpret_cast<uintptr_t>(out5) % 8 == 0;
+        for (int i = 0; i < n_tiles; ++i) vec = vec && tile_offsets_host[i] % 4 == 0;
+        if (out_dtype == SK_F32)
+            gate_dilate_scatter_words_kernel<float, false><<<grid, 256, 0, (hipStream_t)stream>>>(
+                (const float*)out5, g, (uint2*)vec4, (__half*)vec_planar, skeleton);
+        else if (vec)
+            gate_dilate_scatter_words_kernel<__half, true><<<grid, 256, 0, (hipStream_t)stream>>>(
+                (const __half*)out5, g, (uint2*)vec4, (__half*)vec_planar, skeleton);
+        else
+            gate_dilate_scatter_words_kernel<__half, false><<<grid, 256, 0, (hipStream_t)stream>>>(
+                (const __half*)out5, g, (uint2*)vec4, (__half*)vec_planar, skeleton);
+    } else if (out_dtype == SK_F16) {
         if (lds > 48 * 1024)
             SK_CHECK_HIP(hipFuncSetAttribute((const void*)gate_dilate_scatter_kernel<__half>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -632,20 +632,52 @@ __global__ void __launch_bounds__(256) heads_kernel(HeadArgs a) {
     t16* ob = a.out5 + (long long)b * 5 * a.n;
     const long long nbox = (long long)a.bx * a.by * a.bz;
     const long long ntiles = (nbox + 31) / 32;
-    for (long long t = (long long)blockIdx.x * 4 + (tid >> 6); t < ntiles; t += (long long)gridDim.x * 4) {
-        const long long i = t * 32 + col;
-        const bool ok = i < nbox;
-        const long long ii = ok ? i : 0;
-        const int z = (int)(ii % a.bz);
-        const long long r2 = ii / a.bz;
-        const long long v = ((long long)(a.lx + (int)(r2 / a.by)) * a.Y + (a.ly + (int)(r2 % a.by))) * a.Z + (a.lz + z);
+    // The lane's voxel i = 32 t + col advances by the same step every iteration, so its box coordinates are
+    // divided out once here and then carried with adds and compares: no division in the loop.
+    const long long t0 = (long long)blockIdx.x * 4 + (tid >> 6);
+    const int step = (int)gridDim.x * 4 * 32;   // voxels; the grid is capped at 4096 blocks
+    const int dz = step % a.bz, dy = (step / a.bz) % a.by, dx = (step / a.bz) / a.by;
+    long long i = t0 * 32 + col;
+    int z = (int)(i % a.bz), y = (int)((i / a.bz) % a.by), x = (int)((i / a.bz) / a.by);
+    // position of the lane's voxel, then one step ahead: {in the box, voxel index in the tile}
+    auto advance = [&](bool& ok, long long& v) {
+        ok = i < nbox;
+        v = ((long long)(a.lx + x) * a.Y + (a.ly + y)) * a.Z + (a.lz + z);
+        i += step;
+        z += dz;
+        const int cz = z >= a.bz;
+        z -= cz ? a.bz : 0;
+        y += dy + cz;
+        const int cy = y >= a.by;
+        y -= cy ? a.by : 0;
+        x += dx + cy;
+    };
+    // The 16-byte pieces of a voxel line this lane multiplies; a lane outside the box reads voxel 0 (no branch around
+    // a request).  The next iteration's pieces are requested before this iteration's are activated: a wave has its
+    // next 2 KiB in flight under its own exp / rcp work instead of one load -> wait -> use round trip per iteration.
+    constexpr int kPieces = SPLIT ? 4 : 2;
+    auto request = [&](bool ok, long long v, half8 (&r)[kPieces]) {
         const half8* p = reinterpret_cast<const half8*>(xb + (ok ? v : 0) * kLine);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            r[ks] = p[2 * ks + h];
+            if constexpr (SPLIT) r[2 + ks] = p[C / 8 + 2 * ks + h];
+        }
+    };
+    bool ok, ok_next;
+    long long v, v_next;
+    half8 cur[kPieces], nxt[kPieces];
+    advance(ok, v);
+    request(ok, v, cur);
+    for (long long t = t0; t < ntiles; t += (long long)gridDim.x * 4) {
+        advance(ok_next, v_next);
+        request(ok_next, v_next, nxt);
         half8 bf[2], bl[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            half8 raw = p[2 * ks + h];
+            half8 raw = cur[ks];
             if constexpr (SPLIT) {
-                const half8 rlo = p[C / 8 + 2 * ks + h];
+                const half8 rlo = cur[2 + ks];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     float y = (float)raw[j] + (float)rlo[j];
@@ -680,6 +712,10 @@ __global__ void __launch_bounds__(256) heads_kernel(HeadArgs a) {
                 ob[4 * a.n + v] = (t16)sk::sigmoid_fast(acc[0]);
             }
         }
+        ok = ok_next;
+        v = v_next;
+#pragma unroll
+        for (int k = 0; k < kPieces; ++k) cur[k] = nxt[k];
     }
 }
 

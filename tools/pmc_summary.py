@@ -70,7 +70,7 @@ def sq(sdir, cmd):
     return out
 
 
-STAGE_KERNELS = {"gate_dilate_scatter": ("gate_dilate_scatter_kernel",),
+STAGE_KERNELS = {"gate_dilate_scatter": ("gate_dilate_scatter_kernel", "gate_dilate_scatter_words_kernel"),
                  "ccl": ("ccl_", "ccl16_"),
                  "follow_assign": ("follow_assign_kernel", "follow_assign2_kernel"),
                  "renumber": ("first_seen_kernel", "mark_kernel", "chunk_popc_kernel", "chunk_scan_kernel", "word_prefix_kernel",
