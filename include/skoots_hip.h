@@ -1162,6 +1162,38 @@ int sk_local_thickness_paint(const double* dist2, int X, int Y, int Z, double wx
                              const int64_t* centres, int64_t n_centres, double* thick2, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Contacts between instances (ABI 23; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* sk_instance_contacts: which rows of an (X, Y, Z) int32 instance mask touch, and across how many voxel pairs.  labels,
+ * lut, max_id and N are those of sk_instance_stats; r(v) is the row of voxel v (1 .. N, 0 for background: ids <= 0, ids
+ * above max_id, rows outside 1 .. N).  Take two voxels p and q = p + d inside the volume, d in {-1, 0, 1}^3 and not
+ * zero, every unordered voxel pair once.  The pair is a contact of class
+ *   0, 1, 2   d has one nonzero component, x / y / z: a shared face with its normal along that axis;
+ *   3, 4, 5   two nonzero components, x and y / x and z / y and z: a shared edge;
+ *   6         three: a shared corner.
+ * connectivity 6 counts the classes 0 .. 2, 18 the classes 0 .. 5, 26 all seven; the others stay 0.  A contact counts
+ * when r(p) != r(q) and both rows are positive; with background = 1 also when exactly one of them is.  It is booked
+ * under (lo, hi) = (min, max) of the two rows.  rows receives one row of 9 int64 per distinct (lo, hi) that has a
+ * contact -- lo, hi, c0 .. c6 -- in no particular order, and counts[0] their number.
+ * The pairs are collected in an open-addressing table of `capacity` slots (a power of two) in `workspace`
+ * (sk_instance_contacts_workspace_bytes(capacity) bytes, 0 for a capacity that is not in [1, 2^40]); rows holds
+ * capacity rows.  A key that finds no slot within a bounded number of probes is refused for the whole launch: nothing
+ * is written for it, and every refused insertion adds 1 to counts[1].  counts[1] == 0 says that rows is complete and
+ * exact, and then the set of rows is the same on every run; otherwise counts[0] + counts[1] is at least the number of
+ * distinct pairs, and the caller repeats the call with a larger table (validate/lib.py: instance_contacts).  A refusal is
+ * never a fault.  Integer atomics only; one pass over the mask and one over the table, no workgroup waits for another.
+ * Checked before anything is launched or written (SK_ERR_ARG): extents, N and max_id not negative, X Y Z < 2^62,
+ * connectivity in {6, 18, 26}, background in {0, 1}, capacity a power of two in [1, 2^40], workspace_bytes at least the
+ * query's, no NULL pointer, pointers aligned to their elements.  An empty volume or N == 0 writes counts = {0, 0} and
+ * returns SK_OK (labels and lut are not looked at).  sk_instance_contacts_row_values() = 9. */
+int sk_instance_contacts_row_values(void);
+size_t sk_instance_contacts_workspace_bytes(int64_t capacity);
+int sk_instance_contacts(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                         int connectivity, int background, int64_t* rows, int64_t capacity, int64_t* counts,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

@@ -210,6 +210,9 @@ _SIGS = {
     "sk_nearest_label": (i32, [vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp,
                                vp, vp, vp]),
     "sk_local_thickness_paint": (i32, [vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, i64, vp, vp]),
+    "sk_instance_contacts_row_values": (i32, []),
+    "sk_instance_contacts_workspace_bytes": (sz, [i64]),
+    "sk_instance_contacts": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i64, vp, vp, sz, vp]),
 }
 
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and

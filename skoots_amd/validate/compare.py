@@ -28,6 +28,10 @@ of the largest ball inside its instance that holds it (``sk_local_thickness_pain
 closed, the Euler characteristic (``sk_instance_mesh_count``) -- and ``--save-meshes`` writes the
 meshes of ``lib.instance_meshes`` into one PLY file.
 
+``contacts=6`` / ``18`` / ``26`` / ``--contacts`` adds who touches whom: the table of touching pairs with their shared
+faces, edges and corners from one kernel pass (``sk_instance_contacts``), per instance its neighbours and
+the share of its surface that lies against them, and ``<mask>_contacts.csv``, one row per pair.
+
 ``compare(ground_truth, predictions)`` / ``--ground-truth GT`` matches every ground-truth instance to a predicted one
 by IoU and measures the pair: overlap, volume and centroid differences, and the distances between the two voxel
 surfaces -- Hausdorff, its 95th percentile, average symmetric surface distance, surface Dice -- from an exact
@@ -45,8 +49,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .lib import (check_shape, id_rows, instance_local_thickness, instance_mesh_cells, instance_mesh_counts,
-                  instance_meshes, instance_skeleton_graph, instance_sums, instance_thickness)
+from .lib import (check_shape, id_rows, instance_contacts, instance_local_thickness, instance_mesh_cells,
+                  instance_mesh_counts, instance_meshes, instance_skeleton_graph, instance_sums, instance_thickness)
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
@@ -63,6 +67,10 @@ MESH_MODES = (None, "open", "closed")
 PIECES_COLUMNS = "pieces,largest_piece_voxels"           # appended with --pieces
 PIECES_MODES = (None, 6, 18, 26)
 LOCAL_THICKNESS_COLUMNS = "local_radius_mean,local_radius_std,local_radius_min"  # appended with --local-thickness
+CONTACT_COLUMNS = "neighbours,contact_area,contact_fraction,largest_contact_id,largest_contact_area"  # --contacts
+CONTACT_MODES = (None, 6, 18, 26)
+CONTACT_CSV_COLUMNS = ("id_a,id_b,faces_x,faces_y,faces_z,edges_xy,edges_xz,edges_yz,corners,contact_area,fraction_a,"
+                       "fraction_b")
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -275,10 +283,91 @@ def pieces_columns(table: Tensor, ids) -> Dict[str, Tensor]:
     return {"pieces": torch.from_numpy(count), "largest_piece_voxels": torch.from_numpy(largest)}
 
 
+def _contact_table(table) -> np.ndarray:
+    t = table.cpu().numpy() if isinstance(table, Tensor) else np.asarray(table)
+    return t.astype(np.int64).reshape(-1, 9) if t.size else np.zeros((0, 9), np.int64)
+
+
+def contact_area(table, spacing=(1.0, 1.0, 1.0)) -> np.ndarray:
+    """(P) float64: the face-contact area of every row of a (P, 9) contact table (``lo, hi, c0 .. c6``) at the voxel
+    spacing, ``c0 sy sz + c1 sx sz + c2 sx sy`` -- ``derive``'s expression for ``face_area``, so an instance wholly
+    enclosed by another has a fraction of exactly 1.  Edge and corner contacts have no area.  The one place the area is
+    computed: the dict, both CSV files and ``utils.merge`` call it, so they agree to the last bit."""
+    sx, sy, sz = _spacing(spacing)
+    t = _contact_table(table).astype(np.float64)
+    return t[:, 2] * (sy * sz) + t[:, 3] * (sx * sz) + t[:, 4] * (sx * sy)
+
+
+def _contact_pairs(table, ids, face_area, spacing):
+    """(t, ia, ib, area, fa): the rows of the table between two instances (a row with id 0, the background, is left
+    out), the positions of their two ids in ``ids``, their contact areas and the (N) face areas as float64."""
+    ids = np.asarray(ids.cpu() if isinstance(ids, Tensor) else ids, dtype=np.int64).reshape(-1)
+    fa = np.asarray(face_area.cpu() if isinstance(face_area, Tensor) else face_area, dtype=np.float64).reshape(-1)
+    if fa.size != ids.size:
+        raise ValueError(f"face_area has {fa.size} values for {ids.size} ids")
+    t = _contact_table(table)
+    t = t[t[:, 0] != 0]
+    ia, ib = np.searchsorted(ids, t[:, 0]), np.searchsorted(ids, t[:, 1])
+    if t.shape[0] and (max(ia.max(), ib.max()) >= ids.size or not np.array_equal(ids[ia], t[:, 0])
+                       or not np.array_equal(ids[ib], t[:, 1])):
+        raise ValueError("the table names an id that is not among ids")
+    return t, ia, ib, contact_area(t, spacing), fa
+
+
+def contact_columns(table, ids, face_area, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor]:
+    """The contact columns (host tensors, one row per id of ``ids``, ascending) from the (P, 9) contact table with ids in
+    its first two columns (``stats_per_instance``'s ``contact_table``) and the (N) ``face_area`` of ``derive``:
+
+    ``neighbours`` int64: the distinct instances the id touches at the table's connectivity.  ``contact_area`` float64:
+    its face-contact area (``contact_area``) summed over the partners in ascending order of their ids.
+    ``contact_fraction`` = ``contact_area / face_area``: the share of the instance's exposed faces that lie against
+    another instance (the rest faces background or the volume's border).  ``largest_contact_id`` int64 and
+    ``largest_contact_area`` float64: the partner with the largest face-contact area, the smaller id on a tie; 0 and 0.0
+    when no partner shares a face.  Rows of the table against the background (id 0) are ignored."""
+    t, ia, ib, area, fa = _contact_pairs(table, ids, face_area, spacing)
+    n = fa.size
+    me = np.concatenate((ia, ib))
+    partner = np.concatenate((t[:, 1], t[:, 0]))
+    ar = np.concatenate((area, area))
+    neighbours = np.zeros(n, np.int64)
+    np.add.at(neighbours, me, 1)
+    total = np.zeros(n, np.float64)
+    order = np.lexsort((partner, me))
+    np.add.at(total, me[order], ar[order])                   # unbuffered: one order, ascending partner id
+    best_id, best_area = np.zeros(n, np.int64), np.zeros(n, np.float64)
+    order = np.lexsort((partner, -ar, me))                   # per id: largest area first, then the smaller partner
+    first = order[np.concatenate(([True], me[order][1:] != me[order][:-1]))] if order.size else order
+    first = first[ar[first] > 0]
+    best_id[me[first]], best_area[me[first]] = partner[first], ar[first]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fraction = total / fa
+    return {"neighbours": torch.from_numpy(neighbours), "contact_area": torch.from_numpy(total),
+            "contact_fraction": torch.from_numpy(fraction), "largest_contact_id": torch.from_numpy(best_id),
+            "largest_contact_area": torch.from_numpy(best_area)}
+
+
+def format_contacts_csv(mask_path: str, table, ids, face_area, spacing=(1.0, 1.0, 1.0), connectivity: int = 6) -> str:
+    """The text of ``_contacts.csv``: two header lines (file; spacing and connectivity), the column names, and one row
+    per touching pair of instances sorted by ``(id_a, id_b)``: the seven counts of the (P, 9) contact table (ids in its
+    first two columns), the pair's ``contact_area`` and that area over the ``face_area`` of either side.  Floats are
+    printed with ``repr``.  A pure function of its arguments."""
+    spacing = _spacing(spacing)
+    t, ia, ib, area, fa = _contact_pairs(table, ids, face_area, spacing)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fr_a, fr_b = area / fa[ia], area / fa[ib]
+    lines = [f"Mask File: {mask_path}\n",
+             "Spacing: {} {} {} Connectivity: {}\n".format(*(repr(v) for v in spacing), int(connectivity)),
+             CONTACT_CSV_COLUMNS + "\n"]
+    for k in np.lexsort((t[:, 1], t[:, 0])).tolist():
+        lines.append(",".join([*(str(v) for v in t[k].tolist()), repr(float(area[k])), repr(float(fr_a[k])),
+                               repr(float(fr_b[k]))]) + "\n")
+    return "".join(lines)
+
+
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
                        skeleton: bool = False, thickness: Optional[str] = None,
                        mesh: Optional[str] = None, pieces: Optional[int] = None,
-                       local_thickness: Optional[str] = None) -> Dict[str, Tensor]:
+                       local_thickness: Optional[str] = None, contacts: Optional[int] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -320,7 +409,14 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     radius of the largest ball inside its instance that holds it (``lib.instance_local_thickness``; the modes are those
     of ``thickness``, and when both name the same mode the distance transform runs once), ``max_dist2`` if ``thickness``
     did not add it, and ``local_radius_mean``, ``local_radius_std``, ``local_radius_min`` (``local_thickness_columns``,
-    DESIGN.md §28)."""
+    DESIGN.md §28).
+
+    ``contacts=6``, ``18`` or ``26`` adds ``contact_table`` (P, 9) int64 -- one row ``id_a, id_b, c0 .. c6`` per pair of
+    instances that touch at that connectivity, ``id_a < id_b``, sorted, from ``lib.instance_contacts`` -- and the
+    columns of ``contact_columns``: ``neighbours``, ``contact_area``, ``contact_fraction``, ``largest_contact_id``,
+    ``largest_contact_area``."""
+    if contacts not in CONTACT_MODES or isinstance(contacts, bool):
+        raise ValueError(f"contacts must be one of {CONTACT_MODES}, got {contacts!r}")
     if local_thickness not in THICKNESS_MODES:
         raise ValueError(f"local_thickness must be one of {THICKNESS_MODES}, got {local_thickness!r}")
     if pieces not in PIECES_MODES or isinstance(pieces, bool):
@@ -366,6 +462,11 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         out["thick2"] = thick2
         out.setdefault("max_dist2", max_d2)
         out.update({k: v.to(sums.device) for k, v in local_thickness_columns(table, int(ids.numel())).items()})
+    if contacts is not None:
+        table = instance_contacts(x, contacts, False, rows)[1]
+        table = torch.cat((ids[table[:, :2] - 1], table[:, 2:]), 1)      # rows 1..N -> ids; no background rows here
+        out["contact_table"] = table
+        out.update({k: v.to(sums.device) for k, v in contact_columns(table, ids, out["face_area"], spacing).items()})
     return out
 
 
@@ -499,7 +600,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                min_voxels: int = 1, mesh_cells: Optional[Tensor] = None,
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
-               mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None) -> str:
+               mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None,
+               contact_table=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -513,7 +615,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     of closed mode.  With ``piece_table`` (the (P, 6) table of ``label_components``) ``pieces,largest_piece_voxels``
     follow behind everything else; without it the text is byte for byte what it was before they existed.  With
     ``thickness_table`` (the (K, 3) table of ``instance_local_thickness``) ``local_radius_mean,local_radius_std,
-    local_radius_min`` follow behind all of that, under the same rule."""
+    local_radius_min`` follow behind all of that, under the same rule.  With ``contact_table`` (the (P, 9) table of
+    ``stats_per_instance(contacts=...)``, ids in its first two columns) ``neighbours,contact_area,contact_fraction,
+    largest_contact_id,largest_contact_area`` follow last, under the same rule again."""
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
@@ -533,6 +637,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
     if thickness_table is not None:
         d.update(local_thickness_columns(thickness_table, len(ids)))
+    if contact_table is not None:
+        d.update(contact_columns(contact_table, ids, d["face_area"], spacing))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
@@ -540,7 +646,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + THICKNESS_COLUMNS if max_dist2 is not None else "") +
              ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") +
              "".join("," + k for k in mesh_names) + ("," + PIECES_COLUMNS if piece_table is not None else "") +
-             ("," + LOCAL_THICKNESS_COLUMNS if thickness_table is not None else "") + "\n"]
+             ("," + LOCAL_THICKNESS_COLUMNS if thickness_table is not None else "") +
+             ("," + CONTACT_COLUMNS if contact_table is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -561,6 +668,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
             cells += [d[k][i] for k in PIECES_COLUMNS.split(",")]
         if thickness_table is not None:
             cells += [repr(d[k][i]) for k in LOCAL_THICKNESS_COLUMNS.split(",")]
+        if contact_table is not None:
+            cells += [d["neighbours"][i], repr(d["contact_area"][i]), repr(d["contact_fraction"][i]),
+                      d["largest_contact_id"][i], repr(d["largest_contact_area"][i])]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -616,6 +726,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--pieces", type=int, default=None, choices=(6, 18, 26),
                         help="Append " + PIECES_COLUMNS + ": the connected pieces of every id at this connectivity and "
                              "the voxels of the largest (an id in several pieces is not one body)")
+    parser.add_argument("--contacts", type=int, default=None, choices=(6, 18, 26),
+                        help="Append " + CONTACT_COLUMNS + ": the instances every id touches at this connectivity and the "
+                             "area of the voxel faces it shares with them; also write <mask>_contacts.csv, one row per "
+                             "touching pair: " + CONTACT_CSV_COLUMNS)
     parser.add_argument("--ground-truth", type=str, default=None, metavar="GT",
                         help="Also write <mask>_compare.csv: the mask is a prediction and GT (.tif or .npy of the same "
                              "shape) the ground truth; one row per ground-truth instance with the predicted instance it "
@@ -684,12 +798,23 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         have = (dist2, max_d2) if args.thickness == args.local_thickness else None
         thickness_table, thick2 = instance_local_thickness(dev_mask, spacing, args.local_thickness == "closed", rows,
                                                            have)[1:3]
+    contact_table = None
+    if args.contacts:
+        contact_table = instance_contacts(dev_mask, args.contacts, False, rows)[1]
+        contact_table = torch.cat((ids[contact_table[:, :2] - 1], contact_table[:, 2:]), 1)      # rows 1..N -> ids
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
-                      max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table)
+                      max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table,
+                      contact_table)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
     print(f"File Written: {out_path}")
+    if args.contacts:
+        face_area = derive(sums.cpu(), boxes.cpu(), tuple(mask.shape[-3:]), spacing)["face_area"]
+        contacts_path = f"{os.path.splitext(args.mask)[0]}_contacts.csv"
+        with open(contacts_path, "w") as file:
+            file.write(format_contacts_csv(args.mask, contact_table, ids, face_area, spacing, args.contacts))
+        print(f"File Written: {contacts_path}")
     if args.save_skeletons:
         from ..lib import tiff
         # rows 1 .. N -> ids, 0 stays 0; (X, Y, Z) -> the mask's [Z, X, Y]

@@ -15,6 +15,8 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 ``instance_thickness`` is the exact distance transform of every instance and its maximum per instance.
 ``instance_local_thickness`` is the local thickness of every instance voxel and its distribution per instance
 (DESIGN.md §28).
+``instance_contacts`` says which instances touch and across how many shared faces, edges and corners, one row per pair
+(DESIGN.md §29).
 ``instance_surfaces``, ``surface_distances``, ``match_instances`` and ``pair_summaries`` are the parts of
 ``validate/compare.py: compare()``: every instance's surface voxels as sorted keys, the exact squared distance from
 every surface voxel of one instance to the surface of another for many pairs at once, the matching rule, and the
@@ -268,6 +270,69 @@ def instance_mesh_cells(x: Tensor, closed: bool = False, rows=None) -> Tuple[Ten
     _ffi.check(_ffi.lib.sk_instance_mesh_cells(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(class_of),
                                                n_classes, int(bool(closed)), _ffi.ptr(cells), _ffi.stream_ptr(dev)))
     return ids, cells
+
+
+CONTACT_CONNECTIVITIES = (6, 18, 26)
+N_CONTACT = 9                  # int64 values per row of sk_instance_contacts: lo, hi, c0 .. c6
+MAX_CONTACT_CAPACITY = 1 << 30
+
+
+def _pow2_at_least(n: int) -> int:
+    return 1 << max(int(n) - 1, 0).bit_length()
+
+
+def instance_contacts(x: Tensor, connectivity: int = 6, background: bool = False, rows=None,
+                      capacity=None) -> Tuple[Tensor, Tensor]:
+    """(ids (N) int64 ascending, table (P, 9) int64) of the positive ids of an (X, Y, Z) integer device tensor: which
+    instances touch and across how many voxel pairs, from ``sk_instance_contacts`` (include/skoots_hip.h has the
+    definition).  A row of ``table`` is ``lo, hi, c0 .. c6``: two ROWS of ``ids`` (1 .. N; 0 is the
+    background, which appears only with ``background=True``), ``lo < hi``, and the contacts between them by class --
+    shared faces with the normal along x / y / z, shared edges in the xy / xz / yz planes, shared corners.
+    ``connectivity`` 6 fills the faces, 18 the edges too, 26 all seven.  The table is sorted by ``(lo, hi)`` with
+    torch, so two runs give equal tensors.  ``rows`` is ``id_rows(x)`` when the caller already has it.
+
+    The kernel collects the pairs in a hash table of ``capacity`` slots, a power of two; ``None`` starts at the next
+    power of two >= ``max(1024, 8 N)``, a given value is where the search STARTS.  After the launch the function reads
+    the two counters back; if insertions were refused it runs again at the next power of two >=
+    ``2 * (stored + refused)`` -- at least twice the distinct pairs, and never more than twice the pairs the mask can
+    hold -- and raises ``RuntimeError`` rather than go past 2^30 slots."""
+    assert _ffi.lib.sk_instance_contacts_row_values() == N_CONTACT
+    if connectivity not in CONTACT_CONNECTIVITIES or isinstance(connectivity, bool):
+        raise ValueError(f"connectivity must be one of {CONTACT_CONNECTIVITIES}, got {connectivity!r}")
+    x, rows = id_rows(x) if rows is None else rows
+    X, Y, Z = (int(v) for v in x.shape)
+    if X * Y * Z >= 2 ** 62:
+        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure: X*Y*Z must stay below 2^62")
+    dev = x.device
+    if rows is None:
+        return (torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty((0, N_CONTACT), dtype=torch.int64, device=dev))
+    a, ids, lut, max_id = rows
+    N = int(ids.numel())
+    if capacity is None:
+        capacity = _pow2_at_least(max(1024, 8 * N))
+    capacity = int(capacity)
+    if capacity < 1 or capacity & (capacity - 1):
+        raise ValueError(f"capacity must be a power of two >= 1, got {capacity}")
+    most = min((N + 1) * N // 2, 13 * X * Y * Z)             # distinct pairs the mask can hold, background included
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    while True:
+        if capacity > MAX_CONTACT_CAPACITY:
+            raise RuntimeError(f"instance_contacts: the pair table would need {capacity} slots, more than 2^30")
+        ws_bytes = int(_ffi.lib.sk_instance_contacts_workspace_bytes(capacity))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((capacity, N_CONTACT), dtype=torch.int64, device=dev)
+        _ffi.check(_ffi.lib.sk_instance_contacts(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, int(connectivity),
+                                                 int(bool(background)), _ffi.ptr(out), capacity, _ffi.ptr(counts),
+                                                 _ffi.ptr(ws), ws_bytes, _ffi.stream_ptr(dev)))
+        stored, refused = (int(v) for v in counts.tolist())
+        if refused == 0:
+            break
+        del ws, out
+        capacity = max(2 * capacity, _pow2_at_least(2 * min(stored + refused, most)))
+    table = out[:stored]
+    order = torch.argsort(table[:, 0] * (N + 1) + table[:, 1])     # lo, hi <= N: one int64 key
+    return ids, table[order].contiguous()
 
 
 MESH_BUDGET = 4 << 30          # bytes of vertex and triangle records instance_meshes may ask for
