@@ -201,7 +201,7 @@ typedef struct sk_conv_src {
  * sk_conv3d_pack_weight_host; bias (cout) fp32; out (B, ox, oy, oz, cout) fp16 raw.
  * gn_partial: (B, sk_conv3d_num_blocks, cout/4, 2) fp32 per-block (sum, sumsq) per channel quad, or NULL.  What is
  * summed: ksize 3 (conv3_px_kernel, conv3_m16_kernel, conv3_kernel) the values as STORED, i.e. the results rounded to 16
- * bits -- the statistics of the tensor the GroupNorm pass reads; ksize 1 / 2 (gather_gemm_kernel, down2_act_kernel) the
+ * bits -- the statistics of the tensor the GroupNorm pass reads; ksize 1 / 2 (gather_gemm_kernel, pointwise_lds_kernel, down2_act_kernel) the
  * fp32 accumulators; sk_conv3d_split, sk_conv3d_box_split, sk_conv3d_mix8 and the split / mix8 down convs the fp32
  * accumulators for every ksize (tests/test_hip_conv16_exact.py tells the two apart).  zero_page: 4 KiB; bytes [0, 1024) must
  * be zero and stay zero (source of the halo / padding lanes of the LDS-DMA), bytes
@@ -288,6 +288,26 @@ int64_t sk_conv3d_pack_weight_upfold_mix8_host(const float* w_host, int cout, in
 
 /* Rows of gn_partial per batch item that sk_conv3d writes for this output shape. */
 int sk_conv3d_num_blocks(int B, int ox, int oy, int oz, int cout, int ksize);
+
+/* HOST (ABI 24; no GPU needed): which kernel a conv launch runs, and with what geometry -- the answer of the one function
+ * the launches themselves ask.  family: SK_CONV_ENTRY for sk_conv3d, _box, _split, _box_split and _mix8, SK_CONV_ENTRY_DOWN_ACT
+ * for sk_conv3d_down_act, _split and _mix8 (srcs[0].c = cin, ksize 2).  Of srcs only c, upsample and affine != NULL are read.
+ * SK_ERR_ARG, with the launch's own message, for a shape the launch refuses.  name: the instantiation, e.g. "px",
+ * "m16<4,3,2>", "conv3<64,3,split>", "down2<128,64>", "gather<32,2>", "pointwise<32,64>".  The plan fields are those of the
+ * 3x3x3 kernels (zero for ksize 1 / 2); grid workgroups of 256 threads with lds bytes of dynamic LDS. */
+enum { SK_CONV_FP16 = 0, SK_CONV_SPLIT = 1, SK_CONV_MIX8 = 2 };
+enum { SK_CONV_ENTRY = 0, SK_CONV_ENTRY_DOWN_ACT = 1 };
+typedef struct sk_conv_route {
+    char name[32];
+    int mode, tz, nzc, pitch, nposp, npatch, xc, nxc, xs;
+    int64_t plan_lds;     /* the plane ring of the plan; lds adds what the kernel keeps behind it */
+    int num_blocks;       /* rows of gn_partial per batch item: sk_conv3d_num_blocks */
+    int64_t grid, lds;
+} sk_conv_route;
+int sk_conv3d_route(int family, int precision, const sk_conv_src* srcs, int n_src, int B, int ox, int oy, int oz,
+                    int cout, int ksize, sk_conv_route* route);
+/* The i-th kernel name a launch of this precision can reach in the release build, NULL past the end. */
+const char* sk_conv3d_route_name(int precision, int i);
 
 /* HOST: torch-layout weight (cout, cin, k, k, k) fp32 -> MFMA A-fragment order fp16.
  * Returns the bytes needed / written (dst_host == NULL only queries). */
@@ -512,6 +532,25 @@ int sk_train_conv_wgrad(const sk_conv_src* srcs, int n_src, const float* dy, int
                         float* workspace, void* stream);
 int64_t sk_train_conv_wgrad_workspace_floats(int B, int ox, int oy, int oz, int cout, int cin,
                                              int ksize);
+
+/* HOST (ABI 24; no GPU needed): which kernel a weight-gradient launch runs and how it cuts the work -- the answer of the one
+ * function that sk_train_conv_wgrad (SK_WGRAD_FP32), sk_train_conv_wgrad_f16 (SK_WGRAD_F16; has_zero_page: zero_page != NULL)
+ * and sk_train_stem_wgrad_f16 (SK_WGRAD_STEM_F16: only B and the extents are read) ask themselves.  Of srcs only c and upsample
+ * are read.  name: e.g. "wgrad<9>", "wgrad16x", "wgrad16t<8>", "wgrad_stem16".  nchunk partial rows (nchunk_b voxel chunks of
+ * `chunk` voxels per batch item; for "wgrad16x" its own count nchunk_x of 16 x 16 footprints x nxs segments of xseg planes),
+ * ngroup tap groups, ncol_chunk columns a chunk of "wgrad16y"; workspace_floats: sk_train_conv_wgrad_workspace_floats. */
+enum { SK_WGRAD_FP32 = 0, SK_WGRAD_F16 = 1, SK_WGRAD_STEM_F16 = 2 };
+typedef struct sk_wgrad_route {
+    char name[32];
+    int nchunk, nchunk_b;
+    int64_t chunk;
+    int ngroup, nchunk_x, nxs, xseg, ncol_chunk;
+    int64_t grid, workspace_floats;
+} sk_wgrad_route;
+int sk_train_conv_wgrad_route(int entry, const sk_conv_src* srcs, int n_src, int B, int ox, int oy, int oz, int cout,
+                              int ksize, int has_zero_page, sk_wgrad_route* route);
+/* The i-th kernel name the entry can reach in the release build, NULL past the end. */
+const char* sk_train_conv_wgrad_route_name(int entry, int i);
 
 /* Mixed-precision pieces (TrainUNet precision="mixed"): fp16 copies feed the fp16 MFMA kernels.
  * sk_train_absmax_scale: scale (3 floats, device) <- [2^k, 2^-k, scratch] with max|x| * 2^k in [2^12, 2^13).

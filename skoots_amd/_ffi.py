@@ -44,6 +44,20 @@ class ConvSrc(C.Structure):
     _fields_ = [("data", vp), ("affine", vp), ("c", i32), ("upsample", i32)]
 
 
+class ConvRoute(C.Structure):
+    """sk_conv_route (include/skoots_hip.h)."""
+    _fields_ = [("name", C.c_char * 32)] + \
+               [(n, i32) for n in ("mode", "tz", "nzc", "pitch", "nposp", "npatch", "xc", "nxc", "xs")] + \
+               [("plan_lds", i64), ("num_blocks", i32), ("grid", i64), ("lds", i64)]
+
+
+class WgradRoute(C.Structure):
+    """sk_wgrad_route (include/skoots_hip.h)."""
+    _fields_ = [("name", C.c_char * 32), ("nchunk", i32), ("nchunk_b", i32), ("chunk", i64)] + \
+               [(n, i32) for n in ("ngroup", "nchunk_x", "nxs", "xseg", "ncol_chunk")] + \
+               [("grid", i64), ("workspace_floats", i64)]
+
+
 class AugParams(C.Structure):
     """sk_aug_params (include/skoots_hip.h)."""
     _fields_ = [(n, i32) for n in ("src_x", "src_y", "src_z", "c1_x0", "c1_y0", "c1_z0", "w1", "h1", "d1",
@@ -87,6 +101,8 @@ _SIGS = {
     "sk_conv3d_down_act": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "sk_conv3d_down_act_split": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "sk_conv3d_num_blocks": (i32, [i32, i32, i32, i32, i32, i32]),
+    "sk_conv3d_route": (i32, [i32, i32, C.POINTER(ConvSrc), i32, i32, i32, i32, i32, i32, i32, C.POINTER(ConvRoute)]),
+    "sk_conv3d_route_name": (C.c_char_p, [i32, i32]),
     "sk_conv3d_pack_weight_host": (i64, [fp, i32, i32, i32, vp]),
     "sk_conv3d_upfold": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "sk_conv3d_upfold_split": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
@@ -135,6 +151,8 @@ _SIGS = {
     "sk_train_conv_dgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "sk_train_conv_wgrad": (i32, [C.POINTER(ConvSrc), i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "sk_train_conv_wgrad_workspace_floats": (i64, [i32, i32, i32, i32, i32, i32, i32]),
+    "sk_train_conv_wgrad_route": (i32, [i32, C.POINTER(ConvSrc), i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(WgradRoute)]),
+    "sk_train_conv_wgrad_route_name": (C.c_char_p, [i32, i32]),
     "sk_train_pack_weight": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "sk_train_interleave2": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
     "sk_train_gn_silu_f16": (i32, [vp, vp, vp, vp, i32, i64, i32, vp]),
@@ -218,14 +236,14 @@ _SIGS = {
 # bf16 twins (include/skoots_hip_bf16.h): the training-path sources are compiled a second time on bf16 storage and
 # exported with the suffix _bf16, same signatures
 BF16_TWINS = (
-    "sk_conv3d", "sk_conv3d_box", "sk_conv3d_box_split", "sk_conv3d_down_act", "sk_conv3d_down_act_split", "sk_conv3d_num_blocks", "sk_conv3d_pack_weight_host", "sk_conv3d_pack_weight_split_host",
+    "sk_conv3d", "sk_conv3d_box", "sk_conv3d_box_split", "sk_conv3d_down_act", "sk_conv3d_down_act_split", "sk_conv3d_num_blocks", "sk_conv3d_route", "sk_conv3d_route_name", "sk_conv3d_pack_weight_host", "sk_conv3d_pack_weight_split_host",
     "sk_conv3d_mix8", "sk_conv3d_down_act_mix8", "sk_conv3d_pack_weight_mix8_host", "sk_conv3d_stem_apply_mix8", "sk_groupnorm_silu_mix8",
     "sk_conv3d_split", "sk_conv3d_stem", "sk_conv3d_stem_raw", "sk_conv3d_stem_apply", "sk_conv3d_stem_apply_split",
     "sk_conv3d_stem_num_blocks", "sk_conv3d_stem_workspace_bytes", "sk_groupnorm_finalize",
     "sk_groupnorm_finalize_stats", "sk_groupnorm_silu", "sk_groupnorm_silu_split", "sk_heads", "sk_heads_split",
     "sk_baked_embed_to_prob", "sk_train_absmax_scale", "sk_train_adamw", "sk_train_cast_f16_f32",
-    "sk_train_cast_f32_f16", "sk_train_conv_wgrad", "sk_train_conv_wgrad_f16",
-    "sk_train_conv_wgrad_workspace_floats", "sk_train_gn_bwd_f16_workspace_floats", "sk_train_gn_bwd_num_blocks",
+    "sk_train_cast_f32_f16", "sk_train_conv_wgrad", "sk_train_conv_wgrad_f16", "sk_train_conv_wgrad_route",
+    "sk_train_conv_wgrad_route_name", "sk_train_conv_wgrad_workspace_floats", "sk_train_gn_bwd_f16_workspace_floats", "sk_train_gn_bwd_num_blocks",
     "sk_train_gn_bwd_workspace_floats", "sk_train_gn_silu", "sk_train_gn_silu_bwd", "sk_train_gn_silu_bwd_f16",
     "sk_train_gn_silu_bwd_f16h", "sk_train_gn_silu_f16", "sk_train_heads_fwd_f16", "sk_train_heads_wgrad_f16",
     "sk_train_heads_wgrad_workspace_floats", "sk_train_interleave2", "sk_train_interleave2_add16", "sk_train_interleave2_h",

@@ -31,6 +31,7 @@
 //     16 bits; split / mix8 forms and the ksize 1 / 2 kernels: of the fp32 accumulators); per-block partials are reduced in a fixed order by
 //     sk_groupnorm_finalize (deterministic, no float atomics).
 #include <stdlib.h>
+#include <string.h>
 
 #include <cmath>
 
@@ -2737,16 +2738,6 @@ int launch(void (*kern)(Args), unsigned grid, size_t lds, const Args& a, hipStre
     SK_CHECK_LAUNCH();
     return SK_OK;
 }
-// a 3x3x3 kernel: one workgroup per (batch item, x-chunk, patch)
-int launch_conv3_grid(void (*kern)(Conv3Args), size_t lds, const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    return launch(kern, (unsigned)(p.npatch * p.nxc * a.B), lds, a, stream);
-}
-
-template <int XS, int RES = 0, bool SPLIT = false, int WL = 0, bool MIX8 = false>
-int launch_conv3_m16(const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    // the ring + the tap rows kept in LDS behind it
-    return launch_conv3_grid(conv3_m16_kernel<32, XS, RES, SPLIT, WL, MIX8>, p.lds + (RES > 0 ? WL * 6144 : 0), a, p, stream);
-}
 
 // conv3_px_kernel is built for the plane geometry of the production tile: linear mode with 176 positions per plane
 // (Zt 16 .. 20: 128 + 2 Zt + 2 positions plus six padding positions -- bias, GroupNorm coefficients, the 256-byte zero window).  The first
@@ -2763,24 +2754,233 @@ static_assert(kPxLds <= 80 * 1024, "two workgroups per CU");
 // padding positions behind the `needed` ones: 2 (bias / GroupNorm coefficients) + the 4-position zero window
 bool conv3_px_covers(const Plan& p, int Zt) { return p.mode == 0 && p.nposp == kPxPositions && kPatch + 2 * Zt + 2 + 6 <= kPxPositions; }
 
-template <int COUT, int XS, int RES = 0, bool SPLIT = false, bool MIX8 = false>
-int launch_conv3(const Conv3Args& a, const Plan& p, hipStream_t stream) {
-    return launch_conv3_grid(conv3_kernel<COUT, XS, RES, SPLIT, MIX8>, p.lds, a, p, stream);
+// ------------------------------------------------------------------------------------------
+// The dispatch.  Which instantiation a launch runs is decided by conv3d_route and nowhere else; the tables below keep
+// every kernel's name (as tests/conv16_cases.py spells it: sk_conv3d_route_name) beside the pointer that is launched.
+// ------------------------------------------------------------------------------------------
+enum { kFp16 = SK_CONV_FP16, kSplit = SK_CONV_SPLIT, kMix8 = SK_CONV_MIX8, kPrecisions };
+constexpr size_t kTapRowBytes = 6144;   // one tap row of conv3_m16_kernel's fragments kept in LDS
+
+template <class Args>
+struct KernelRow {
+    const char* name;     // nullptr: the precision has no kernel in this slot
+    void (*kern)(Args);
+    size_t lds;           // dynamic LDS of the kernel's own ...
+    bool ring;            // ... on top of the plan's plane ring (the 3x3x3 kernels but px)
+};
+
+// the LDS-staged stride-2 pairs: [fp16 | split, which mix8 shares][cin 32 | 64]
+constexpr size_t kDownLds = 2 * 32768 + 4 * kPadBytes;
+const KernelRow<DownArgs> kDown[2 * 2] = {
+    {"down2<64,32>", down2_act_kernel<64, 32>, kDownLds, false},
+    {"down2<128,64>", down2_act_kernel<128, 64>, kDownLds, false},
+    {"down2<64,32,split>", down2_act_split_kernel<64, 32>, kDownLds, false},
+    {"down2<128,64,split>", down2_act_split_kernel<128, 64>, kDownLds, false},
+};
+
+// 3x3x3: [precision][slot]; conv3_m16_kernel<32, XS, RES, SPLIT, WL, MIX8>, conv3_kernel<COUT, XS, RES, SPLIT, MIX8>
+enum { kSlotPx, kSlotM16W2, kSlotM16W1, kSlotM16W0, kSlotM16x4, kSlotM16x3, kSlotC64x4, kSlotC64x3, kSlotC128, kConv3Slots };
+const KernelRow<Conv3Args> kConv3[kPrecisions * kConv3Slots] = {
+    {"px", conv3_px_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, false},
+    {"m16<4,3,2>", conv3_m16_kernel<32, 4, 3, false, 2>, 2 * kTapRowBytes, true},   // single chunk: 3 tap rows in registers,
+    {"m16<4,3,1>", conv3_m16_kernel<32, 4, 3, false, 1>, 1 * kTapRowBytes, true},   // 2 | 1 | 0 more in LDS behind the ring
+    {"m16<4,3,0>", conv3_m16_kernel<32, 4, 3>, 0, true},
+    {"m16<4>", conv3_m16_kernel<32, 4>, 0, true},
+    {"m16<3>", conv3_m16_kernel<32, 3>, 0, true},
+    {"conv3<64,4>", conv3_kernel<64, 4>, 0, true},
+    {"conv3<64,3>", conv3_kernel<64, 3>, 0, true},
+    {"conv3<128,2>", conv3_kernel<128, 2>, 0, true},
+    {}, {}, {}, {},
+    {"m16<4,split>", conv3_m16_kernel<32, 4, 0, true>, 0, true},
+    {"m16<3,split>", conv3_m16_kernel<32, 3, 0, true>, 0, true},
+    {"conv3<64,4,split>", conv3_kernel<64, 4, 0, true>, 0, true},
+    {"conv3<64,3,split>", conv3_kernel<64, 3, 0, true>, 0, true},
+    {"conv3<128,2,split>", conv3_kernel<128, 2, 0, true>, 0, true},
+    {"pxm", conv3_pxm_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, false},
+    {}, {}, {},
+    {"m16<4,mix8>", conv3_m16_kernel<32, 4, 0, true, 0, true>, 0, true},
+    {"m16<3,mix8>", conv3_m16_kernel<32, 3, 0, true, 0, true>, 0, true},
+    {"conv3<64,4,mix8>", conv3_kernel<64, 4, 0, true, true>, 0, true},
+    {"conv3<64,3,mix8>", conv3_kernel<64, 3, 0, true, true>, 0, true},
+    {"conv3<128,2,mix8>", conv3_kernel<128, 2, 0, true, true>, 0, true},
+};
+
+// ksize 1 / 2: [cout 32 | 64 | 128][slot]; gather_gemm_kernel<COUT, PV, depth, SPLIT> (depth 2: cin 32 at ksize 1, and
+// split -- twice the fragments in flight per step), pointwise_lds_kernel<COUT, CIN> (the channel reducers: nothing to gather)
+enum { kSlotGatherSplit, kSlotDeep, kSlotTwo, kSlotPointwise, kGatherSlots };
+const KernelRow<GatherArgs> kGather[3 * kGatherSlots] = {
+    {"gather<32,split>", gather_gemm_kernel<32, 2, 2, true>, 0, false},
+    {"gather<32,deep>", gather_gemm_kernel<32, 2, 4>, 0, false},
+    {"gather<32,2>", gather_gemm_kernel<32, 2, 2>, 0, false},
+    {"pointwise<32,64>", pointwise_lds_kernel<32, 64>, (size_t)256 * 2 * 64 + 4 * kPadBytes, false},
+    {"gather<64,split>", gather_gemm_kernel<64, 2, 2, true>, 0, false},
+    {"gather<64,deep>", gather_gemm_kernel<64, 2, 4>, 0, false},
+    {"gather<64,2>", gather_gemm_kernel<64, 2, 2>, 0, false},
+    {"pointwise<64,128>", pointwise_lds_kernel<64, 128>, (size_t)256 * 2 * 128 + 4 * kPadBytes, false},
+    {"gather<128,split>", gather_gemm_kernel<128, 1, 2, true>, 0, false},
+    {"gather<128,deep>", gather_gemm_kernel<128, 1, 4>, 0, false},
+    {"gather<128,2>", gather_gemm_kernel<128, 1, 2>, 0, false},
+    {},
+};
+
+struct RouteQuery {
+    int family;      // SK_CONV_ENTRY (sk_conv3d*) | SK_CONV_ENTRY_DOWN_ACT (sk_conv3d_down_act*)
+    int precision;
+    int n_src;
+    struct { int c, upsample, raw; } src[2];
+    int B, ox, oy, oz, cout, ksize;
+};
+
+enum { kTableConv3, kTableGather, kTableDown };
+struct Route {
+    int table, row;
+    Plan plan;       // ksize 3
+    int nblk;        // rows of gn_partial per batch item
+    unsigned grid;
+    size_t lds;
+    int ablate;      // -DSK_TUNING builds: SK_CONV_ABLATE, which also keeps a single-chunk layer off m16<4,3,*>
+};
+
+template <class Args>
+void route_to(Route& r, int table, int row, const KernelRow<Args>& k, int B) {
+    r.table = table;
+    r.row = row;
+    r.grid = (unsigned)(r.nblk * B);
+    r.lds = k.lds + (k.ring ? r.plan.lds : 0);
+}
+
+// Pure host code: shapes in, the launch's kernel and geometry out; SK_ERR_ARG with the message for a shape no kernel takes.
+int conv3d_route(const RouteQuery& q, Route& r) {
+    r = Route{};
+    const bool split = q.precision != kFp16, mix8 = q.precision == kMix8;
+    const int pv = q.cout == 128 ? 1 : 2;   // ksize 1 / 2: 128 pv voxels per block
+    const long long nv = (long long)q.ox * q.oy * q.oz;
+    if (q.family == SK_CONV_ENTRY_DOWN_ACT) {
+        const int cin = q.src[0].c;
+        SK_CHECK_ARG((cin == 32 && q.cout == 64) || (cin == 64 && q.cout == 128), "down conv: (cin, cout) must be (32, 64) or (64, 128)");
+        r.nblk = (int)((nv + 128 * pv - 1) / (128 * pv));   // 256 (cout 64) / 128 (cout 128) voxels per block: NV
+        const int row = 2 * split + (cin == 64);
+        route_to(r, kTableDown, row, kDown[row], q.B);
+        return SK_OK;
+    }
+    SK_CHECK_ARG(q.n_src == 1 || q.n_src == 2, "sk_conv3d: n_src must be 1 or 2");
+    SK_CHECK_ARG(q.B > 0 && q.ox > 0 && q.oy > 0 && q.oz > 0, "sk_conv3d: bad output extents");
+    SK_CHECK_ARG(q.cout == 32 || q.cout == 64 || q.cout == 128, "sk_conv3d: cout must be 32, 64 or 128");
+    if (q.ksize == 3) {
+        int cin = 0;
+        for (int i = 0; i < q.n_src; ++i) {
+            SK_CHECK_ARG(q.src[i].c > 0 && q.src[i].c % kChunk == 0, "sk_conv3d: source %d must have a multiple of 32 channels", i);
+            SK_CHECK_ARG(!q.src[i].raw || !split, "sk_conv3d_split: sources must be activated (affine must be NULL)");
+            SK_CHECK_ARG(!q.src[i].raw || q.cout == 32,
+                         "sk_conv3d: ksize 3 activates a RAW source in LDS only in the COUT 32 kernel (for wider layers the "
+                         "separate pass is cheaper: activate the tensor with sk_groupnorm_silu first)");
+            SK_CHECK_ARG(i == 1 || !q.src[i].upsample, "sk_conv3d: only the second source may be upsampled");
+            SK_CHECK_ARG(!q.src[i].upsample || (q.ox % 2 == 0 && q.oy % 2 == 0 && q.oz % 2 == 0),
+                         "sk_conv3d: upsampled source needs even output extents");
+            cin += q.src[i].c;
+        }
+        // phase chunks of a step: one per 32 channels, split three, mix8 two (conv3d_impl fills them in)
+        const int per = mix8 ? 2 : split ? 3 : 1;
+        SK_CHECK_ARG((cin / kChunk - 1) * per + (split ? 3 : 1) <= kMaxChunks, "sk_conv3d: too many input channels (%d)", cin);
+        Plan& p = r.plan;
+        SK_CHECK_ARG(make_plan(p, q.ox, q.oy, q.oz, q.cout, q.B) == 0, "sk_conv3d: plane geometry (%d,%d) unsupported", q.oy, q.oz);
+        SK_CHECK_ARG(!mix8 || (cin == q.cout && q.n_src == 1 && !q.src[0].upsample),
+                     "sk_conv3d_mix8: one plain source with as many channels as the output (32 | 64 | 128)");
+        r.nblk = p.npatch * p.nxc;   // one workgroup per (batch item, x-chunk, patch)
+        const bool one_chunk = cin == kChunk;   // hence one source
+        bool px = q.precision != kSplit && one_chunk && !q.src[0].upsample && conv3_px_covers(p, q.oz);
+#ifdef SK_TUNING
+        if (getenv("SK_CONV_NO_PX")) px = false;   // A/B: the single-chunk COUT-32 layers on conv3_m16_kernel
+        if (const char* e = getenv("SK_CONV_ABLATE")) r.ablate = atoi(e);
+#endif
+        int slot;
+        if (q.cout == 128)
+            slot = kSlotC128;
+        else if (q.cout == 64)
+            slot = p.xs == 3 ? kSlotC64x3 : kSlotC64x4;
+        else if (px)
+            slot = kSlotPx;
+        else if (p.xs == 3)
+            slot = kSlotM16x3;
+        else if (q.precision == kFp16 && one_chunk && !r.ablate)   // as many tap rows in LDS as keep two workgroups on a CU
+            slot = p.lds + 2 * kTapRowBytes <= 80 * 1024 ? kSlotM16W2 : p.lds + kTapRowBytes <= 80 * 1024 ? kSlotM16W1 : kSlotM16W0;
+        else
+            slot = kSlotM16x4;
+        const int row = q.precision * kConv3Slots + slot;
+        route_to(r, kTableConv3, row, kConv3[row], q.B);
+        return SK_OK;
+    }
+    SK_CHECK_ARG(q.ksize == 1 || q.ksize == 2, "sk_conv3d: ksize must be 1, 2 or 3");
+    SK_CHECK_ARG(!mix8, "sk_conv3d_mix8: ksize must be 3");
+    SK_CHECK_ARG(q.n_src == 1 && !q.src[0].upsample, "sk_conv3d: ksize %d takes one plain source", q.ksize);
+    const int cin = q.src[0].c;
+    SK_CHECK_ARG(cin % 16 == 0, "sk_conv3d: cin must be a multiple of 16");
+    r.nblk = (int)((nv + 128 * pv - 1) / (128 * pv));
+    if (!split && q.ksize == 2 && ((cin == 32 && q.cout == 64) || (cin == 64 && q.cout == 128))) {
+        const int row = cin == 64;
+        route_to(r, kTableDown, row, kDown[row], q.B);
+        return SK_OK;
+    }
+    const int nsteps = q.ksize * q.ksize * q.ksize * (cin / 16);
+    SK_CHECK_ARG(cin <= 128 && nsteps % 2 == 0, "sk_conv3d: ksize %d needs 32 <= cin <= 128 (got %d)", q.ksize, cin);
+    int slot = split ? kSlotGatherSplit : nsteps % 4 == 0 ? kSlotDeep : kSlotTwo;
+    if (!split && q.ksize == 1 && ((cin == 64 && q.cout == 32) || (cin == 128 && q.cout == 64))) slot = kSlotPointwise;
+    const int row = (q.cout / 64) * kGatherSlots + slot;
+    route_to(r, kTableGather, row, kGather[row], q.B);
+    return SK_OK;
+}
+
+// the sources of a launch as the route function sees them
+int conv3d_query(RouteQuery& q, int family, int precision, const sk_conv_src* srcs, int n_src, int B, int ox, int oy, int oz,
+                 int cout, int ksize) {
+    SK_CHECK_ARG(srcs, "sk_conv3d: NULL pointer");
+    SK_CHECK_ARG(n_src == 1 || n_src == 2, "sk_conv3d: n_src must be 1 or 2");
+    q = RouteQuery{family, precision, n_src, {}, B, ox, oy, oz, cout, ksize};
+    for (int i = 0; i < n_src; ++i) {
+        q.src[i].c = srcs[i].c;
+        q.src[i].upsample = srcs[i].upsample ? 1 : 0;
+        q.src[i].raw = srcs[i].affine != nullptr;
+    }
+    return SK_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
+int sk_conv3d_route(int family, int precision, const sk_conv_src* srcs, int n_src, int B, int ox, int oy, int oz, int cout,
+                    int ksize, sk_conv_route* route) {
+    SK_CHECK_ARG(route, "sk_conv3d_route: NULL pointer");
+    SK_CHECK_ARG(precision >= 0 && precision < kPrecisions, "sk_conv3d_route: precision must be SK_CONV_FP16, _SPLIT or _MIX8");
+    RouteQuery q;
+    Route r;
+    if (const int e = conv3d_query(q, family, precision, srcs, n_src, B, ox, oy, oz, cout, ksize)) return e;
+    if (const int e = conv3d_route(q, r)) return e;
+    const Plan& p = r.plan;
+    const char* name = r.table == kTableConv3 ? kConv3[r.row].name : r.table == kTableGather ? kGather[r.row].name : kDown[r.row].name;
+    *route = sk_conv_route{{}, p.mode, p.TZ, p.nzc, p.pitch, p.nposp, p.npatch, p.XC, p.nxc, p.xs, (int64_t)p.lds,
+                           r.nblk, (int64_t)r.grid, (int64_t)r.lds};
+    strncpy(route->name, name, sizeof(route->name) - 1);
+    return SK_OK;
+}
+
+const char* sk_conv3d_route_name(int precision, int i) {
+    if (precision < 0 || precision >= kPrecisions || i < 0) return nullptr;
+    auto nth = [&i](const char* name, bool mine) { return name && mine && i-- == 0; };
+    for (int k = 0; k < kConv3Slots; ++k)
+        if (nth(kConv3[precision * kConv3Slots + k].name, true)) return kConv3[precision * kConv3Slots + k].name;
+    for (int k = 0; k < 3 * kGatherSlots; ++k)   // the split form serves sk_conv3d_split alone: mix8 has no ksize 1 / 2
+        if (nth(kGather[k].name, (k % kGatherSlots == kSlotGatherSplit) == (precision == kSplit) && precision != kMix8)) return kGather[k].name;
+    for (int k = 0; k < 4; ++k)
+        if (nth(kDown[k].name, (k >= 2) == (precision != kFp16))) return kDown[k].name;
+    return nullptr;
+}
+
 int sk_conv3d_num_blocks(int B, int ox, int oy, int oz, int cout, int ksize) {
-    if (ksize == 3) {
-        Plan p;
-        if (make_plan(p, ox, oy, oz, cout, B)) return -1;
-        return p.npatch * p.nxc;
-    }
-    int pv = cout == 128 ? 1 : 2;
-    long long nv = (long long)ox * oy * oz;
-    return (int)((nv + 128 * pv - 1) / (128 * pv));
+    // the row count depends on the output shape alone: ask for one plain 32-channel source, which every ksize takes
+    const RouteQuery q{SK_CONV_ENTRY, kFp16, 1, {{kChunk, 0, 0}}, B, ox, oy, oz, cout, ksize};
+    Route r;
+    return conv3d_route(q, r) == SK_OK ? r.nblk : -1;
 }
 
 int64_t sk_conv3d_pack_weight_host(const float* w, int cout, int cin, int ksize, void* dst) {
@@ -2834,12 +3034,15 @@ int64_t sk_conv3d_pack_weight_host(const float* w, int cout, int cin, int ksize,
     return nfrag * 1024;
 }
 
+// writeback 0: the input is activated or activated on the fly (sk_conv3d, ksize 2); 1 / 2: sk_conv3d_down_act* store it back
 static int launch_down2(const void* in, const float* affine, int writeback, const void* weight, const float* bias, void* out,
                         int B, int ox, int oy, int oz, int cin, int cout, float* gn_partial, void* zeros, hipStream_t stream,
-                        bool split = false) {
+                        int precision = kFp16) {
     SK_CHECK_ARG(in && weight && bias && out && zeros, "down conv: NULL pointer (the zero page is required)");
-    SK_CHECK_ARG((cin == 32 && cout == 64) || (cin == 64 && cout == 128), "down conv: (cin, cout) must be (32, 64) or (64, 128)");
     SK_CHECK_ARG(!writeback || affine, "down conv: write-back needs the affine of the raw input");
+    const RouteQuery q{SK_CONV_ENTRY_DOWN_ACT, precision, 1, {{cin, 0, affine != nullptr}}, B, ox, oy, oz, cout, 2};
+    Route r;
+    if (const int e = conv3d_route(q, r)) return e;
     DownArgs a{};
     a.in = (char*)in;
     a.affine = affine;
@@ -2853,219 +3056,150 @@ static int launch_down2(const void* in, const float* affine, int writeback, cons
     a.Yo = oy;
     a.Zo = oz;
     a.writeback = writeback;
-    a.nblk = sk_conv3d_num_blocks(B, ox, oy, oz, cout, 2);   // 256 (cout 64) / 128 (cout 128) voxels per block: NV
-    const int lds = 2 * 32768 + 4 * kPadBytes;
-    void (*kern)(DownArgs);
-    if (split)
-        kern = cin == 32 ? down2_act_split_kernel<64, 32> : down2_act_split_kernel<128, 64>;
-    else
-        kern = cin == 32 ? down2_act_kernel<64, 32> : down2_act_kernel<128, 64>;
-    return launch(kern, (unsigned)(a.nblk * B), lds, a, stream);
+    a.nblk = r.nblk;
+    return launch(kDown[r.row].kern, r.grid, r.lds, a, stream);
 }
 
 static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
                        int B, int ox, int oy, int oz, int cout, int ksize, float* gn_partial,
-                       void* zeros, void* stream_, const bool split, const int* store_box = nullptr,
-                       const bool mix8 = false, const int w8_scale_exp = 0) {
+                       void* zeros, void* stream_, const int precision, const int* store_box = nullptr,
+                       const int w8_scale_exp = 0) {
     hipStream_t stream = (hipStream_t)stream_;
+    const bool split = precision != kFp16, mix8 = precision == kMix8;
     const int lanes = split ? 2 : 1;   // fp16 values per logical channel in a voxel line: [hi | lo]
     SK_CHECK_ARG(srcs && weight && bias && out, "sk_conv3d: NULL pointer");
-    SK_CHECK_ARG(n_src == 1 || n_src == 2, "sk_conv3d: n_src must be 1 or 2");
-    SK_CHECK_ARG(B > 0 && ox > 0 && oy > 0 && oz > 0, "sk_conv3d: bad output extents");
-    SK_CHECK_ARG(cout == 32 || cout == 64 || cout == 128, "sk_conv3d: cout must be 32, 64 or 128");
-    if (ksize == 3) {
-        SK_CHECK_ARG(zeros, "sk_conv3d: zero page is NULL");
-        Conv3Args a{};
-        int cin = 0;
-        for (int i = 0; i < n_src; ++i) {
-            SK_CHECK_ARG(srcs[i].data && srcs[i].c > 0 && srcs[i].c % kChunk == 0,
-                         "sk_conv3d: source %d must have a multiple of 32 channels", i);
-            SK_CHECK_ARG(srcs[i].affine == nullptr || !split,
-                         "sk_conv3d_split: sources must be activated (affine must be NULL)");
-            SK_CHECK_ARG(srcs[i].affine == nullptr || cout == 32,
-                         "sk_conv3d: ksize 3 activates a RAW source in LDS only in the COUT 32 kernel (for wider layers the "
-                         "separate pass is cheaper: activate the tensor with sk_groupnorm_silu first)");
-            a.act[i] = srcs[i].affine;   // RAW source: activated in LDS by the lanes that stage it
-            SK_CHECK_ARG(i == 1 || !srcs[i].upsample, "sk_conv3d: only the second source may be upsampled");
-            int up = srcs[i].upsample ? 1 : 0;
-            SK_CHECK_ARG(!up || (ox % 2 == 0 && oy % 2 == 0 && oz % 2 == 0),
-                         "sk_conv3d: upsampled source needs even output extents");
-            int xs = up ? ox / 2 : ox, ys = up ? oy / 2 : oy, zs = up ? oz / 2 : oz;
-            a.src[i].data = (const char*)srcs[i].data;
-            a.src[i].C = srcs[i].c * lanes;     // halves per voxel line
-            a.src[i].up = up;
-            a.src[i].Ys = ys;
-            a.src[i].Zs = zs;
-            a.src[i].plane = (long long)ys * zs * srcs[i].c * lanes * 2;
-            a.src[i].batch = a.src[i].plane * xs;
-            cin += srcs[i].c;
-        }
-        if (n_src == 1) {
-            a.src[1] = a.src[0];
-            a.act[1] = a.act[0];
-        }
-        a.c0chunks = srcs[0].c / kChunk;
-        // phase chunks of a step.  Plain: the 32-channel chunks of the concatenated sources in order.  Split: per
-        // logical chunk three phases -- (x_hi, w_lo), (x_hi again: no DMA, w_hi), (x_lo, w_hi); the packed weight
-        // (sk_conv3d_pack_weight_split_host) holds the matching [lo, hi, hi] fragment sets in this order.
-        a.nchunks = 0;
-        for (int k = 0; k < cin / kChunk; ++k) {
-            const int si = k < a.c0chunks ? 0 : 1;
-            const unsigned off = (unsigned)(k - (si ? a.c0chunks : 0)) * kChunk * 2;
-            const unsigned lo_off = off + (unsigned)srcs[si].c * 2;
-            SK_CHECK_ARG(a.nchunks + (split ? 3 : 1) <= kMaxChunks, "sk_conv3d: too many input channels (%d)", cin);
-            if (!split) {
-                a.chinfo[a.nchunks++] = (unsigned)si | (off << 8);
-            } else if (mix8) {   // [hi fp16 | x8 | lo8] lines: the fp16 phase, then ONE fp8 phase over the 64 bytes behind the hi halves
-                a.chinfo[a.nchunks++] = (unsigned)si | (off << 8);
-                a.chinfo[a.nchunks++] = (unsigned)si | 4u | (lo_off << 8);
-            } else {
-                a.chinfo[a.nchunks++] = (unsigned)si | (off << 8);
-                a.chinfo[a.nchunks++] = (unsigned)si | 2u | (off << 8);
-                a.chinfo[a.nchunks++] = (unsigned)si | (lo_off << 8);
-            }
-        }
-        a.wpk = (const char*)weight;
-        a.bias = bias;
-        a.out = (char*)out;
-        a.partial = gn_partial;
-        a.zeros = (const char*)zeros;
-        a.B = B;
-        a.Xt = ox;
-        a.Yt = oy;
-        a.Zt = oz;
-        Plan p;
-        SK_CHECK_ARG(make_plan(p, ox, oy, oz, cout, B) == 0, "sk_conv3d: plane geometry (%d,%d) unsupported", oy, oz);
-        a.XC = p.XC;
-        a.nxc = p.nxc;
-        a.npatch = p.npatch;
-        a.mode = p.mode;
-        a.TZ = p.TZ;
-        a.nzc = p.nzc;
-        a.pitch = p.pitch;
-        a.nposp = p.nposp;
-        a.jstep = (p.mode == 1 && p.TZ == 16) ? p.pitch : 16;
-        // two-chunk layers only: with four chunks the reuse is 1/12 of the loads and measured +1.6 % time (COUT 128);
-        // split mode: the chunk triples carry their own reuse flags
-        a.alt = (!split && a.nchunks == 2) ? 1 : 0;
-        a.dbg = nullptr;
-#ifdef SK_TIMING
-        a.dbg = sk::timing_buffer();
-        if (const char* e = getenv("SK_CONV_DBG_OFF")) a.dbg_off = atoi(e);
-#endif
-        a.ablate = 0;
-#ifdef SK_TUNING
-        if (const char* e = getenv("SK_CONV_ABLATE")) a.ablate = atoi(e);
-#endif
-        a.has_box = 0;
-        if (store_box && cout == 32) {   // honoured by the COUT-32 kernels (conv3_px_kernel, conv3_m16_kernel); wider layers store everything
-            for (int k = 0; k < 3; ++k) {
-                a.box_lo[k] = store_box[k];
-                a.box_hi[k] = store_box[3 + k];
-                SK_CHECK_ARG(a.box_lo[k] >= 0 && a.box_lo[k] <= a.box_hi[k], "sk_conv3d_box: bad box on axis %d", k);
-            }
-            a.has_box = 1;
-        }
-        if (mix8) {
-            SK_CHECK_ARG(split && cin == cout && n_src == 1 && !srcs[0].upsample,
-                         "sk_conv3d_mix8: one plain source with as many channels as the output (32 | 64 | 128)");
-            SK_CHECK_ARG(w8_scale_exp >= 0 && w8_scale_exp < 64, "sk_conv3d_mix8: bad weight scale exponent %d", w8_scale_exp);
-            a.w8_off = mix8_fp16_bytes(cout, cin);
-            a.wpk_bytes = a.w8_off + mix8_fp8_bytes(cout, cin);
-            a.w8_scale = 0x01010101 * (127 - w8_scale_exp);
-            if (cout == 32) {
-                bool use_pxm = conv3_px_covers(p, oz);
-#ifdef SK_TUNING
-                if (getenv("SK_CONV_NO_PX")) use_pxm = false;   // A/B: conv3_m16_kernel's mix8 form
-#endif
-                if (use_pxm) return launch_conv3_grid(conv3_pxm_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, a, p, stream);
-                return p.xs == 3 ? launch_conv3_m16<3, 0, true, 0, true>(a, p, stream) : launch_conv3_m16<4, 0, true, 0, true>(a, p, stream);
-            }
-            if (cout == 64) return p.xs == 3 ? launch_conv3<64, 3, 0, true, true>(a, p, stream) : launch_conv3<64, 4, 0, true, true>(a, p, stream);
-            return launch_conv3<128, 2, 0, true, true>(a, p, stream);
-        }
-        if (split) {
-            if (cout == 32) return p.xs == 3 ? launch_conv3_m16<3, 0, true>(a, p, stream) : launch_conv3_m16<4, 0, true>(a, p, stream);
-            if (cout == 64) return p.xs == 3 ? launch_conv3<64, 3, 0, true>(a, p, stream) : launch_conv3<64, 4, 0, true>(a, p, stream);
-            return launch_conv3<128, 2, 0, true>(a, p, stream);
-        }
-        bool use_px = cout == 32 && a.nchunks == 1 && n_src == 1 && !srcs[0].upsample && conv3_px_covers(p, oz);
-#ifdef SK_TUNING
-        if (getenv("SK_CONV_NO_PX")) use_px = false;   // A/B: the single-chunk COUT-32 layers on conv3_m16_kernel
-#endif
-        if (use_px) return launch_conv3_grid(conv3_px_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, a, p, stream);
-        if (cout == 32) {   // 16x16x32 kernel
-            if (p.xs == 3) return launch_conv3_m16<3>(a, p, stream);
-            if (a.nchunks == 1 && !a.ablate) {   // single chunk: 3 tap rows in registers, 2 more in LDS where they fit
-                if (p.lds + 2 * 6144 <= 80 * 1024) return launch_conv3_m16<4, 3, false, 2>(a, p, stream);
-                if (p.lds + 1 * 6144 <= 80 * 1024) return launch_conv3_m16<4, 3, false, 1>(a, p, stream);   // the 8 x 16 rectangles
-                return launch_conv3_m16<4, 3>(a, p, stream);
-            }
-            return launch_conv3_m16<4>(a, p, stream);
-        }
-        if (cout == 64) return p.xs == 3 ? launch_conv3<64, 3>(a, p, stream) : launch_conv3<64, 4>(a, p, stream);
-        return launch_conv3<128, 2>(a, p, stream);
-    }
-    SK_CHECK_ARG(ksize == 1 || ksize == 2, "sk_conv3d: ksize must be 1, 2 or 3");
-    SK_CHECK_ARG(n_src == 1 && !srcs[0].upsample, "sk_conv3d: ksize %d takes one plain source", ksize);
-    SK_CHECK_ARG(srcs[0].c % 16 == 0, "sk_conv3d: cin must be a multiple of 16");
-    if (!split && ksize == 2 && ((srcs[0].c == 32 && cout == 64) || (srcs[0].c == 64 && cout == 128)))
+    SK_CHECK_ARG(ksize != 3 || zeros, "sk_conv3d: zero page is NULL");
+    RouteQuery q;
+    Route r;
+    if (const int e = conv3d_query(q, SK_CONV_ENTRY, precision, srcs, n_src, B, ox, oy, oz, cout, ksize)) return e;
+    if (const int e = conv3d_route(q, r)) return e;
+    if (r.table == kTableDown)   // the LDS-staged pairs, without write-back
         return launch_down2(srcs[0].data, srcs[0].affine, 0, weight, bias, out, B, ox, oy, oz, srcs[0].c, cout, gn_partial,
                             zeros, stream);
-    GatherArgs g{};
-    g.in = (const char*)srcs[0].data;
-    g.affine = srcs[0].affine;
-    g.wpk = (const char*)weight;
-    g.bias = bias;
-    g.out = (char*)out;
-    g.partial = gn_partial;
-    g.B = B;
-    g.Xo = ox;
-    g.Yo = oy;
-    g.Zo = oz;
-    g.Xi = ox * ksize;
-    g.Yi = oy * ksize;
-    g.Zi = oz * ksize;
-    g.Cin = srcs[0].c;
-    g.ksize = ksize;
-    g.nblk = sk_conv3d_num_blocks(B, ox, oy, oz, cout, ksize);
-    const int nsteps = ksize * ksize * ksize * (g.Cin / 16);
-    SK_CHECK_ARG(g.Cin <= 128 && nsteps % 2 == 0, "sk_conv3d: ksize %d needs 32 <= cin <= 128 (got %d)", ksize, g.Cin);
-    const bool deep = nsteps % 4 == 0;  // pipeline depth 4 (2 only for the 32-channel pointwise case)
-    void (*kern)(GatherArgs);
-    if (!split && ksize == 1 && ((g.Cin == 64 && cout == 32) || (g.Cin == 128 && cout == 64))) {   // the channel reducers: nothing to gather
-        kern = cout == 32 ? pointwise_lds_kernel<32, 64> : pointwise_lds_kernel<64, 128>;
-        return launch(kern, (unsigned)(g.nblk * B), (size_t)256 * 2 * g.Cin + 4 * kPadBytes, g, stream);
+    if (r.table == kTableGather) {
+        GatherArgs g{};
+        g.in = (const char*)srcs[0].data;
+        g.affine = srcs[0].affine;
+        g.wpk = (const char*)weight;
+        g.bias = bias;
+        g.out = (char*)out;
+        g.partial = gn_partial;
+        g.B = B;
+        g.Xo = ox;
+        g.Yo = oy;
+        g.Zo = oz;
+        g.Xi = ox * ksize;
+        g.Yi = oy * ksize;
+        g.Zi = oz * ksize;
+        g.Cin = srcs[0].c;
+        g.ksize = ksize;
+        g.nblk = r.nblk;
+        return launch(kGather[r.row].kern, r.grid, r.lds, g, stream);
     }
-    if (split)   // depth 2: twice the fragments in flight per step
-        kern = cout == 32 ? gather_gemm_kernel<32, 2, 2, true> : cout == 64 ? gather_gemm_kernel<64, 2, 2, true> : gather_gemm_kernel<128, 1, 2, true>;
-    else if (cout == 32)
-        kern = deep ? gather_gemm_kernel<32, 2, 4> : gather_gemm_kernel<32, 2, 2>;
-    else if (cout == 64)
-        kern = deep ? gather_gemm_kernel<64, 2, 4> : gather_gemm_kernel<64, 2, 2>;
-    else
-        kern = deep ? gather_gemm_kernel<128, 1, 4> : gather_gemm_kernel<128, 1, 2>;
-    return launch(kern, (unsigned)(g.nblk * B), 0, g, stream);
+    const Plan& p = r.plan;
+    Conv3Args a{};
+    int cin = 0;
+    for (int i = 0; i < n_src; ++i) {
+        SK_CHECK_ARG(srcs[i].data, "sk_conv3d: source %d must have a multiple of 32 channels", i);
+        a.act[i] = srcs[i].affine;   // RAW source: activated in LDS by the lanes that stage it
+        int up = srcs[i].upsample ? 1 : 0;
+        int xs = up ? ox / 2 : ox, ys = up ? oy / 2 : oy, zs = up ? oz / 2 : oz;
+        a.src[i].data = (const char*)srcs[i].data;
+        a.src[i].C = srcs[i].c * lanes;     // halves per voxel line
+        a.src[i].up = up;
+        a.src[i].Ys = ys;
+        a.src[i].Zs = zs;
+        a.src[i].plane = (long long)ys * zs * srcs[i].c * lanes * 2;
+        a.src[i].batch = a.src[i].plane * xs;
+        cin += srcs[i].c;
+    }
+    if (n_src == 1) {
+        a.src[1] = a.src[0];
+        a.act[1] = a.act[0];
+    }
+    a.c0chunks = srcs[0].c / kChunk;
+    // phase chunks of a step.  Plain: the 32-channel chunks of the concatenated sources in order.  Split: per
+    // logical chunk three phases -- (x_hi, w_lo), (x_hi again: no DMA, w_hi), (x_lo, w_hi); the packed weight
+    // (sk_conv3d_pack_weight_split_host) holds the matching [lo, hi, hi] fragment sets in this order.
+    a.nchunks = 0;
+    for (int k = 0; k < cin / kChunk; ++k) {
+        const int si = k < a.c0chunks ? 0 : 1;
+        const unsigned off = (unsigned)(k - (si ? a.c0chunks : 0)) * kChunk * 2;
+        const unsigned lo_off = off + (unsigned)srcs[si].c * 2;
+        if (!split) {
+            a.chinfo[a.nchunks++] = (unsigned)si | (off << 8);
+        } else if (mix8) {   // [hi fp16 | x8 | lo8] lines: the fp16 phase, then ONE fp8 phase over the 64 bytes behind the hi halves
+            a.chinfo[a.nchunks++] = (unsigned)si | (off << 8);
+            a.chinfo[a.nchunks++] = (unsigned)si | 4u | (lo_off << 8);
+        } else {
+            a.chinfo[a.nchunks++] = (unsigned)si | (off << 8);
+            a.chinfo[a.nchunks++] = (unsigned)si | 2u | (off << 8);
+            a.chinfo[a.nchunks++] = (unsigned)si | (lo_off << 8);
+        }
+    }
+    a.wpk = (const char*)weight;
+    a.bias = bias;
+    a.out = (char*)out;
+    a.partial = gn_partial;
+    a.zeros = (const char*)zeros;
+    a.B = B;
+    a.Xt = ox;
+    a.Yt = oy;
+    a.Zt = oz;
+    a.XC = p.XC;
+    a.nxc = p.nxc;
+    a.npatch = p.npatch;
+    a.mode = p.mode;
+    a.TZ = p.TZ;
+    a.nzc = p.nzc;
+    a.pitch = p.pitch;
+    a.nposp = p.nposp;
+    a.jstep = (p.mode == 1 && p.TZ == 16) ? p.pitch : 16;
+    // two-chunk layers only: with four chunks the reuse is 1/12 of the loads and measured +1.6 % time (COUT 128);
+    // split mode: the chunk triples carry their own reuse flags
+    a.alt = (!split && a.nchunks == 2) ? 1 : 0;
+    a.dbg = nullptr;
+#ifdef SK_TIMING
+    a.dbg = sk::timing_buffer();
+    if (const char* e = getenv("SK_CONV_DBG_OFF")) a.dbg_off = atoi(e);
+#endif
+    a.ablate = r.ablate;
+    a.has_box = 0;
+    if (store_box && cout == 32) {   // honoured by the COUT-32 kernels (conv3_px_kernel, conv3_m16_kernel); wider layers store everything
+        for (int k = 0; k < 3; ++k) {
+            a.box_lo[k] = store_box[k];
+            a.box_hi[k] = store_box[3 + k];
+            SK_CHECK_ARG(a.box_lo[k] >= 0 && a.box_lo[k] <= a.box_hi[k], "sk_conv3d_box: bad box on axis %d", k);
+        }
+        a.has_box = 1;
+    }
+    if (mix8) {
+        SK_CHECK_ARG(w8_scale_exp >= 0 && w8_scale_exp < 64, "sk_conv3d_mix8: bad weight scale exponent %d", w8_scale_exp);
+        a.w8_off = mix8_fp16_bytes(cout, cin);
+        a.wpk_bytes = a.w8_off + mix8_fp8_bytes(cout, cin);
+        a.w8_scale = 0x01010101 * (127 - w8_scale_exp);
+    }
+    return launch(kConv3[r.row].kern, r.grid, r.lds, a, stream);
 }
 
 int sk_conv3d(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
               int B, int ox, int oy, int oz, int cout, int ksize, float* gn_partial,
               void* zeros, void* stream) {
-    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, false);
+    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, kFp16);
 }
 
 int sk_conv3d_box(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
                   int B, int ox, int oy, int oz, int cout, int ksize, float* gn_partial,
                   void* zeros, const int* store_box, void* stream) {
     SK_CHECK_ARG(ksize == 3 || store_box == nullptr, "sk_conv3d_box: a store box needs ksize 3");
-    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, false, store_box);
+    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, kFp16, store_box);
 }
 
 int sk_conv3d_box_split(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
                         int B, int ox, int oy, int oz, int cout, int ksize, float* gn_partial,
                         void* zeros, const int* store_box, void* stream) {
     SK_CHECK_ARG(ksize == 3 || store_box == nullptr, "sk_conv3d_box_split: a store box needs ksize 3");
-    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, true, store_box);
+    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, kSplit, store_box);
 }
 
 int sk_conv3d_down_act(void* in_raw, const float* affine, const void* weight, const float* bias, void* out, int B,
@@ -3139,26 +3273,25 @@ int64_t sk_conv3d_pack_weight_mix8_host(const float* w, int cout, int cin, void*
 
 int sk_conv3d_mix8(const sk_conv_src* srcs, int n_src, const void* weight, int weight_scale_exp, const float* bias, void* out,
                    int B, int ox, int oy, int oz, int cout, float* gn_partial, void* zeros, const int* store_box, void* stream) {
-    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, 3, gn_partial, zeros, stream, true, store_box, true,
-                       weight_scale_exp);
+    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, 3, gn_partial, zeros, stream, kMix8, store_box, weight_scale_exp);
 }
 
 int sk_conv3d_down_act_split(void* in_raw, const float* affine, const void* weight, const float* bias, void* out, int B,
                              int ox, int oy, int oz, int cin, int cout, float* gn_partial, void* zeros, void* stream) {
     SK_CHECK_ARG(affine, "sk_conv3d_down_act_split: affine is NULL (use sk_conv3d_split for an activated input)");
-    return launch_down2(in_raw, affine, 1, weight, bias, out, B, ox, oy, oz, cin, cout, gn_partial, zeros, (hipStream_t)stream, true);
+    return launch_down2(in_raw, affine, 1, weight, bias, out, B, ox, oy, oz, cin, cout, gn_partial, zeros, (hipStream_t)stream, kSplit);
 }
 
 int sk_conv3d_down_act_mix8(void* in_raw, const float* affine, const void* weight, const float* bias, void* out, int B,
                             int ox, int oy, int oz, int cin, int cout, float* gn_partial, void* zeros, void* stream) {
     SK_CHECK_ARG(affine, "sk_conv3d_down_act_mix8: affine is NULL");
-    return launch_down2(in_raw, affine, 2, weight, bias, out, B, ox, oy, oz, cin, cout, gn_partial, zeros, (hipStream_t)stream, true);
+    return launch_down2(in_raw, affine, 2, weight, bias, out, B, ox, oy, oz, cin, cout, gn_partial, zeros, (hipStream_t)stream, kMix8);
 }
 
 int sk_conv3d_split(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
                     int B, int ox, int oy, int oz, int cout, int ksize, float* gn_partial,
                     void* zeros, void* stream) {
-    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, true);
+    return conv3d_impl(srcs, n_src, weight, bias, out, B, ox, oy, oz, cout, ksize, gn_partial, zeros, stream, kSplit);
 }
 
 int64_t sk_conv3d_pack_weight_split_host(const float* w, int cout, int cin, int ksize, void* dst) {

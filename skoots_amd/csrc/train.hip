@@ -13,6 +13,8 @@
 //   * 2x2x2 sum pooling (backward of the nearest upsampling), AdamW.
 // All reductions are two-stage (per-block partials, then a fixed-order sum in double), so a step
 // is deterministic.
+#include <string.h>
+
 #include "common.h"
 
 #include <type_traits>
@@ -2431,6 +2433,197 @@ int wgrad_fill_srcs(Args& a, const char* fn, const sk_conv_src* srcs, int n_src,
     return SK_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The weight gradient's dispatch.  Which instantiation an entry point launches, with what chunking, grid and workspace, is
+// decided by wgrad_route and nowhere else; the tables keep every kernel's name (as tests/train_grad_cases.py spells it:
+// sk_train_conv_wgrad_route_name) beside the pointer that is launched.
+// ------------------------------------------------------------------------------------------
+struct WgradRoute {
+    int row;                   // in the entry's table
+    int nchunk, nchunk_b;      // partial rows the launch writes (wgrad16x: its own count), voxel chunks per batch item
+    long long chunk;           // voxels per chunk, after the 16-rounding of the 16-bit kernels
+    int ngroup;                // tap groups per (chunk, cout tile, cin tile)
+    int nchunk_x, nxs, xseg;   // wgrad16x_kernel's rows and x segments for this shape, 0 where it does not cover it
+    int ncol_chunk;            // wgrad16y_kernel: (x, 16-voxel z block) columns per chunk
+    unsigned grid;
+    int64_t workspace_floats;  // the larger row count x (cout cin k^3 + cout)
+};
+
+template <class Args>
+struct WgradRow {
+    const char* name;
+    int (*launch)(const Args&, const WgradRoute&, const char* zero_page, hipStream_t);
+};
+template <void (*K)(WgradArgs)>
+int wgrad_go(const WgradArgs& a, const WgradRoute& r, const char*, hipStream_t st) {
+    K<<<r.grid, 64, 0, st>>>(a);
+    return SK_OK;
+}
+template <void (*K)(Wgrad16Args)>
+int wgrad16_go(const Wgrad16Args& a, const WgradRoute& r, const char*, hipStream_t st) {
+    K<<<r.grid, 64, 0, st>>>(a);
+    return SK_OK;
+}
+template <void (*K)(Wgrad16Args, const char*)>
+int wgrad16t_go(const Wgrad16Args& a, const WgradRoute& r, const char* zero_page, hipStream_t st) {
+    K<<<r.grid, 64, 0, st>>>(a, zero_page);
+    return SK_OK;
+}
+int wgrad16y_go(const Wgrad16Args& a, const WgradRoute& r, const char* zero_page, hipStream_t st) {
+    wgrad16y_kernel<<<r.grid, 64, 0, st>>>(a, zero_page, r.ncol_chunk);
+    return SK_OK;
+}
+int wgrad16x_go(const Wgrad16Args& a, const WgradRoute& r, const char*, hipStream_t st) {
+    SK_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad16x_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kWxLds));
+    wgrad16x_kernel<<<r.grid, 256, kWxLds, st>>>(a, a.oy / 16, a.oz / 16, r.nxs, r.xseg);
+    return SK_OK;
+}
+
+// sk_train_conv_wgrad: [the stem | 4 - ksize]
+const WgradRow<WgradArgs> kWgradF32[] = {
+    {"wgrad_stem<false>", wgrad_go<wgrad_stem_kernel<false>>},
+    {"wgrad<9>", wgrad_go<wgrad_kernel<9>>},
+    {"wgrad<8>", wgrad_go<wgrad_kernel<8>>},
+    {"wgrad<1>", wgrad_go<wgrad_kernel<1>>},
+};
+// sk_train_stem_wgrad_f16: [Z % 16 != 0]
+const WgradRow<WgradArgs> kWgradStem16[] = {
+    {"wgrad_stem16", wgrad_go<wgrad_stem16_kernel>},
+    {"wgrad_stem<true>", wgrad_go<wgrad_stem_kernel<true>>},
+};
+// sk_train_conv_wgrad_f16: [whole 64-byte lines][3 - ksize], then the two plane-geometry kernels of ksize 3
+enum { kRowWgrad16y = 6, kRowWgrad16x = 7, kRowWgrad16t3 = 8 };
+const WgradRow<Wgrad16Args> kWgradF16[] = {
+    {"wgrad16<9>", wgrad16_go<wgrad16_kernel<9>>},
+    {"wgrad16<8>", wgrad16_go<wgrad16_kernel<8>>},
+    {"wgrad16<1>", wgrad16_go<wgrad16_kernel<1>>},
+    {"wgrad16t<9>", wgrad16t_go<wgrad16t_kernel<9>>},
+    {"wgrad16t<8>", wgrad16t_go<wgrad16t_kernel<8>>},
+    {"wgrad16t<1>", wgrad16t_go<wgrad16t_kernel<1>>},
+    {"wgrad16y", wgrad16y_go},
+    {"wgrad16x", wgrad16x_go},
+    // three taps per wave (nine tap groups): 8 KiB of LDS tiles per wave instead of 20, so ~2.5x the waves and DMA steps in
+    // flight per CU; measured 1.5 % slower -- the kernel is bound by L2 bandwidth (every input line is read once per tap).
+    // Only a -DSK_TUNING build (SK_WGRAD_TPW=3) routes here: the release build's name list ends in front of it.
+    {"wgrad16t<3>", wgrad16t_go<wgrad16t_kernel<3>>},
+};
+#ifdef SK_TUNING
+constexpr int kWgradF16Rows = kRowWgrad16t3 + 1;
+#else
+constexpr int kWgradF16Rows = kRowWgrad16t3;
+#endif
+
+// Pure host code.  Of srcs only c is read; SK_WGRAD_STEM_F16 (1 -> 32 channels, ksize 3) reads neither srcs nor cout nor ksize.
+int wgrad_route(int entry, const sk_conv_src* srcs, int n_src, int B, int ox, int oy, int oz, int cout, int ksize,
+                bool has_zero_page, WgradRoute& r) {
+    r = WgradRoute{};
+    SK_CHECK_ARG(entry == SK_WGRAD_FP32 || entry == SK_WGRAD_F16 || entry == SK_WGRAD_STEM_F16, "wgrad route: unknown entry %d", entry);
+    int cin = 1;
+    bool lines = has_zero_page;   // whole 64-byte channel lines: LDS-DMA + transposed reads
+    if (entry == SK_WGRAD_STEM_F16) {
+        cout = 32;
+        ksize = 3;
+    } else {
+        SK_CHECK_ARG(srcs && (n_src == 1 || n_src == 2) && (ksize == 1 || ksize == 2 || ksize == 3), "wgrad route: bad sources or ksize");
+        cin = 0;
+        for (int i = 0; i < n_src; ++i) {
+            cin += srcs[i].c;
+            lines = lines && srcs[i].c % 32 == 0;
+        }
+        lines = lines && cout % 32 == 0;
+    }
+    SK_CHECK_ARG(B >= 1 && ox >= 1 && oy >= 1 && oz >= 1 && cout >= 1 && cin >= 1, "wgrad route: bad extents");
+    const int ncot = (cout + 31) / 32, ncit = (cin + 31) / 32;
+    // voxel chunks per batch item: ~4096 waves in all, at least 512 voxels each, an even count
+    r.ngroup = ksize == 3 ? 3 : 1;
+    const long long nvox = (long long)ox * oy * oz;
+    long long want = 4096 / ((long long)ncot * ncit * r.ngroup * B);
+    if (want < 1) want = 1;
+    long long c = (nvox + want - 1) / want;
+    if (c < 512) c = 512;
+    c = (c + 1) & ~1LL;
+    r.chunk = c;
+    r.nchunk_b = (int)((nvox + c - 1) / c);
+    r.nchunk = B * r.nchunk_b;
+    // wgrad16x_kernel: 16 x 16 (y, z) footprints x segments of x, about 1024 workgroups (four rounds of the 256 CUs) but
+    // at least eight planes a segment (each segment fetches two planes it does not own)
+    if (ksize == 3 && oy % 16 == 0 && oz % 16 == 0 && cout % 32 == 0 && cin % 32 == 0) {
+        const long long wg = (long long)B * (oy / 16) * (oz / 16) * (cout / 32) * (cin / 32);
+        long long s = (1024 + wg - 1) / wg;
+        if (s > ox / 8) s = ox / 8;
+        if (s < 1) s = 1;
+        r.xseg = (int)((ox + s - 1) / s);
+        r.nxs = (ox + r.xseg - 1) / r.xseg;
+        r.nchunk_x = B * (oy / 16) * (oz / 16) * r.nxs;
+    }
+    r.workspace_floats = (int64_t)(r.nchunk_x > r.nchunk ? r.nchunk_x : r.nchunk) * ((int64_t)cout * cin * ksize * ksize * ksize + cout);
+    const long long tiles = (long long)ncot * ncit;
+    if (entry == SK_WGRAD_FP32) {
+        const bool stem = ksize == 3 && n_src == 1 && cin == 1 && !srcs[0].upsample;
+        r.row = stem ? 0 : 4 - ksize;
+        r.grid = (unsigned)(stem ? (long long)r.nchunk * ncot : r.nchunk * tiles * r.ngroup);
+        return SK_OK;
+    }
+    // the 16-bit kernels step 16 voxels at a time; the chunk count of the plan still covers the volume
+    if (entry == SK_WGRAD_STEM_F16) {
+        r.row = oz % 16 == 0 ? 0 : 1;
+        if (r.row == 0) r.chunk = (r.chunk + 15) & ~15LL;
+        r.grid = (unsigned)r.nchunk;
+        return SK_OK;
+    }
+    r.chunk = (r.chunk + 15) & ~15LL;
+    bool strips = true, xmarch = true;   // -DSK_TUNING builds (tools/) can switch the plane-geometry kernels off for A/B timing
+    int tpw = 9;
+#ifdef SK_TUNING
+    strips = getenv("SK_WGRAD_NOSTRIP") == nullptr;
+    xmarch = getenv("SK_WGRAD_NOXMARCH") == nullptr;
+    if (const char* e = getenv("SK_WGRAD_TPW")) tpw = atoi(e) == 3 ? 3 : 9;
+#endif
+    if (lines && strips && xmarch && r.nchunk_x > 0) {
+        r.row = kRowWgrad16x;
+        r.nchunk = r.nchunk_x;
+        r.grid = (unsigned)((((long long)r.nchunk + 7) / 8) * 8 * tiles);   // whole XCD rounds of chunks
+    } else if (lines && strips && ksize == 3 && oz % 16 == 0 && oy % 4 == 0) {
+        r.row = kRowWgrad16y;
+        r.ncol_chunk = (ox * (oz / 16) + r.nchunk_b - 1) / r.nchunk_b;
+        r.grid = (unsigned)((((long long)r.nchunk + 7) / 8) * 8 * tiles * 3);   // whole XCD rounds of chunks
+    } else {
+        r.row = 3 * lines + 3 - ksize;
+        if (lines && ksize == 3 && tpw == 3) {
+            r.row = kRowWgrad16t3;
+            r.ngroup = 9;
+        }
+        r.grid = (unsigned)(r.nchunk * tiles * r.ngroup);
+    }
+    return SK_OK;
+}
+
+// the chunking of a route in a launch's arguments
+template <class Args>
+void wgrad_fill_plan(Args& a, const WgradRoute& r, float* workspace, bool with_bias) {
+    a.ncot = (a.cout + 31) / 32;
+    a.ncit = (a.cin + 31) / 32;
+    a.nchunk = r.nchunk;
+    a.nchunk_b = r.nchunk_b;
+    a.chunk = r.chunk;
+    a.ngroup = r.ngroup;
+    a.part = workspace;
+    a.part_bias = with_bias ? workspace + (long long)r.nchunk * a.cout * a.cin * a.ksize * a.ksize * a.ksize : nullptr;
+}
+
+// dweight (and dbias) = the partial rows summed in a fixed order, times scale[1]; taps > 0: tap-major rows to the torch layout
+int wgrad_reduce(const float* part, const float* part_bias, int nchunk, int cout, int cin, int k3, int taps, float* dweight,
+                 float* dbias, const float* scale, hipStream_t st) {
+    const long long nw = (long long)cout * cin * k3;
+    wgrad_reduce_kernel<<<sk::cdiv(nw, 64), 64 * kWredSlices, 0, st>>>(part, nchunk, nw, dweight, scale, cout, cin, taps);
+    SK_CHECK_LAUNCH();
+    if (dbias) {
+        wgrad_reduce_kernel<<<sk::cdiv(cout, 64), 64 * kWredSlices, 0, st>>>(part_bias, nchunk, cout, dbias, scale, 0, 0, 0);
+        SK_CHECK_LAUNCH();
+    }
+    return SK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2535,43 +2728,28 @@ int sk_train_tversky(const float* predicted, const float* ground_truth, int B, i
     return SK_OK;
 }
 
-static int wgrad_plan(int B, int ox, int oy, int oz, int cout, int cin, int ksize, int* nchunk, int* nchunk_b,
-                      long long* chunk, int* ngroup) {
-    const int ncot = (cout + 31) / 32, ncit = (cin + 31) / 32;
-    *ngroup = ksize == 3 ? 3 : 1;
-    const long long nvox = (long long)ox * oy * oz;
-    long long want = 4096 / ((long long)ncot * ncit * *ngroup * B);  // chunks per batch item: ~4096 waves in all
-    if (want < 1) want = 1;
-    long long c = (nvox + want - 1) / want;
-    if (c < 512) c = 512;
-    c = (c + 1) & ~1LL;
-    *chunk = c;
-    *nchunk_b = (int)((nvox + c - 1) / c);
-    *nchunk = B * *nchunk_b;
-    return 0;
+int sk_train_conv_wgrad_route(int entry, const sk_conv_src* srcs, int n_src, int B, int ox, int oy, int oz, int cout, int ksize,
+                              int has_zero_page, sk_wgrad_route* route) {
+    SK_CHECK_ARG(route, "sk_train_conv_wgrad_route: NULL pointer");
+    WgradRoute r;
+    if (const int e = wgrad_route(entry, srcs, n_src, B, ox, oy, oz, cout, ksize, has_zero_page != 0, r)) return e;
+    const char* name = entry == SK_WGRAD_FP32 ? kWgradF32[r.row].name : entry == SK_WGRAD_F16 ? kWgradF16[r.row].name : kWgradStem16[r.row].name;
+    *route = sk_wgrad_route{{}, r.nchunk, r.nchunk_b, r.chunk, r.ngroup, r.nchunk_x, r.nxs, r.xseg, r.ncol_chunk, (int64_t)r.grid,
+                            r.workspace_floats};
+    strncpy(route->name, name, sizeof(route->name) - 1);
+    return SK_OK;
 }
 
-// wgrad16x_kernel: 16 x 16 (y, z) footprints x segments of x, about 1024 workgroups (four rounds of the 256 CUs) but
-// at least eight planes a segment (each segment fetches two planes it does not own).  Returns the chunk count, 0 if the
-// kernel does not cover the shape.
-static int wgrad_x_plan(int B, int ox, int oy, int oz, int cout, int cin, int ksize, int* nxs, int* xseg) {
-    if (ksize != 3 || oy % 16 || oz % 16 || cout % 32 || cin % 32) return 0;
-    const long long wg = (long long)B * (oy / 16) * (oz / 16) * (cout / 32) * (cin / 32);
-    long long s = (1024 + wg - 1) / wg;
-    if (s > ox / 8) s = ox / 8;
-    if (s < 1) s = 1;
-    *xseg = (int)((ox + s - 1) / s);
-    *nxs = (ox + *xseg - 1) / *xseg;
-    return B * (oy / 16) * (oz / 16) * *nxs;
+const char* sk_train_conv_wgrad_route_name(int entry, int i) {
+    auto nth = [i](const auto& table, int rows) { return i >= 0 && i < rows ? table[i].name : nullptr; };
+    return entry == SK_WGRAD_FP32 ? nth(kWgradF32, 4) : entry == SK_WGRAD_F16 ? nth(kWgradF16, kWgradF16Rows) : entry == SK_WGRAD_STEM_F16 ? nth(kWgradStem16, 2) : nullptr;
 }
 
 int64_t sk_train_conv_wgrad_workspace_floats(int B, int ox, int oy, int oz, int cout, int cin, int ksize) {
-    int nchunk, nchunk_b, ngroup, nxs, xseg;
-    long long chunk;
-    wgrad_plan(B, ox, oy, oz, cout, cin, ksize, &nchunk, &nchunk_b, &chunk, &ngroup);
-    const int nx = wgrad_x_plan(B, ox, oy, oz, cout, cin, ksize, &nxs, &xseg);
-    if (nx > nchunk) nchunk = nx;
-    return (int64_t)nchunk * ((int64_t)cout * cin * ksize * ksize * ksize + cout);
+    const sk_conv_src all{nullptr, nullptr, cin, 0};   // the size depends on the channel total alone
+    WgradRoute r;
+    if (const int e = wgrad_route(SK_WGRAD_F16, &all, 1, B, ox, oy, oz, cout, ksize, false, r)) return e;
+    return r.workspace_floats;
 }
 
 int sk_train_conv_wgrad(const sk_conv_src* srcs, int n_src, const float* dy, int B, int ox, int oy, int oz, int cout,
@@ -2582,6 +2760,9 @@ int sk_train_conv_wgrad(const sk_conv_src* srcs, int n_src, const float* dy, int
     SK_CHECK_ARG(B >= 1 && ox >= 1 && oy >= 1 && oz >= 1 && cout >= 1, "sk_train_conv_wgrad: bad extents");
     WgradArgs a{};
     if (const int e = wgrad_fill_srcs(a, "sk_train_conv_wgrad", srcs, n_src, ox, oy, oz, ksize)) return e;
+    SK_CHECK_ARG((long long)ox * oy * oz * cout * 4 < (1LL << 32), "sk_train_conv_wgrad: dy of one batch item must be < 4 GiB");
+    WgradRoute r;
+    if (const int e = wgrad_route(SK_WGRAD_FP32, srcs, n_src, B, ox, oy, oz, cout, ksize, false, r)) return e;
     a.dy = dy;
     a.B = B;
     a.ox = ox;
@@ -2589,32 +2770,12 @@ int sk_train_conv_wgrad(const sk_conv_src* srcs, int n_src, const float* dy, int
     a.oz = oz;
     a.cout = cout;
     a.ksize = ksize;
-    a.ncot = (cout + 31) / 32;
-    a.ncit = (a.cin + 31) / 32;
-    wgrad_plan(B, ox, oy, oz, cout, a.cin, ksize, &a.nchunk, &a.nchunk_b, &a.chunk, &a.ngroup);
-    SK_CHECK_ARG((long long)ox * oy * oz * cout * 4 < (1LL << 32), "sk_train_conv_wgrad: dy of one batch item must be < 4 GiB");
-    const long long nw = (long long)cout * a.cin * ksize * ksize * ksize;
-    a.part = workspace;
-    a.part_bias = dbias ? workspace + (long long)a.nchunk * nw : nullptr;
+    wgrad_fill_plan(a, r, workspace, dbias != nullptr);
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((long long)a.nchunk * a.ncot * a.ncit * a.ngroup);
-    const bool stem = ksize == 3 && n_src == 1 && a.cin == 1 && !a.src[0].up;
-    if (stem)
-        wgrad_stem_kernel<false><<<(unsigned)((long long)a.nchunk * a.ncot), 64, 0, st>>>(a);
-    else if (ksize == 3)
-        wgrad_kernel<9><<<grid, 64, 0, st>>>(a);
-    else if (ksize == 2)
-        wgrad_kernel<8><<<grid, 64, 0, st>>>(a);
-    else
-        wgrad_kernel<1><<<grid, 64, 0, st>>>(a);
+    kWgradF32[r.row].launch(a, r, nullptr, st);
     SK_CHECK_LAUNCH();
-    wgrad_reduce_kernel<<<sk::cdiv(nw, 64), 64 * kWredSlices, 0, st>>>(a.part, a.nchunk, nw, dweight, nullptr, cout, a.cin, stem ? 0 : ksize * ksize * ksize);
-    SK_CHECK_LAUNCH();
-    if (dbias) {
-        wgrad_reduce_kernel<<<sk::cdiv(cout, 64), 64 * kWredSlices, 0, st>>>(a.part_bias, a.nchunk, cout, dbias, nullptr, 0, 0, 0);
-        SK_CHECK_LAUNCH();
-    }
-    return SK_OK;
+    const int k3 = ksize * ksize * ksize;   // the stem kernel writes its rows in the torch layout
+    return wgrad_reduce(a.part, a.part_bias, a.nchunk, cout, a.cin, k3, r.row == 0 ? 0 : k3, dweight, dbias, nullptr, st);
 }
 
 int sk_train_stem_wgrad_f16(const float* image, const void* dy16, const float* dy_scale, int B, int X, int Y, int Z,
@@ -2622,6 +2783,9 @@ int sk_train_stem_wgrad_f16(const float* image, const void* dy16, const float* d
     SK_CHECK_ARG(image && dy16 && dy_scale && dweight && workspace, "sk_train_stem_wgrad_f16: NULL pointer");
     SK_CHECK_ARG(B >= 1 && X >= 1 && Y >= 1 && Z >= 1, "sk_train_stem_wgrad_f16: bad extents");
     const int cout = 32;
+    SK_CHECK_ARG((long long)X * Y * Z * cout * 2 < (1LL << 32), "sk_train_stem_wgrad_f16: dy of one batch item must be < 4 GiB");
+    WgradRoute r;
+    if (const int e = wgrad_route(SK_WGRAD_STEM_F16, nullptr, 0, B, X, Y, Z, cout, 3, false, r)) return e;
     WgradArgs a{};
     a.nsrc = 1;
     a.src[0].data = image;
@@ -2638,27 +2802,11 @@ int sk_train_stem_wgrad_f16(const float* image, const void* dy16, const float* d
     a.cout = cout;
     a.cin = 1;
     a.ksize = 3;
-    a.ncot = 1;
-    a.ncit = 1;
-    wgrad_plan(B, X, Y, Z, cout, 1, 3, &a.nchunk, &a.nchunk_b, &a.chunk, &a.ngroup);
-    SK_CHECK_ARG((long long)X * Y * Z * cout * 2 < (1LL << 32), "sk_train_stem_wgrad_f16: dy of one batch item must be < 4 GiB");
-    const long long nw = (long long)cout * 27;
-    a.part = workspace;
-    a.part_bias = dbias ? workspace + (long long)a.nchunk * nw : nullptr;
+    wgrad_fill_plan(a, r, workspace, dbias != nullptr);
     hipStream_t st = (hipStream_t)stream;
-    if (Z % 16 == 0) {
-        a.chunk = (a.chunk + 15) & ~15LL;   // whole 16-voxel steps; the plan's chunk count still covers the volume
-        wgrad_stem16_kernel<<<(unsigned)a.nchunk, 64, 0, st>>>(a);
-    } else
-        wgrad_stem_kernel<true><<<(unsigned)((long long)a.nchunk * a.ncot), 64, 0, st>>>(a);
+    kWgradStem16[r.row].launch(a, r, nullptr, st);
     SK_CHECK_LAUNCH();
-    wgrad_reduce_kernel<<<sk::cdiv(nw, 64), 64 * kWredSlices, 0, st>>>(a.part, a.nchunk, nw, dweight, dy_scale, cout, 1, 0);
-    SK_CHECK_LAUNCH();
-    if (dbias) {
-        wgrad_reduce_kernel<<<sk::cdiv(cout, 64), 64 * kWredSlices, 0, st>>>(a.part_bias, a.nchunk, cout, dbias, dy_scale, 0, 0, 0);
-        SK_CHECK_LAUNCH();
-    }
-    return SK_OK;
+    return wgrad_reduce(a.part, a.part_bias, a.nchunk, cout, 1, 27, 0, dweight, dbias, dy_scale, st);
 }
 
 int sk_train_conv_wgrad_f16(const sk_conv_src* srcs, int n_src, const void* dy, const float* dy_scale, int B, int ox, int oy,
@@ -2671,6 +2819,8 @@ int sk_train_conv_wgrad_f16(const sk_conv_src* srcs, int n_src, const void* dy, 
     Wgrad16Args a{};
     if (const int e = wgrad_fill_srcs(a, "sk_train_conv_wgrad_f16", srcs, n_src, ox, oy, oz, ksize)) return e;
     SK_CHECK_ARG((long long)ox * oy * oz * cout * 2 < (1LL << 32), "sk_train_conv_wgrad_f16: dy of one batch item must be < 4 GiB");
+    WgradRoute r;
+    if (const int e = wgrad_route(SK_WGRAD_F16, srcs, n_src, B, ox, oy, oz, cout, ksize, zero_page != nullptr, r)) return e;
     a.dy = (const t16*)dy;
     a.B = B;
     a.ox = ox;
@@ -2678,73 +2828,15 @@ int sk_train_conv_wgrad_f16(const sk_conv_src* srcs, int n_src, const void* dy, 
     a.oz = oz;
     a.cout = cout;
     a.ksize = ksize;
-    a.ncot = (cout + 31) / 32;
-    a.ncit = (a.cin + 31) / 32;
-    wgrad_plan(B, ox, oy, oz, cout, a.cin, ksize, &a.nchunk, &a.nchunk_b, &a.chunk, &a.ngroup);
-    a.chunk = (a.chunk + 15) & ~15LL;  // whole 16-voxel MFMA steps; the chunk count of the plan still covers the volume
-    const long long nw = (long long)cout * a.cin * ksize * ksize * ksize;
-    a.part = workspace;
-    a.part_bias = dbias ? workspace + (long long)a.nchunk * nw : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((long long)a.nchunk * a.ncot * a.ncit * a.ngroup);
-    bool lines = zero_page != nullptr && cout % 32 == 0;  // whole 64-byte channel lines: LDS-DMA + transposed reads
-    for (int i = 0; i < n_src; ++i) lines = lines && srcs[i].c % 32 == 0;
-    bool strips = true;   // -DSK_TUNING builds (tools/) can switch the strip kernel off for A/B timing
-#ifdef SK_TUNING
-    strips = getenv("SK_WGRAD_NOSTRIP") == nullptr;
-#endif
-    int nxs = 0, xseg = 0;
-    int nchunk_x = lines && strips ? wgrad_x_plan(B, ox, oy, oz, cout, a.cin, ksize, &nxs, &xseg) : 0;
-#ifdef SK_TUNING
-    if (getenv("SK_WGRAD_NOXMARCH")) nchunk_x = 0;
-#endif
-    if (nchunk_x > 0) {
+    wgrad_fill_plan(a, r, workspace, dbias != nullptr);
 #ifdef SK_TIMING
-        a.dbg = sk::timing_buffer();
+    if (r.row == kRowWgrad16x) a.dbg = sk::timing_buffer();
 #endif
-        a.nchunk = nchunk_x;
-        a.part_bias = dbias ? workspace + (long long)a.nchunk * nw : nullptr;
-        SK_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad16x_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kWxLds));
-        const unsigned gx = (unsigned)((((long long)a.nchunk + 7) / 8) * 8 * a.ncot * a.ncit);   // whole XCD rounds of chunks
-        wgrad16x_kernel<<<gx, 256, kWxLds, st>>>(a, oy / 16, oz / 16, nxs, xseg);
-    } else if (lines && ksize == 3 && oz % 16 == 0 && oy % 4 == 0 && strips) {
-        a.ngroup = 3;
-        const unsigned g3 = (unsigned)((((long long)a.nchunk + 7) / 8) * 8 * a.ncot * a.ncit * 3);   // whole XCD rounds of chunks
-        const int ncol = ox * (oz / 16);
-        wgrad16y_kernel<<<g3, 64, 0, st>>>(a, (const char*)zero_page, (ncol + a.nchunk_b - 1) / a.nchunk_b);
-    } else if (lines) {
-        if (ksize == 3) {
-            // three taps per wave (nine tap groups): 8 KiB of LDS tiles per wave instead of 20, so ~2.5x the waves
-            // and DMA steps in flight per CU -- the kernel is bound by the latency of its tile loads
-            int tpw = 9;  // 3 measured 1.5 % slower: the kernel is bound by L2 bandwidth (every input line is read once per tap), not by latency
-#ifdef SK_TUNING
-            if (const char* e = getenv("SK_WGRAD_TPW")) tpw = atoi(e) == 3 ? 3 : 9;
-#endif
-            a.ngroup = 27 / tpw;
-            const unsigned g = (unsigned)((long long)a.nchunk * a.ncot * a.ncit * a.ngroup);
-            if (tpw == 3)
-                wgrad16t_kernel<3><<<g, 64, 0, st>>>(a, (const char*)zero_page);
-            else
-                wgrad16t_kernel<9><<<g, 64, 0, st>>>(a, (const char*)zero_page);
-        }
-        else if (ksize == 2)
-            wgrad16t_kernel<8><<<grid, 64, 0, st>>>(a, (const char*)zero_page);
-        else
-            wgrad16t_kernel<1><<<grid, 64, 0, st>>>(a, (const char*)zero_page);
-    } else if (ksize == 3)
-        wgrad16_kernel<9><<<grid, 64, 0, st>>>(a);
-    else if (ksize == 2)
-        wgrad16_kernel<8><<<grid, 64, 0, st>>>(a);
-    else
-        wgrad16_kernel<1><<<grid, 64, 0, st>>>(a);
+    hipStream_t st = (hipStream_t)stream;
+    if (const int e = kWgradF16[r.row].launch(a, r, (const char*)zero_page, st)) return e;
     SK_CHECK_LAUNCH();
-    wgrad_reduce_kernel<<<sk::cdiv(nw, 64), 64 * kWredSlices, 0, st>>>(a.part, a.nchunk, nw, dweight, dy_scale, cout, a.cin, ksize * ksize * ksize);
-    SK_CHECK_LAUNCH();
-    if (dbias) {
-        wgrad_reduce_kernel<<<sk::cdiv(cout, 64), 64 * kWredSlices, 0, st>>>(a.part_bias, a.nchunk, cout, dbias, dy_scale, 0, 0, 0);
-        SK_CHECK_LAUNCH();
-    }
-    return SK_OK;
+    const int k3 = ksize * ksize * ksize;
+    return wgrad_reduce(a.part, a.part_bias, a.nchunk, cout, a.cin, k3, k3, dweight, dbias, dy_scale, st);
 }
 
 int sk_train_pack_weight(const float* weight, int Co, int Ci, int ksize, int transposed, int c_lo, int c_n, void* dst,

@@ -1,13 +1,15 @@
-"""The cases, dispatch mirror, seeded operands and float64 references that tests/test_conv16_cases_cpu.py and
+"""The cases, plan mirror, seeded operands and float64 references that tests/test_conv16_cases_cpu.py and
 tests/test_hip_conv16_exact.py share (torch on the CPU only): the fp16 and split conv kernels of skoots_amd/csrc/conv3d.hip
 behind sk_conv3d, sk_conv3d_split and sk_conv3d_box.
 
 A case is ``(B, out spatial, [(C, up)], cout, ksize)``: the layer's sources are concatenated along the channels, a source
 with ``up`` is stored at half the output extent and read through a nearest upsample; ksize 3 has padding 1 and stride 1,
 ksize 2 stride 2, ksize 1 stride 1.  CASES holds, next to every case, the instantiation it runs in precision "fp16" and in
-precision "split" -- what ``route`` (a restatement of make_plan, conv3d_impl and launch_down2 without the SK_TUNING switches)
-returns for it; tests/test_conv16_cases_cpu.py asserts both columns and that together they cover every reachable
-instantiation.  Each case is the smallest shape that reaches its branch and edge.
+precision "split" -- what ``route`` returns for it, which is the library's own answer: conv3d_route of
+skoots_amd/csrc/conv3d.hip, the one function the launches ask, through the host-only sk_conv3d_route.  tests/test_conv16_cases_cpu.py
+asserts both columns and that together they cover every name sk_conv3d_route_name lists.  ``make_plan`` and ``num_blocks``
+stay an independent restatement of the plan's numbers, compared with the library's.  Each case is the smallest shape that
+reaches its branch and edge.
 
 Route names:
 ``px``                conv3_px_kernel (32 -> 32, one plain source, z 16 .. 20)
@@ -16,6 +18,7 @@ Route names:
 ``conv3<C,XS>``       conv3_kernel<C, XS>;   ``..,split>``: the SPLIT form of any of the above
 ``down2<C,CIN>``      down2_act_kernel<C, CIN> without activation (fp16, ksize 2, 32 -> 64 | 64 -> 128)
 ``gather<C,deep|2>``  gather_gemm_kernel<C, PV, 4 | 2>;   ``gather<C,split>``: gather_gemm_kernel<C, PV, 2, true>
+``pointwise<C,CIN>``  pointwise_lds_kernel<C, CIN> (fp16, ksize 1, 64 -> 32 | 128 -> 64: the channel reducers)
 
 Three kinds of operands:
 
@@ -43,94 +46,86 @@ import functools
 import torch
 import torch.nn.functional as F
 
-# ---------------------------------------------------------------------------------------------- the dispatch mirror
-kPosBytes = 64            # skoots_amd/csrc/conv3_device.h:21
-kPatch = 128              # skoots_amd/csrc/conv3_device.h:22
-kPadBytes = 32 * 64       # skoots_amd/csrc/conv3_device.h:23-24 (32 * kPadStride)
-kZeroPos = 4              # skoots_amd/csrc/common.h:120 (SK_ZERO_WINDOW, the default build)
-kMaxDma = 4               # skoots_amd/csrc/conv3d.hip:48
-kMaxChunks = 24           # skoots_amd/csrc/conv3d.hip:49
-kLdsTwoPerCU = 80 * 1024  # skoots_amd/csrc/conv3d.hip:2537, 2846-2847: two workgroups per CU need <= 80 KiB each
-kPlanBatch = 8            # skoots_amd/csrc/conv3d.hip:2546
-kTarget = 256 * 2 * 8     # skoots_amd/csrc/conv3d.hip:2547 (`target`)
-kPxPositions = 176        # skoots_amd/csrc/conv3d.hip:2606
-kTapRowBytes = 6144       # skoots_amd/csrc/conv3d.hip:2594, 2846-2847: one tap row of fragments in LDS
+# ---------------------------------------------------------------------------------------------- what the library says
+PRECISION_CODE = {"fp16": 0, "split": 1, "mix8": 2}      # SK_CONV_FP16, SK_CONV_SPLIT, SK_CONV_MIX8
 
 
-def make_plan(ox, oy, oz, cout):
-    """make_plan (skoots_amd/csrc/conv3d.hip:2501-2569) -> dict(mode, TY, TZ, nposp, npatch, xs, lds, XC, nxc), or None
-    where it refuses the plane geometry"""
-    xs = 2 if cout == 128 else 4                                   # conv3_xs, :2499
-    if oz <= 40:                                                   # :2503
-        mode, TZ, TY = 0, oz, None
-        npatch = (oy * oz + kPatch - 1) // kPatch                  # :2509
-        nposp = (kPatch + 2 * oz + 2 + 15) // 16 * 16              # :2510
-    else:
-        mode, TZ = 1, (16 if cout == 32 else 32)                   # :2517
-        TY = kPatch // TZ
-        nzc = (oz + TZ - 1) // TZ
-        npatch = ((oy + TY - 1) // TY) * nzc                       # :2524
-        nposp = ((TY + 2) * (TZ + 2) + 15) // 16 * 16              # :2525
-    if nposp > 64 * kMaxDma:                                       # :2527
-        return None
-    pads = 0 if cout == 32 else 4 * kPadBytes                      # :2529
-    lds = (xs + 2) * (nposp + kZeroPos) * kPosBytes + pads         # :2530
-    if xs == 4 and lds > kLdsTwoPerCU:                             # :2537
-        xs = 3
-        lds = (xs + 2) * (nposp + kZeroPos) * kPosBytes + pads
-    nxc = (kTarget + npatch * kPlanBatch - 1) // (npatch * kPlanBatch)   # :2548
-    if cout == 32 and mode == 0:                                   # :2554
-        nxc = 2 if nxc >= 4 else (nxc + 1) // 2
-    nxc = max(1, min(nxc, (ox + 2 * xs - 1) // (2 * xs)))          # :2555-2557
-    XC = (ox + nxc - 1) // nxc                                     # :2558
-    XC = (XC + xs - 1) // xs * xs                                  # :2565
-    return dict(mode=mode, TY=TY, TZ=TZ, nposp=nposp, npatch=npatch, xs=xs, lds=lds, XC=XC, nxc=(ox + XC - 1) // XC)
-
-
-def px_covers(p, oz):
-    """conv3_px_covers (skoots_amd/csrc/conv3d.hip:2610)"""
-    return p["mode"] == 0 and p["nposp"] == kPxPositions and kPatch + 2 * oz + 2 + 6 <= kPxPositions
+def library_route(case, precision, twin=False):
+    """sk_conv3d_route (host only: no GPU) for a case as sk_conv3d / sk_conv3d_split would launch it -> the filled
+    skoots_amd._ffi.ConvRoute; ValueError with the launch's message for a shape the launch refuses"""
+    from skoots_amd import _ffi
+    B, (ox, oy, oz), srcdef, cout, k = case
+    arr = (_ffi.ConvSrc * len(srcdef))()
+    for a, (c, up) in zip(arr, srcdef):
+        a.data, a.affine, a.c, a.upsample = None, None, c, up
+    r = _ffi.ConvRoute()
+    fn = getattr(_ffi.lib, "sk_conv3d_route" + ("_bf16" if twin else ""))
+    _ffi.check(fn(0, PRECISION_CODE[precision], arr, len(srcdef), B, ox, oy, oz, cout, k, r))
+    return r
 
 
 def route(case, precision):
-    """The instantiation sk_conv3d (precision "fp16") or sk_conv3d_split ("split") launches for a case: the `if` chain of
-    conv3d_impl (skoots_amd/csrc/conv3d.hip:2833-2853 for ksize 3, :2858-2889 for ksize 1 / 2) and launch_down2 (:2705-2708)"""
+    """The instantiation sk_conv3d (precision "fp16") or sk_conv3d_split ("split") launches for a case: conv3d_route of
+    skoots_amd/csrc/conv3d.hip, asked through sk_conv3d_route"""
     assert precision in ("fp16", "split")
-    _, (ox, oy, oz), srcdef, cout, k = case
-    split = precision == "split"
-    tail = ",split>" if split else ">"
-    if k == 3:
-        p = make_plan(ox, oy, oz, cout)
-        nchunks = sum(c for c, _ in srcdef) // 32                  # :2758 (split: three phase chunks each, :2769-2771)
-        assert p is not None and nchunks * (3 if split else 1) <= kMaxChunks
-        if split:                                                  # :2833-2837
-            return f"m16<{p['xs']}{tail}" if cout == 32 else f"conv3<{cout},{p['xs']}{tail}"
-        if cout == 32 and nchunks == 1 and len(srcdef) == 1 and not srcdef[0][1] and px_covers(p, oz):   # :2838
-            return "px"
-        if cout == 32:                                             # :2843-2851
-            if p["xs"] == 3:
-                return "m16<3>"
-            if nchunks == 1:
-                if p["lds"] + 2 * kTapRowBytes <= kLdsTwoPerCU:
-                    return "m16<4,3,2>"
-                if p["lds"] + 1 * kTapRowBytes <= kLdsTwoPerCU:
-                    return "m16<4,3,1>"
-                return "m16<4,3,0>"
-            return "m16<4>"
-        return f"conv3<{cout},{p['xs']}>"                          # :2852-2853
-    (c, up), = srcdef                                              # :2856: one plain source
-    assert not up and c % 16 == 0 and c <= 128
-    if not split and k == 2 and (c, cout) in ((32, 64), (64, 128)):   # :2858
-        return f"down2<{cout},{c}>"
-    nsteps = k ** 3 * (c // 16)                                    # :2878
-    assert nsteps % 2 == 0
-    if split:                                                      # :2882-2883
-        return f"gather<{cout},split>"
-    return f"gather<{cout},{'deep' if nsteps % 4 == 0 else '2'}>"   # :2880, :2884-2889
+    return library_route(case, precision).name.decode()
+
+
+def library_names(precision, twin=False):
+    """sk_conv3d_route_name until NULL: every kernel a launch of the precision can reach"""
+    from skoots_amd import _ffi
+    fn = getattr(_ffi.lib, "sk_conv3d_route_name" + ("_bf16" if twin else ""))
+    names = []
+    while fn(PRECISION_CODE[precision], len(names)) is not None:
+        names.append(fn(PRECISION_CODE[precision], len(names)).decode())
+    return names
+
+
+# ---------------------------------------------------------------------------------------------- the plan mirror
+# An independent restatement of the numbers conv3d_route hands a launch; tests compare the library's with these.
+kPosBytes = 64            # skoots_amd/csrc/conv3_device.h
+kPatch = 128              # skoots_amd/csrc/conv3_device.h
+kPadBytes = 32 * 64       # skoots_amd/csrc/conv3_device.h (32 * kPadStride)
+kZeroPos = 4              # skoots_amd/csrc/common.h (SK_ZERO_WINDOW, the default build)
+kMaxDma = 4               # skoots_amd/csrc/conv3d.hip
+kMaxChunks = 24           # skoots_amd/csrc/conv3d.hip
+kLdsTwoPerCU = 80 * 1024  # make_plan, conv3d_route: two workgroups per CU need <= 80 KiB each
+kPlanBatch = 8            # make_plan
+kTarget = 256 * 2 * 8     # make_plan (`target`)
+
+
+def make_plan(ox, oy, oz, cout):
+    """make_plan (skoots_amd/csrc/conv3d.hip) -> dict(mode, TY, TZ, nposp, npatch, xs, lds, XC, nxc), or None where it
+    refuses the plane geometry"""
+    xs = 2 if cout == 128 else 4                                   # conv3_xs
+    if oz <= 40:
+        mode, TZ, TY = 0, oz, None
+        npatch = (oy * oz + kPatch - 1) // kPatch
+        nposp = (kPatch + 2 * oz + 2 + 15) // 16 * 16
+    else:
+        mode, TZ = 1, (16 if cout == 32 else 32)
+        TY = kPatch // TZ
+        nzc = (oz + TZ - 1) // TZ
+        npatch = ((oy + TY - 1) // TY) * nzc
+        nposp = ((TY + 2) * (TZ + 2) + 15) // 16 * 16
+    if nposp > 64 * kMaxDma:
+        return None
+    pads = 0 if cout == 32 else 4 * kPadBytes
+    lds = (xs + 2) * (nposp + kZeroPos) * kPosBytes + pads
+    if xs == 4 and lds > kLdsTwoPerCU:
+        xs = 3
+        lds = (xs + 2) * (nposp + kZeroPos) * kPosBytes + pads
+    nxc = (kTarget + npatch * kPlanBatch - 1) // (npatch * kPlanBatch)
+    if cout == 32 and mode == 0:
+        nxc = 2 if nxc >= 4 else (nxc + 1) // 2
+    nxc = max(1, min(nxc, (ox + 2 * xs - 1) // (2 * xs)))
+    XC = (ox + nxc - 1) // nxc
+    XC = (XC + xs - 1) // xs * xs
+    return dict(mode=mode, TY=TY, TZ=TZ, nposp=nposp, npatch=npatch, xs=xs, lds=lds, XC=XC, nxc=(ox + XC - 1) // XC)
 
 
 def num_blocks(case):
-    """sk_conv3d_num_blocks (skoots_amd/csrc/conv3d.hip:2621-2630): rows of gn_partial per sample"""
+    """sk_conv3d_num_blocks: rows of gn_partial per sample"""
     _, (ox, oy, oz), _, cout, k = case
     if k == 3:
         p = make_plan(ox, oy, oz, cout)
@@ -183,10 +178,12 @@ CASES = [
     ((2, (5, 9, 7), S32, 32, 1), "gather<32,2>", "gather<32,split>"),          # cin 32: two K steps, depth 2; two blocks, ragged
     ((1, (1, 9, 10), S32, 64, 1), "gather<64,2>", "gather<64,split>"),         # ox = 1
     ((1, (5, 9, 5), S32, 128, 1), "gather<128,2>", "gather<128,split>"),
-    ((1, (12, 5, 5), S64, 32, 1), "gather<32,deep>", "gather<32,split>"),      # 300 voxels
+    ((1, (12, 5, 5), S64, 32, 1), "pointwise<32,64>", "gather<32,split>"),     # 300 voxels: two blocks, ragged; z = 5
+    ((2, (1, 9, 5), S64, 32, 1), "pointwise<32,64>", "gather<32,split>"),      # ox = 1, batch 2
     ((2, (3, 7, 10), S128, 32, 1), "gather<32,deep>", "gather<32,split>"),
     ((1, (5, 7, 9), S64, 64, 1), "gather<64,deep>", "gather<64,split>"),
-    ((1, (9, 10, 5), S128, 64, 1), "gather<64,deep>", "gather<64,split>"),
+    ((1, (9, 10, 5), S128, 64, 1), "pointwise<64,128>", "gather<64,split>"),   # 450 voxels: two blocks, ragged; z = 5
+    ((2, (1, 9, 5), S128, 64, 1), "pointwise<64,128>", "gather<64,split>"),    # ox = 1, batch 2
     ((1, (5, 3, 9), S64, 128, 1), "gather<128,deep>", "gather<128,split>"),    # 135 voxels: a second block of seven
     ((2, (1, 5, 9), S128, 128, 1), "gather<128,deep>", "gather<128,split>"),   # ox = 1, batch 2
 ]
@@ -198,20 +195,27 @@ def named(case, precision):
     return CASES[ALL.index(case)][1 if precision == "fp16" else 2]
 
 
-# every instantiation conv3d_impl / launch_down2 can launch without an SK_TUNING switch (mix8 has its own entry point)
+# every instantiation sk_conv3d ("fp16") and sk_conv3d_split ("split") can launch in the release build: literal, and held
+# equal to what sk_conv3d_route_name lists (tests/test_conv16_cases_cpu.py), so that a kernel added to the library's tables
+# without a case here fails on the CPU
 REACHABLE = {
     "fp16": {"px", "m16<4,3,2>", "m16<4,3,1>", "m16<4,3,0>", "m16<4>", "m16<3>", "conv3<64,4>", "conv3<64,3>", "conv3<128,2>",
              "down2<64,32>", "down2<128,64>", "gather<32,deep>", "gather<32,2>", "gather<64,deep>", "gather<64,2>",
-             "gather<128,deep>", "gather<128,2>"},
+             "gather<128,deep>", "gather<128,2>", "pointwise<32,64>", "pointwise<64,128>"},
     "split": {"m16<4,split>", "m16<3,split>", "conv3<64,4,split>", "conv3<64,3,split>", "conv3<128,2,split>",
               "gather<32,split>", "gather<64,split>", "gather<128,split>"},
 }
+# the names without cases in this table (tests/test_hip_unet.py runs them against torch): what sk_conv3d_mix8 launches, and
+# the LDS-staged stride-2 pairs of sk_conv3d_down_act (fp16: the kernels of sk_conv3d's ksize 2), _split and _mix8
+MIX8 = {"pxm", "m16<4,mix8>", "m16<3,mix8>", "conv3<64,4,mix8>", "conv3<64,3,mix8>", "conv3<128,2,mix8>"}
+DOWN_ACT = {"fp16": {"down2<64,32>", "down2<128,64>"}, "split": {"down2<64,32,split>", "down2<128,64,split>"},
+            "mix8": {"down2<64,32,split>", "down2<128,64,split>"}}
 # one case per route that honours a store box, each with x >= 3 so that a box fits strictly inside
 BOX_CASES = [ALL[0], ALL[3], ALL[6], ALL[8], ALL[10]]
 
 
 def family(name):
-    """px | m16 | conv3 | down2 | gather"""
+    """px | m16 | conv3 | down2 | gather | pointwise"""
     return name.split("<")[0]
 
 

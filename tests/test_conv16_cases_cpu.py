@@ -1,8 +1,10 @@
-"""What makes the assertions of tests/test_hip_conv16_exact.py mean something, checked from the references and the dispatch
-mirror of tests/conv16_cases.py alone (CPU).
+"""What makes the assertions of tests/test_hip_conv16_exact.py mean something, checked from the references of
+tests/conv16_cases.py and the library's host-only route queries alone (CPU).
 
-The routes: the GPU test claims to run every instantiation conv3d_impl can launch; that holds only if the table's cases
-reach them, which `route` -- make_plan and the dispatch chain restated -- decides here.  Integer and split_exact operands: the
+The routes: the GPU test claims to run every instantiation sk_conv3d and sk_conv3d_split can launch; that holds only if the
+table's cases reach them, which `route` -- conv3d_route of skoots_amd/csrc/conv3d.hip itself, through sk_conv3d_route -- decides
+here: every name, threshold and edge asserted below pins the library, and the names sk_conv3d_route_name lists must be the
+ones written out in the table.  The plan's numbers are held against conv16_cases.make_plan, an independent restatement.  Integer and split_exact operands: the
 GPU test demands bit equality with float64, a fair demand only while every partial accumulation of the kernel, in whatever
 order it runs, is exact in fp32 -- the conv's own sums, the 16-bit store and the GroupNorm sums.  Realistic operands: the GPU
 test holds the fp16 kernels' GroupNorm totals to d16 / 10 of the definition each implements; that separates "sums of the stored
@@ -19,18 +21,80 @@ PRECISIONS = ("fp16", "split")
 
 
 def test_routes_cover_every_reachable_instantiation():
-    """Over the table, `route` returns exactly the 17 fp16 and 8 split instantiations that conv3d_impl and launch_down2 can
-    launch without an SK_TUNING switch -- written out in conv16_cases.REACHABLE and again here for the ones the suite never
-    reached before -- and for every case the name written next to it."""
+    """Over the table, the library's route is exactly the 19 fp16 and 8 split instantiations that sk_conv3d and
+    sk_conv3d_split can launch in the release build -- written out in conv16_cases.REACHABLE and again here for the ones the
+    suite never reached before -- and for every case the name written next to it.  REACHABLE, together with the literal
+    lists of the entry points that have no cases here (sk_conv3d_mix8, sk_conv3d_down_act*), is what sk_conv3d_route_name
+    lists per precision: a kernel added to the library's tables without a case here fails this test."""
     for prec in PRECISIONS:
         assert {K.route(c, prec) for c in K.ALL} == K.REACHABLE[prec]
         for c in K.ALL:
             assert K.route(c, prec) == K.named(c, prec), (K.case_id(c), prec)
-    assert len(K.REACHABLE["fp16"]) == 17 and len(K.REACHABLE["split"]) == 8
+    assert len(K.REACHABLE["fp16"]) == 19 and len(K.REACHABLE["split"]) == 8
+    assert K.DOWN_ACT["fp16"] <= K.REACHABLE["fp16"]               # sk_conv3d_down_act runs sk_conv3d's ksize-2 kernels
+    for twin in (False, True):
+        for prec, want in (("fp16", K.REACHABLE["fp16"]), ("split", K.REACHABLE["split"] | K.DOWN_ACT["split"]),
+                           ("mix8", K.MIX8 | K.DOWN_ACT["mix8"])):
+            names = K.library_names(prec, twin)
+            assert len(names) == len(set(names)) and set(names) == want, (prec, twin, set(names) ^ want)
+    assert len(K.MIX8) == 6 and all(len(v) == 2 for v in K.DOWN_ACT.values())
     assert {"m16<3>", "m16<4,3,0>", "gather<32,2>", "gather<64,2>", "gather<128,2>", "conv3<128,2>"} <= K.REACHABLE["fp16"]
     assert {"m16<3,split>", "conv3<64,3,split>"} <= K.REACHABLE["split"]
     assert [K.route(c, "fp16") for c in K.BOX_CASES] == ["px", "m16<4,3,2>", "m16<4,3,1>", "m16<4,3,0>", "m16<3>"]
     assert all(min(c[1]) >= 3 for c in K.BOX_CASES)                 # a box strictly inside the tile exists
+
+
+def _sweep():
+    """the table, and shapes around every threshold of the plan and the dispatch: z 1 .. 129 for the 3x3x3 layer kinds, every
+    (cin, cout) pair of ksize 1 and 2"""
+    out = list(K.ALL)
+    for z in range(1, 130):
+        for srcdef, cout in ((K.S32, 32), (K.S64, 32), (K.S64, 64), (K.S128, 128), ([(32, 0), (32, 1)], 32), (K.S32, 64)):
+            out.append((1, (8, 8, z if len(srcdef) == 1 else 2 * ((z + 1) // 2)), srcdef, cout, 3))
+    for k in (1, 2):
+        for c in (32, 64, 128):
+            for cout in (32, 64, 128):
+                out += [(2, osp, [(c, 0)], cout, k) for osp in ((2, 2, 2), (5, 9, 7), (1, 3, 5))]
+    return out
+
+
+def test_library_plan_equals_the_mirror():
+    """Over the table and the sweep, for both precisions and in the bf16 twin: the plan integers sk_conv3d_route reports are
+    those of conv16_cases.make_plan, its row count is num_blocks(case) and what sk_conv3d_num_blocks returns (the GPU test
+    asserts the same where it runs), the grid is B x rows, and the twin routes every case as the fp16 build does."""
+    from skoots_amd import _ffi
+    for case in _sweep():
+        B, (ox, oy, oz), _, cout, k = case
+        for prec in PRECISIONS:
+            r = K.library_route(case, prec)
+            assert r.num_blocks == K.num_blocks(case) and r.grid == B * r.num_blocks, (K.case_id(case), prec)
+            p = K.make_plan(ox, oy, oz, cout) if k == 3 else dict(mode=0, TZ=0, nposp=0, npatch=0, xs=0, lds=0, XC=0, nxc=0)
+            assert (r.mode, r.tz, r.nposp, r.npatch, r.xs, r.plan_lds, r.xc, r.nxc) == \
+                   tuple(p[key] for key in ("mode", "TZ", "nposp", "npatch", "xs", "lds", "XC", "nxc")), (K.case_id(case), prec)
+            assert r.lds >= r.plan_lds or r.name in (b"px", b"pxm")
+            t = K.library_route(case, prec, twin=True)
+            assert bytes(t) == bytes(r), (K.case_id(case), prec)
+        for twin in ("", "_bf16"):
+            assert getattr(_ffi.lib, "sk_conv3d_num_blocks" + twin)(B, ox, oy, oz, cout, k) == K.num_blocks(case), K.case_id(case)
+
+
+def test_library_refuses_what_the_launch_refuses():
+    """sk_conv3d_route answers SK_ERR_ARG with the launch's message"""
+    for case, prec, msg in (((1, (4, 4, 4), [(48, 0)], 32, 3), "fp16", "multiple of 32 channels"),
+                            ((1, (4, 4, 4), K.S32, 48, 3), "fp16", "cout must be 32, 64 or 128"),
+                            ((1, (4, 4, 4), [(32, 1)], 32, 3), "fp16", "only the second source may be upsampled"),
+                            ((1, (4, 4, 5), [(32, 0), (32, 1)], 32, 3), "split", "even output extents"),
+                            ((1, (4, 4, 4), [(128, 0), (128, 0)], 128, 3), "fp16", None),
+                            ((1, (4, 4, 4), [(160, 0), (128, 0)], 128, 3), "split", "too many input channels (288)"),
+                            ((1, (4, 4, 4), [(32, 0), (32, 0)], 32, 1), "fp16", "ksize 1 takes one plain source"),
+                            ((1, (4, 4, 4), [(24, 0)], 32, 1), "fp16", "multiple of 16"),
+                            ((1, (4, 4, 4), [(16, 0)], 32, 1), "fp16", "needs 32 <= cin <= 128 (got 16)"),
+                            ((1, (4, 4, 4), K.S32, 32, 4), "fp16", "ksize must be 1, 2 or 3")):
+        if msg is None:
+            assert K.route(case, prec) == "conv3<128,2>"
+            continue
+        with pytest.raises(ValueError, match=msg.replace("(", r"\(").replace(")", r"\)")):
+            K.library_route(case, prec)
 
 
 def test_route_thresholds_of_cout_32():
@@ -65,22 +129,23 @@ def _ragged(case):
 
 
 def test_case_table_holds_the_edges_it_names():
-    """Per kernel family (px, m16, conv3, down2, gather in fp16; m16, conv3, gather in split), stated from the shapes: batch 2;
+    """Per kernel family (px, m16, conv3, down2, gather, pointwise in fp16; m16, conv3, gather in split), stated from the shapes: batch 2;
     a ragged last patch (linear and, for m16 and conv3, rectangle mode) or block; ox = 1; z = 5 where the family takes it; for
     the 3x3x3 families an x extent that is no multiple of XS and two or more x-chunks with a ragged last one.  Two sources
     with an upsampled second one for cout 32, 64 and 128; the 128 + 128 concat with 8 chunks (24 = kMaxChunks in split); ksize
     2 on both LDS-staged pairs and on one pair of the gather kernel; ksize 1 with cin 32 (depth 2) and with cin 64 and 128
-    (deep) for cout 32, 64 and 128.  Every case stays under 10^4 output voxels."""
+    (deep, but for the two channel reducers 64 -> 32 and 128 -> 64, which are the pointwise family's) for cout 32, 64 and 128.
+    Every case stays under 10^4 output voxels."""
     for prec in PRECISIONS:
         fams = {}
         for c in K.ALL:
             fams.setdefault(K.family(K.route(c, prec)), []).append(c)
-        assert set(fams) == ({"px", "m16", "conv3", "down2", "gather"} if prec == "fp16" else {"m16", "conv3", "gather"})
+        assert set(fams) == ({"px", "m16", "conv3", "down2", "gather", "pointwise"} if prec == "fp16" else {"m16", "conv3", "gather"})
         for fam, cs in fams.items():
             assert any(c[0] == 2 for c in cs), (prec, fam, "batch 2")
             assert any(c[1][0] == 1 for c in cs), (prec, fam, "ox = 1")
             rag = {_ragged(c) for c in cs}
-            if fam in ("down2", "gather"):
+            if fam in ("down2", "gather", "pointwise"):
                 assert "block" in rag, (prec, fam)
                 assert any(K.num_blocks(c) >= 2 for c in cs), (prec, fam, "more than one block")
                 assert any(c[1][2] == 5 for c in cs), (prec, fam, "z = 5")
@@ -116,7 +181,13 @@ def test_case_table_holds_the_edges_it_names():
     for cout in (32, 64, 128):
         assert K.route((1, (2, 2, 2), K.S32, cout, 1), "fp16") == f"gather<{cout},2>"
         assert (64, cout) in k1 and (128, cout) in k1
-        assert K.route((1, (2, 2, 2), K.S64, cout, 1), "fp16") == K.route((1, (2, 2, 2), K.S128, cout, 1), "fp16") == f"gather<{cout},deep>"
+    k1_deep = {(c, cout): K.route((1, (2, 2, 2), [(c, 0)], cout, 1), "fp16") for c in (64, 128) for cout in (32, 64, 128)}
+    assert k1_deep == {(64, 32): "pointwise<32,64>", (128, 32): "gather<32,deep>", (64, 64): "gather<64,deep>",
+                       (128, 64): "pointwise<64,128>", (64, 128): "gather<128,deep>", (128, 128): "gather<128,deep>"}
+    for name in ("pointwise<32,64>", "pointwise<64,128>"):          # either reducer on its own: every edge of the block families
+        cs = [c for c in K.ALL if K.route(c, "fp16") == name]
+        assert any(c[0] == 2 for c in cs) and any(c[1][0] == 1 for c in cs) and any(_ragged(c) for c in cs), name
+        assert any(K.num_blocks(c) >= 2 for c in cs) and any(c[1][2] == 5 for c in cs), name
     assert all(c[0] * c[1][0] * c[1][1] * c[1][2] < 10 ** 4 for c in K.ALL)
 
 

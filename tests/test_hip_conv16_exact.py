@@ -1,6 +1,7 @@
 """GPU tests of the fp16 and split conv kernels of skoots_amd/csrc/conv3d.hip through the C ABI -- sk_conv3d, sk_conv3d_split and
-sk_conv3d_box on every instantiation conv3d_impl can launch (conv3_px_kernel, conv3_m16_kernel, conv3_kernel, down2_act_kernel,
-gather_gemm_kernel; tests/test_conv16_cases_cpu.py proves which case reaches which) -- against float64 references of the
+sk_conv3d_box on every instantiation they can launch (conv3_px_kernel, conv3_m16_kernel, conv3_kernel, down2_act_kernel,
+gather_gemm_kernel, pointwise_lds_kernel; tests/test_conv16_cases_cpu.py asks the library which case reaches which and
+holds its name list to the table's) -- against float64 references of the
 same operations (tests/conv16_cases.py).
 
   * integer operands: fp16 products of small integers are exact and the MFMAs accumulate in fp32, so with every partial
@@ -151,7 +152,7 @@ def test_conv_split_exact_three_products(env, case):
     (x_hi, w_lo), (x_hi, w_hi), (x_lo, w_hi), and that no lo * lo product is formed.  The totals are not exact here (sum |y| in
     units of 2^-13 passes 2^24): the rows summed in float64 against the float64 totals of the reference with the allowance of
     test_conv_split_vs_torch, rtol 1e-4 + atol 1e-3 sqrt(voxels) for the sums and rtol 1e-4 for the sums of squares.
-    Measured on the MI355X over the 40 cases: the sums use at most 2.2e-3 of that allowance (0 in 16 cases), the sums of
+    Measured on the MI355X over the 42 cases: the sums use at most 2.2e-3 of that allowance (0 in 18 cases), the sums of
     squares 3.5e-4 .. 1.5e-3 of theirs -- fp32 summation noise; a voxel wrongly counted would still show in tests a and b."""
     his, los, w, b, want, want_tot = K.split_exact_expected(case)
     out, partial = _run(env, case, "split", _pair_lines(his, los), w, b)
@@ -166,20 +167,22 @@ def test_conv_split_exact_three_products(env, case):
 
 
 # ============================================================================================ d: fp16, realistic totals
-ACCUMULATORS = ("down2", "gather")      # families whose fp16 epilogue sums its fp32 accumulators; px, m16, conv3: the stored values
+# families whose fp16 epilogue sums its fp32 accumulators (pointwise_lds_kernel's adds x0 .. x3 of `acc` next to the
+# rounding store, as gather_gemm_kernel's does); px, m16, conv3: the stored values
+ACCUMULATORS = ("down2", "gather", "pointwise")
 
 
 @pytest.mark.parametrize("case", K.ALL, ids=IDS)
 def test_conv_fp16_realistic_totals(env, case):
     """sk_conv3d on randn fp16 activations, randn / sqrt(cin k^3) weights, 0.1 randn biases: what gn_partial holds.
     conv3_px_kernel, conv3_m16_kernel and conv3_kernel sum the values as STORED (the rounded 16-bit results, on v_dot2c);
-    gather_gemm_kernel and down2_act_kernel sum their fp32 ACCUMULATORS (read from the code; include/skoots_hip.h says so
-    too).  The rows summed in float64 are held to d16 / 10 of the definition the kernel implements -- computed from the kernel's
+    gather_gemm_kernel, pointwise_lds_kernel and down2_act_kernel sum their fp32 ACCUMULATORS (read from the code;
+    include/skoots_hip.h says so too).  The rows summed in float64 are held to d16 / 10 of the definition the kernel implements -- computed from the kernel's
     own stored output for the first, from the float64 conv of the same fp16 operands for the second -- with d16 the distance
     between the two definitions on this case (tests/test_conv16_cases_cpu.py: fp32 summation error is at least ten times
     smaller still).  An epilogue that implements the other definition misses the bound tenfold.
-    Measured on the MI355X over the 40 cases, in units of d16 (the bound is 0.1): stored values (px, m16, conv3) sums
-    0.0003 .. 0.0010, sums of squares 0.0009 .. 0.0076; accumulators (down2, gather) sums 0.0005 .. 0.0017, sums of squares
+    Measured on the MI355X over the 42 cases, in units of d16 (the bound is 0.1): stored values (px, m16, conv3) sums
+    0.0003 .. 0.0010, sums of squares 0.0009 .. 0.0076; accumulators (down2, gather, pointwise) sums 0.0003 .. 0.0017, sums of squares
     0.0006 .. 0.0044; absolute 1.9e-6 .. 2.3e-5 and 9.3e-6 .. 4.8e-4.  The other definition lies 0.94 .. 1.04 d16 away."""
     srcs, w, b, y, t_acc, t_st, d16, _ = K.realistic_expected(case)
     out, partial = _run(env, case, "fp16", _fp16_lines(srcs), w, b)

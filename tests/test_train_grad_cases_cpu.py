@@ -1,9 +1,11 @@
-"""What makes the assertions of tests/test_hip_train_grad_exact.py mean something, checked from the dispatch mirror, the
-operands and the float64 references of tests/train_grad_cases.py alone (CPU).
+"""What makes the assertions of tests/test_hip_train_grad_exact.py mean something, checked from the operands and the float64
+references of tests/train_grad_cases.py and the library's host-only route queries alone (CPU).
 
 The routes: the GPU test claims to run all 14 weight-gradient instantiations of skoots_amd/csrc/train.hip; that holds only if
-the table's cases reach them, which `route` -- the three entry points' dispatch restated -- decides here, together with the
-edges each route family is meant to meet (batch 2, an upsampled second source, several chunks, several channel tiles, ragged
+the table's cases reach them, which `route` -- wgrad_route of train.hip itself, through sk_train_conv_wgrad_route -- decides
+here: every name and boundary asserted below pins the library, the names sk_train_conv_wgrad_route_name lists must be the
+ones written out in the table, and the route's numbers are held against train_grad_cases.plan, an independent restatement;
+together with the edges each route family is meant to meet (batch 2, an upsampled second source, several chunks, several channel tiles, ragged
 channels, chunks left empty by the 16-rounding).  The operands: the GPU test demands bit equality with float64, a fair demand
 only while every partial sum of the kernels, in whatever order they run, is an exact fp32 value -- operands exact in the
 16-bit type, sums of absolute products below 2^24 units, results inside the exact range of the type that stores them.
@@ -39,6 +41,10 @@ def test_routes_equal_the_written_ones_and_cover_every_instantiation():
     assert T.REACHABLE["f16"] == {"wgrad16x", "wgrad16y"} | {f"wgrad16{t}<{n}>" for t in ("t", "") for n in (9, 8, 1)}
     assert T.REACHABLE["stem_f16"] == {"wgrad_stem16", "wgrad_stem<true>"}
     assert sum(len(v) for v in T.REACHABLE.values()) == 14
+    for entry in T.ENTRIES:
+        for twin in (False, True):
+            names = T.library_names(entry, twin)
+            assert len(names) == len(set(names)) and set(names) == T.REACHABLE[entry], (entry, twin, names)
 
 
 def test_every_route_family_meets_its_edges():
@@ -116,6 +122,57 @@ def test_plan_and_workspace_agree(case):
     p = T.plan(case)
     row = cout * T.cin_of(case) * k ** 3 + cout
     assert T.workspace_floats(case) == max(p["nchunk"], p["nchunk_x"]) * row
+
+
+def _probes():
+    """the table and shapes around the x-marching kernel's conditions"""
+    return T.ALL + [(B, (ox, oy, oz), [(c, 0)], cout, 3) for B in (1, 2, 3) for ox in (1, 2, 7, 64) for oy in (15, 16, 48)
+                    for oz in (16, 32, 64) for c, cout in ((32, 32), (64, 128), (31, 32))]
+
+
+@pytest.mark.parametrize("twin", [False, True])
+def test_exported_workspace_size_is_the_mirrors(twin):
+    """sk_train_conv_wgrad_workspace_floats (a host function) against the restated plan, over the table and over shapes around
+    the x-marching kernel's conditions: with one or two planes its row count exceeds or equals the plan's and sizes the
+    workspace (asserted for some probes of batch 1 and of batch >= 2), with more planes the plan's does"""
+    from skoots_amd import _ffi
+    probes = _probes()
+    for B in (1, 2):
+        assert any(T.plan(c)["nchunk_x"] > T.plan(c)["nchunk"] for c in probes if c[0] >= B)
+    assert any(0 < T.plan(c)["nchunk_x"] < T.plan(c)["nchunk"] for c in probes)
+    fn = getattr(_ffi.lib, "sk_train_conv_wgrad_workspace_floats" + ("_bf16" if twin else ""))
+    for case in probes:
+        B, (ox, oy, oz), _, cout, k = case
+        assert int(fn(B, ox, oy, oz, cout, T.cin_of(case), k)) == T.workspace_floats(case), T.case_id(case)
+
+
+def test_library_plan_equals_the_mirror():
+    """Over the table and the probes, through every entry point that takes the case, with and without a zero page: the
+    integers sk_train_conv_wgrad_route reports are the mirror's -- the chunking after the entry's 16-rounding, the x-marching
+    kernel's rows and segments, wgrad16y's columns a chunk, the workspace size -- its `nchunk` is the row count the chosen
+    kernel writes (wgrad16x: its own), the grid is what that kernel's launch geometry makes of them, and the bf16 twin
+    answers the same."""
+    for case in _probes():
+        B, (ox, oy, oz), _, cout, k = case
+        tiles = ((cout + 31) // 32) * ((T.cin_of(case) + 31) // 32)
+        for entry in T.ENTRIES:
+            if not T.accepts(case, entry):
+                continue
+            for zp in ((False, True) if entry == "f16" else (False,)):
+                r, p, what = T.library_route(case, entry, zp), T.plan(case, entry), (T.case_id(case), entry, zp)
+                name = r.name.decode()
+                rows = p["nchunk_x"] if name == "wgrad16x" else p["nchunk"]
+                assert (r.nchunk, r.nchunk_b, r.chunk, r.ngroup) == (rows, p["nchunk_b"], p["chunk"], p["ngroup"]), what
+                assert (r.nchunk_x, r.nxs, r.xseg) == (p["nchunk_x"], p["nxs"], p["xseg"]), what
+                assert r.workspace_floats == T.workspace_floats(case), what
+                assert r.ncol_chunk == (T.y_columns(case)[1] if name == "wgrad16y" else 0), what
+                if name in ("wgrad16x", "wgrad16y"):                # whole launch rounds of eight chunks
+                    assert r.grid == (rows + 7) // 8 * 8 * tiles * (3 if name == "wgrad16y" else 1), what
+                elif name.startswith("wgrad_stem"):
+                    assert r.grid == rows, what
+                else:
+                    assert r.grid == rows * tiles * p["ngroup"], what
+                assert bytes(T.library_route(case, entry, zp, twin=True)) == bytes(r), what
 
 
 def test_route_boundaries():

@@ -1,4 +1,4 @@
-"""The cases, dispatch mirror, seeded operands and float64 references that tests/test_train_grad_cases_cpu.py and
+"""The cases, plan mirror, seeded operands and float64 references that tests/test_train_grad_cases_cpu.py and
 tests/test_hip_train_grad_exact.py share (torch on the CPU only): the conv gradients of the training step in
 skoots_amd/csrc/train.hip -- the weight gradient behind sk_train_conv_wgrad, sk_train_conv_wgrad_f16 and
 sk_train_stem_wgrad_f16, and the 16-bit data gradient sk_train_pack_weight + sk_conv3d (+ sk_train_interleave2).
@@ -6,9 +6,11 @@ sk_train_stem_wgrad_f16, and the 16-bit data gradient sk_train_pack_weight + sk_
 A case is ``(B, out spatial, [(C, up)], cout, ksize)``, the tuple of BWD_CASES in tests/test_hip_train.py: the layer's sources
 are concatenated along the channels, a source with ``up`` is stored at half the output extent and read through a nearest
 upsample; ksize 3 has padding 1 and stride 1, ksize 2 stride 2, ksize 1 stride 1.  CASES holds, next to every case, the
-instantiation it runs through each entry point -- what ``route`` (a restatement of the three entry points' dispatch without
-the SK_TUNING switches, which the product build compiles out) returns for it; tests/test_train_grad_cases_cpu.py asserts
-every column and that together they cover every reachable instantiation.
+instantiation it runs through each entry point -- what ``route`` returns for it, which is the library's own answer: wgrad_route
+of skoots_amd/csrc/train.hip, the one function the three entry points ask, through the host-only sk_train_conv_wgrad_route.
+tests/test_train_grad_cases_cpu.py asserts every column and that together they cover every name
+sk_train_conv_wgrad_route_name lists.  ``plan``, ``y_columns`` and ``workspace_floats`` stay an independent restatement of the
+route's numbers, compared with the library's.
 
 Entries and route names:
 ``fp32``      sk_train_conv_wgrad:       ``wgrad_stem<false>`` (one plain 1-channel source, ksize 3), ``wgrad<9>`` ``wgrad<8>``
@@ -53,7 +55,7 @@ def is_stem(case):
 
 
 def plan(case, entry="f16"):
-    """wgrad_plan and wgrad_x_plan (skoots_amd/csrc/train.hip, above sk_train_conv_wgrad_workspace_floats) as `entry` runs them
+    """The chunking of wgrad_route (skoots_amd/csrc/train.hip), voxel chunks and x-marching footprints, as `entry` runs it
     -> dict(nchunk, nchunk_b, chunk, ngroup, nchunk_x, nxs, xseg, empty).  The 16-bit entry points round ``chunk`` up to whole
     16-voxel steps AFTER the chunk count was fixed: sk_train_conv_wgrad_f16 ("f16") always, sk_train_stem_wgrad_f16
     ("stem_f16") where Z % 16 == 0 (wgrad_stem16; wgrad_stem<true> keeps the plan's chunk), sk_train_conv_wgrad ("fp32")
@@ -106,24 +108,39 @@ def accepts(case, entry):
     return entry != "stem_f16" or (is_stem(case) and case[3] == 32)
 
 
-def route(case, entry, zero_page=False):
-    """The instantiation an entry point launches: the `if` chains of sk_train_conv_wgrad, sk_train_conv_wgrad_f16 and
-    sk_train_stem_wgrad_f16"""
+def library_route(case, entry, zero_page=False, twin=False):
+    """sk_train_conv_wgrad_route (host only: no GPU) for a case as the entry point would launch it -> the filled
+    skoots_amd._ffi.WgradRoute"""
+    from skoots_amd import _ffi
     assert entry in ENTRIES and accepts(case, entry)
-    _, (ox, oy, oz), srcdef, cout, k = case
-    nt = {3: 9, 2: 8, 1: 1}[k]
-    if entry == "fp32":
-        return "wgrad_stem<false>" if is_stem(case) else f"wgrad<{nt}>"
-    if entry == "stem_f16":
-        return "wgrad_stem16" if oz % 16 == 0 else "wgrad_stem<true>"
-    lines = zero_page and cout % 32 == 0 and all(c % 32 == 0 for c, _ in srcdef)
-    if lines and plan(case)["nchunk_x"] > 0:
-        return "wgrad16x"
-    if lines and k == 3 and oz % 16 == 0 and oy % 4 == 0:
-        return "wgrad16y"
-    return f"wgrad16t<{nt}>" if lines else f"wgrad16<{nt}>"
+    B, (ox, oy, oz), srcdef, cout, k = case
+    arr = (_ffi.ConvSrc * len(srcdef))()
+    for a, (c, up) in zip(arr, srcdef):
+        a.data, a.affine, a.c, a.upsample = None, None, c, up
+    r = _ffi.WgradRoute()
+    fn = getattr(_ffi.lib, "sk_train_conv_wgrad_route" + ("_bf16" if twin else ""))
+    _ffi.check(fn(ENTRIES.index(entry), arr, len(srcdef), B, ox, oy, oz, cout, k, int(zero_page), r))
+    return r
 
 
+def route(case, entry, zero_page=False):
+    """The instantiation an entry point launches: wgrad_route of skoots_amd/csrc/train.hip, asked through
+    sk_train_conv_wgrad_route"""
+    return library_route(case, entry, zero_page).name.decode()
+
+
+def library_names(entry, twin=False):
+    """sk_train_conv_wgrad_route_name until NULL: every kernel the entry point can reach in the release build"""
+    from skoots_amd import _ffi
+    fn = getattr(_ffi.lib, "sk_train_conv_wgrad_route_name" + ("_bf16" if twin else ""))
+    names = []
+    while fn(ENTRIES.index(entry), len(names)) is not None:
+        names.append(fn(ENTRIES.index(entry), len(names)).decode())
+    return names
+
+
+# literal, and held equal to what sk_train_conv_wgrad_route_name lists (tests/test_train_grad_cases_cpu.py): a kernel added
+# to the library's tables without a case below fails on the CPU
 REACHABLE = {
     "fp32": {"wgrad_stem<false>", "wgrad<9>", "wgrad<8>", "wgrad<1>"},
     "f16": {"wgrad16x", "wgrad16y", "wgrad16t<9>", "wgrad16t<8>", "wgrad16t<1>", "wgrad16<9>", "wgrad16<8>", "wgrad16<1>"},
