@@ -1233,6 +1233,29 @@ int sk_instance_contacts(const int32_t* labels, int X, int Y, int Z, const int32
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * The image under every instance (ABI 25; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* sk_instance_intensity: one pass over an (X, Y, Z) int32 instance mask and an image of the same shape (z fastest both)
+ * measures the image under every instance.  labels, lut, max_id and N are those of sk_instance_stats.  image holds
+ * unsigned samples of elem_bytes = 1 or 2 bytes; the histogram bin of a sample v is min(v >> shift, 255), shift 0 .. 8
+ * (0 for 1-byte samples).  Row r fills
+ *   moments[(r - 1) * 6 ..]  int64: n, S v, S v^2, S v x, S v y, S v z over the row's voxels, x, y, z the voxel indices;
+ *   extrema[(r - 1) * 2 ..]  int32: min v, max v; a row without voxels keeps INT32_MAX / -1;
+ *   hist[(r - 1) * 256 ..]   int64: the voxels per bin.  hist may be NULL: then no histogram work is done.
+ * The entry point initialises the outputs itself (stream-ordered) and measures in one launch; background voxels take
+ * no atomic, and only integer atomics are used, so the result is exact and the same on every run.  Checked before
+ * anything is launched or written (SK_ERR_ARG): extents, N and max_id not negative; elem_bytes 1 or 2; shift 0 .. 8 and
+ * 0 with elem_bytes 1; with V = 255 or 65535 and m = max(X, Y, Z), X Y Z V max(V, m) < 2^63 (every sum stays inside
+ * int64; formed in 128 bits); then, unless N == 0, no NULL pointer but hist, and pointers aligned to their elements.
+ * An empty volume returns SK_OK with the outputs initialised, N == 0 returns SK_OK and writes nothing.
+ * sk_instance_intensity_row_values(0) = 6, (1) = 2, (2) = 256: the values per row of the three outputs. */
+int sk_instance_intensity_row_values(int which);
+int sk_instance_intensity(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
+                          const void* image, int elem_bytes, int shift, int64_t* moments, int32_t* extrema,
+                          int64_t* hist, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Diagnostics (no reference counterpart; not on the hot path)
  * ------------------------------------------------------------------------ */
 

@@ -32,6 +32,17 @@ meshes of ``lib.instance_meshes`` into one PLY file.
 faces, edges and corners from one kernel pass (``sk_instance_contacts``), per instance its neighbours and
 the share of its surface that lies against them, and ``<mask>_contacts.csv``, one row per pair.
 
+``image=I`` / ``--image I`` adds the other half of the question, the image under every instance: one kernel pass over
+mask and image (``sk_instance_intensity``) gives count, sums, extrema and a 256-bin histogram per instance,
+integers all, and ``intensity_columns`` turns them into ``intensity_mean``, ``intensity_std``, ``intensity_min``,
+``intensity_max``, ``intensity_median``, ``intensity_p05``, ``intensity_p95`` and the intensity-weighted centroid
+``wcx, wcy, wcz``.  The image is 8- or 16-bit; a 16-bit image whose largest sample is 256 or more is binned by
+``v >> shift`` and its three quantiles are then the LOWER EDGE of their bin, ``bin << shift``.
+``intensity_ring=D`` / ``--intensity-ring D`` adds the background within the distance D that is nearer to this instance
+than to any other (``lib.intensity_ring``): ``ring_voxels``, ``ring_mean``, ``ring_std`` and ``contrast`` =
+``(intensity_mean - ring_mean) / (intensity_mean + ring_mean)``.  ``--save-histograms`` writes
+``<mask>_histograms.csv``, the 256 counts of every instance.
+
 ``compare(ground_truth, predictions)`` / ``--ground-truth GT`` matches every ground-truth instance to a predicted one
 by IoU and measures the pair: overlap, volume and centroid differences, and the distances between the two voxel
 surfaces -- Hausdorff, its 95th percentile, average symmetric surface distance, surface Dice -- from an exact
@@ -49,8 +60,10 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .lib import (check_shape, id_rows, instance_contacts, instance_local_thickness, instance_mesh_cells,
-                  instance_mesh_counts, instance_meshes, instance_skeleton_graph, instance_sums, instance_thickness)
+from .lib import (check_shape, id_rows, instance_contacts, instance_intensity, instance_local_thickness,
+                  instance_mesh_cells, instance_mesh_counts, instance_meshes, instance_skeleton_graph, instance_sums,
+                  instance_thickness, nearest_rank)
+from .lib import intensity_ring as _intensity_ring
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
 
 CSV_COLUMNS = ("id,voxels,volume,x0,y0,z0,x1,y1,z1,touches_border,cx,cy,cz,face_area,axis_major,axis_mid,"
@@ -71,6 +84,9 @@ CONTACT_COLUMNS = "neighbours,contact_area,contact_fraction,largest_contact_id,l
 CONTACT_MODES = (None, 6, 18, 26)
 CONTACT_CSV_COLUMNS = ("id_a,id_b,faces_x,faces_y,faces_z,edges_xy,edges_xz,edges_yz,corners,contact_area,fraction_a,"
                        "fraction_b")
+INTENSITY_COLUMNS = ("intensity_mean,intensity_std,intensity_min,intensity_max,intensity_median,intensity_p05,"
+                     "intensity_p95,wcx,wcy,wcz")                                          # appended with --image
+RING_COLUMNS = "ring_voxels,ring_mean,ring_std,contrast"                                  # --intensity-ring
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -364,10 +380,91 @@ def format_contacts_csv(mask_path: str, table, ids, face_area, spacing=(1.0, 1.0
     return "".join(lines)
 
 
+def _int_table(t, width: int) -> np.ndarray:
+    t = t.cpu().numpy() if isinstance(t, Tensor) else np.asarray(t)
+    return t.astype(np.int64).reshape(-1, width)
+
+
+def _mean_std(m: np.ndarray):
+    """(mean, std) float64 of the rows ``n, S v, S v^2, ...``: ``S v / n`` and ``sqrt((n S v^2 - (S v)^2) / n^2)``, the
+    numerator in exact integers; ``nan`` where n is 0"""
+    mean, std = np.full(m.shape[0], np.nan), np.full(m.shape[0], np.nan)
+    for i, (n, sv, svv) in enumerate(m[:, :3].tolist()):
+        if n > 0:
+            mean[i] = sv / n
+            std[i] = float(np.sqrt(np.float64((n * svv - sv * sv) / (n * n))))
+    return mean, std
+
+
+def intensity_columns(moments, extrema, hist, shift: int, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor]:
+    """The intensity columns (host tensors, float64 unless noted) from the tables of ``lib.instance_intensity``:
+    (N, 6) ``n, S v, S v^2, S v x, S v y, S v z``, (N, 2) ``min, max`` and the (N, 256) histogram with bins ``v >> shift``:
+
+    ``intensity_mean`` = ``S v / n``.  ``intensity_std`` = ``sqrt((n S v^2 - (S v)^2) / n^2)``, the population standard
+    deviation, its numerator formed in exact integer arithmetic.  ``intensity_min``, ``intensity_max``, int64.
+    ``intensity_median``, ``intensity_p05``, ``intensity_p95``, int64: the nearest-rank quantile from the histogram, the
+    lowest bin whose cumulative count reaches ``lib.nearest_rank(n, p) + 1``, reported as ``bin << shift``.  At
+    ``shift = 0`` (every 8-bit image) that is ``np.sort(values)[nearest_rank(n, p)]``, one of the samples; at
+    ``shift > 0`` it is the LOWER EDGE of the bin that holds that sample.  ``weighted_centroid`` (N, 3) =
+    ``(S v x, S v y, S v z) / S v * spacing``, ``nan`` where ``S v`` is 0 (an instance on an all-zero image).  A row
+    without voxels has ``nan`` floats and 0 quantiles."""
+    s = np.array(_spacing(spacing), np.float64)
+    m, e, h = _int_table(moments, 6), _int_table(extrema, 2), _int_table(hist, 256)
+    shift = int(shift)
+    if not (m.shape[0] == e.shape[0] == h.shape[0]) or not 0 <= shift <= 8:
+        raise ValueError(f"tables of {m.shape[0]}, {e.shape[0]} and {h.shape[0]} rows, shift {shift}: the rows must agree "
+                         "and the shift lie in 0 .. 8")
+    mean, std = _mean_std(m)
+    cum = np.cumsum(h, axis=1)
+    quant = np.zeros((m.shape[0], 3), np.int64)
+    for i, n in enumerate(m[:, 0].tolist()):
+        if n > 0:
+            for k, p in enumerate((50, 5, 95)):
+                quant[i, k] = int(np.searchsorted(cum[i], nearest_rank(n, p) + 1)) << shift
+    sv = m[:, 1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        centroid = np.where(m[:, 1:2] > 0, m[:, 3:6].astype(np.float64) / sv[:, None], np.nan) * s
+    return {"intensity_mean": torch.from_numpy(mean), "intensity_std": torch.from_numpy(std),
+            "intensity_min": torch.from_numpy(e[:, 0].copy()), "intensity_max": torch.from_numpy(e[:, 1].copy()),
+            "intensity_median": torch.from_numpy(quant[:, 0].copy()), "intensity_p05": torch.from_numpy(quant[:, 1].copy()),
+            "intensity_p95": torch.from_numpy(quant[:, 2].copy()), "weighted_centroid": torch.from_numpy(centroid)}
+
+
+def ring_columns(ring_moments, moments) -> Dict[str, Tensor]:
+    """The ring columns (host tensors) from the (N, 6) moments of ``lib.intensity_ring`` and those of the instances
+    themselves: ``ring_voxels`` int64; ``ring_mean`` and ``ring_std`` float64 as ``intensity_mean`` and
+    ``intensity_std``, ``nan`` where the ring is empty; ``contrast`` = ``(intensity_mean - ring_mean) / (intensity_mean +
+    ring_mean)``, in [-1, 1], ``nan`` where the ring is empty or the denominator is 0."""
+    r, m = _int_table(ring_moments, 6), _int_table(moments, 6)
+    if r.shape[0] != m.shape[0]:
+        raise ValueError(f"{r.shape[0]} ring rows for {m.shape[0]} instances")
+    ring_mean, ring_std = _mean_std(r)
+    mean = _mean_std(m)[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        contrast = np.where(mean + ring_mean != 0, (mean - ring_mean) / (mean + ring_mean), np.nan)
+    return {"ring_voxels": torch.from_numpy(r[:, 0].copy()), "ring_mean": torch.from_numpy(ring_mean),
+            "ring_std": torch.from_numpy(ring_std), "contrast": torch.from_numpy(contrast)}
+
+
+def format_histograms_csv(mask_path: str, ids, hist, shift: int) -> str:
+    """The text of ``_histograms.csv``: two header lines (the file; ``Bin width: 2^shift``), ``id,b0,...,b255`` and one
+    row per instance: the voxels whose sample v has ``v >> shift`` equal to the bin.  A pure function of its arguments."""
+    ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
+    h = _int_table(hist, 256)
+    if h.shape[0] != len(ids):
+        raise ValueError(f"{h.shape[0]} histograms for {len(ids)} ids")
+    lines = [f"Mask File: {mask_path}\n", f"Bin width: 2^{int(shift)}\n",
+             "id," + ",".join(f"b{k}" for k in range(256)) + "\n"]
+    for u, row in zip(ids, h.tolist()):
+        lines.append(",".join(str(v) for v in (int(u), *row)) + "\n")
+    return "".join(lines)
+
+
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
                        skeleton: bool = False, thickness: Optional[str] = None,
                        mesh: Optional[str] = None, pieces: Optional[int] = None,
-                       local_thickness: Optional[str] = None, contacts: Optional[int] = None) -> Dict[str, Tensor]:
+                       local_thickness: Optional[str] = None, contacts: Optional[int] = None,
+                       image: Optional[Tensor] = None, intensity_ring=None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -414,7 +511,18 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     ``contacts=6``, ``18`` or ``26`` adds ``contact_table`` (P, 9) int64 -- one row ``id_a, id_b, c0 .. c6`` per pair of
     instances that touch at that connectivity, ``id_a < id_b``, sorted, from ``lib.instance_contacts`` -- and the
     columns of ``contact_columns``: ``neighbours``, ``contact_area``, ``contact_fraction``, ``largest_contact_id``,
-    ``largest_contact_area``."""
+    ``largest_contact_area``.
+
+    ``image`` (a uint8 or uint16 tensor of the mask's shape on its device; ``lib.instance_intensity`` says what else is
+    taken) adds ``intensity_moments`` (N, 6) int64, ``intensity_extrema`` (N, 2) int32, ``intensity_hist`` (N, 256) int64,
+    ``intensity_shift`` (a Python int) and the columns of ``intensity_columns``: ``intensity_mean``, ``intensity_std``,
+    ``intensity_min``, ``intensity_max``, ``intensity_median``, ``intensity_p05``, ``intensity_p95``,
+    ``weighted_centroid``.  ``intensity_ring=D`` with it adds ``ring_moments`` (N, 6) int64, the image
+    over the background within D (in the units of ``anisotropy``) that is nearest to this instance
+    (``lib.intensity_ring``), and the columns of ``ring_columns``: ``ring_voxels``, ``ring_mean``, ``ring_std``,
+    ``contrast``.  ``intensity_ring`` without ``image`` raises ``ValueError``."""
+    if intensity_ring is not None and image is None:
+        raise ValueError("intensity_ring measures the image around every instance: it needs image")
     if contacts not in CONTACT_MODES or isinstance(contacts, bool):
         raise ValueError(f"contacts must be one of {CONTACT_MODES}, got {contacts!r}")
     if local_thickness not in THICKNESS_MODES:
@@ -467,6 +575,14 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         table = torch.cat((ids[table[:, :2] - 1], table[:, 2:]), 1)      # rows 1..N -> ids; no background rows here
         out["contact_table"] = table
         out.update({k: v.to(sums.device) for k, v in contact_columns(table, ids, out["face_area"], spacing).items()})
+    if image is not None:
+        _, moments, extrema, hist, shift = instance_intensity(x, image, rows)
+        out.update(intensity_moments=moments, intensity_extrema=extrema, intensity_hist=hist, intensity_shift=shift)
+        out.update({k: v.to(sums.device) for k, v in intensity_columns(moments, extrema, hist, shift, spacing).items()})
+        if intensity_ring is not None:
+            ring = _intensity_ring(x, image, intensity_ring, spacing, rows)[0]
+            out["ring_moments"] = ring
+            out.update({k: v.to(sums.device) for k, v in ring_columns(ring, moments).items()})
     return out
 
 
@@ -601,7 +717,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
                mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None,
-               contact_table=None) -> str:
+               contact_table=None, intensity=None, ring=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -617,7 +733,13 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     ``thickness_table`` (the (K, 3) table of ``instance_local_thickness``) ``local_radius_mean,local_radius_std,
     local_radius_min`` follow behind all of that, under the same rule.  With ``contact_table`` (the (P, 9) table of
     ``stats_per_instance(contacts=...)``, ids in its first two columns) ``neighbours,contact_area,contact_fraction,
-    largest_contact_id,largest_contact_area`` follow last, under the same rule again."""
+    largest_contact_id,largest_contact_area`` follow behind those, under the same rule again.  With ``intensity`` (the
+    ``(moments, extrema, hist, shift)`` of ``instance_intensity``) ``intensity_mean,intensity_std,intensity_min,
+    intensity_max,intensity_median,intensity_p05,intensity_p95,wcx,wcy,wcz`` follow, and with ``ring`` (the (N, 6) moments
+    of ``intensity_ring``; it needs ``intensity``) ``ring_voxels,ring_mean,ring_std,contrast`` last, under the same rule
+    once more: floats with ``repr`` (``nan`` prints as ``nan``), integers as integers."""
+    if ring is not None and intensity is None:
+        raise ValueError("ring comes with intensity: the contrast needs both")
     spacing = _spacing(spacing)
     d = derive(sums.cpu(), boxes.cpu(), shape, spacing)
     if mesh_cells is not None:
@@ -639,6 +761,10 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         d.update(local_thickness_columns(thickness_table, len(ids)))
     if contact_table is not None:
         d.update(contact_columns(contact_table, ids, d["face_area"], spacing))
+    if intensity is not None:
+        d.update(intensity_columns(*intensity, spacing))
+    if ring is not None:
+        d.update(ring_columns(ring, intensity[0]))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
@@ -647,7 +773,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + SKELETON_RADIUS_COLUMNS if skeleton_radius is not None else "") +
              "".join("," + k for k in mesh_names) + ("," + PIECES_COLUMNS if piece_table is not None else "") +
              ("," + LOCAL_THICKNESS_COLUMNS if thickness_table is not None else "") +
-             ("," + CONTACT_COLUMNS if contact_table is not None else "") + "\n"]
+             ("," + CONTACT_COLUMNS if contact_table is not None else "") +
+             ("," + INTENSITY_COLUMNS if intensity is not None else "") +
+             ("," + RING_COLUMNS if ring is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -671,6 +799,11 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         if contact_table is not None:
             cells += [d["neighbours"][i], repr(d["contact_area"][i]), repr(d["contact_fraction"][i]),
                       d["largest_contact_id"][i], repr(d["largest_contact_area"][i])]
+        if intensity is not None:
+            cells += [repr(d["intensity_mean"][i]), repr(d["intensity_std"][i]),
+                      *(d[k][i] for k in INTENSITY_COLUMNS.split(",")[2:7]), *(repr(v) for v in d["weighted_centroid"][i])]
+        if ring is not None:
+            cells += [d["ring_voxels"][i], repr(d["ring_mean"][i]), repr(d["ring_std"][i]), repr(d["contrast"][i])]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -730,6 +863,17 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                         help="Append " + CONTACT_COLUMNS + ": the instances every id touches at this connectivity and the "
                              "area of the voxel faces it shares with them; also write <mask>_contacts.csv, one row per "
                              "touching pair: " + CONTACT_CSV_COLUMNS)
+    parser.add_argument("--image", type=str, default=None, metavar="I",
+                        help="Append " + INTENSITY_COLUMNS + ": the image under every instance, from I (.tif or .npy, 8- "
+                             "or 16-bit, stored [Z, X, Y] like the mask): mean, population standard deviation, extrema, "
+                             "nearest-rank quantiles from a 256-bin histogram (the lower edge of the bin when a 16-bit "
+                             "image needs bins wider than 1) and the intensity-weighted centroid")
+    parser.add_argument("--intensity-ring", type=float, default=None, metavar="D",
+                        help="With --image: append " + RING_COLUMNS + ": the image over the background within D (in the "
+                             "units of --spacing) that is nearer to this instance than to any other, and the contrast "
+                             "(intensity_mean - ring_mean) / (intensity_mean + ring_mean)")
+    parser.add_argument("--save-histograms", action="store_true",
+                        help="With --image: also write <mask>_histograms.csv, the 256 histogram counts of every instance")
     parser.add_argument("--ground-truth", type=str, default=None, metavar="GT",
                         help="Also write <mask>_compare.csv: the mask is a prediction and GT (.tif or .npy of the same "
                              "shape) the ground truth; one row per ground-truth instance with the predicted instance it "
@@ -757,7 +901,24 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         parser.error("--iou-threshold and --tolerance belong to --ground-truth")
     if args.iou_threshold is None:
         args.iou_threshold = 0.1
+    if args.image is None and (args.intensity_ring is not None or args.save_histograms):
+        parser.error("--intensity-ring and --save-histograms belong to --image")
+    if args.intensity_ring is not None and not (0.0 < args.intensity_ring < float("inf")):
+        parser.error("--intensity-ring takes a positive finite distance")
     return args
+
+
+def load_image(path: str, mask_path: str, mask_shape) -> Tensor:
+    """(X, Y, Z) uint8 or uint16 host tensor from a .tif or .npy stored [Z, X, Y] like the mask, its dtype kept; any
+    other dtype, or a shape that is not the mask's (X, Y, Z), is an error that names both files."""
+    from ..lib.tiff import read_image
+    image = read_image(path)
+    want = tuple(int(v) for v in mask_shape[-3:])
+    if image.dtype not in (np.uint8, np.uint16) or image.ndim != 3 or (image.shape[1], image.shape[2],
+                                                                         image.shape[0]) != want:
+        raise ValueError(f"{path} holds {image.dtype} samples of shape {tuple(image.shape)} [Z, X, Y(, C)] and {mask_path} "
+                         f"has (X, Y, Z) = {want}: --image takes one 8- or 16-bit sample per voxel of the mask")
+    return torch.from_numpy(np.ascontiguousarray(image.transpose(1, 2, 0)))
 
 
 def main(argv: Optional[Sequence[str]] = None) -> str:
@@ -802,9 +963,17 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
     if args.contacts:
         contact_table = instance_contacts(dev_mask, args.contacts, False, rows)[1]
         contact_table = torch.cat((ids[contact_table[:, :2] - 1], contact_table[:, 2:]), 1)      # rows 1..N -> ids
+    intensity = ring = None
+    if args.image:
+        if not os.path.exists(args.image):
+            raise RuntimeError(f"{args.image} does not exist")
+        dev_image = load_image(args.image, args.mask, mask.shape).to("cuda")
+        intensity = instance_intensity(dev_mask, dev_image, rows)[1:]
+        if args.intensity_ring is not None:
+            ring = _intensity_ring(dev_mask, dev_image, args.intensity_ring, spacing, rows)[0]
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
                       max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table,
-                      contact_table)
+                      contact_table, intensity, ring)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
@@ -815,6 +984,11 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         with open(contacts_path, "w") as file:
             file.write(format_contacts_csv(args.mask, contact_table, ids, face_area, spacing, args.contacts))
         print(f"File Written: {contacts_path}")
+    if args.save_histograms:
+        hist_path = f"{os.path.splitext(args.mask)[0]}_histograms.csv"
+        with open(hist_path, "w") as file:
+            file.write(format_histograms_csv(args.mask, ids, intensity[2], intensity[3]))
+        print(f"File Written: {hist_path}")
     if args.save_skeletons:
         from ..lib import tiff
         # rows 1 .. N -> ids, 0 stays 0; (X, Y, Z) -> the mask's [Z, X, Y]

@@ -17,6 +17,8 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 (DESIGN.md §28).
 ``instance_contacts`` says which instances touch and across how many shared faces, edges and corners, one row per pair
 (DESIGN.md §29).
+``instance_intensity`` reads the image under every instance -- count, sums, extrema and a 256-bin histogram -- and
+``intensity_ring`` the image over the background around it.
 ``instance_surfaces``, ``surface_distances``, ``match_instances`` and ``pair_summaries`` are the parts of
 ``validate/compare.py: compare()``: every instance's surface voxels as sorted keys, the exact squared distance from
 every surface voxel of one instance to the surface of another for many pairs at once, the matching rule, and the
@@ -333,6 +335,176 @@ def instance_contacts(x: Tensor, connectivity: int = 6, background: bool = False
     table = out[:stored]
     order = torch.argsort(table[:, 0] * (N + 1) + table[:, 1])     # lo, hi <= N: one int64 key
     return ids, table[order].contiguous()
+
+
+# ---- the image under every instance ----
+
+N_MOMENTS, N_EXTREMA, N_BINS = 6, 2, 256       # values per instance of sk_instance_intensity (checked against the library)
+_SIGNED_IMAGE_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _volume_shape(x):
+    """(X, Y, Z) of a tensor given as (X, Y, Z) or (1, X, Y, Z), or None when it is neither"""
+    if not isinstance(x, Tensor):
+        return None
+    s = tuple(int(v) for v in x.shape)
+    s = s[1:] if len(s) == 4 and s[0] == 1 else s
+    return s if len(s) == 3 else None
+
+
+def check_image(image, shape) -> None:
+    """What an image must be to be measured under a mask of ``shape`` (X, Y, Z), checked on the tensor's description
+    alone, before any device is touched: a tensor of dtype uint8 or uint16, or of a signed integer dtype (its values
+    are checked later), of shape (X, Y, Z) or (1, X, Y, Z).  Floating, bool and complex images raise ``TypeError``: the
+    measurement is exact integer work, and that is the contract."""
+    if not isinstance(image, Tensor):
+        raise TypeError(f"image must be a tensor, got {type(image).__name__}")
+    if image.dtype not in (torch.uint8, getattr(torch, "uint16", torch.uint8)) + _SIGNED_IMAGE_DTYPES:
+        raise TypeError(f"image must be uint8 or uint16 (or a signed integer dtype with values in 0 .. 65535), got "
+                        f"{image.dtype}: intensities are measured in exact integer arithmetic")
+    got = _volume_shape(image)
+    if got is None or got != tuple(int(v) for v in shape):
+        raise ValueError(f"image has the shape {tuple(image.shape)}, the mask {tuple(int(v) for v in shape)}: the image "
+                         "must be (X, Y, Z) or (1, X, Y, Z) with the mask's extents")
+
+
+def check_intensity_shape(shape, elem_bytes: int) -> None:
+    """The guard of ``sk_instance_intensity``, applied before any call: with V = 255 or 65535 the largest sample,
+    X Y Z V max(V, X, Y, Z) < 2^63 keeps every sum in int64."""
+    X, Y, Z = (int(v) for v in shape)
+    V = 255 if elem_bytes == 1 else 65535
+    if min(X, Y, Z) < 0 or max(X, Y, Z) > _INT32_MAX or X * Y * Z * V * max(V, X, Y, Z) >= 2 ** 63:
+        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure a {8 * elem_bytes}-bit image under: "
+                         f"X*Y*Z*V*max(V, X, Y, Z) with V = {V} must stay below 2^63, or the sums leave int64")
+
+
+def _as_image(image: Tensor, shape, device):
+    """(samples, elem_bytes, largest sample or None) of a checked image: the (X, Y, Z) contiguous uint8 or uint16 device
+    tensor the kernel reads.  A signed image is checked to lie in 0 .. 65535 and converted (int8 to uint8)."""
+    check_image(image, shape)
+    if image.device != device:
+        raise ValueError(f"image is on {image.device} and the mask on {device}: both must be on one device")
+    img = image[0] if image.ndim == 4 else image
+    top = None
+    if img.dtype in _SIGNED_IMAGE_DTYPES:
+        if img.numel():
+            low, top = int(img.min().item()), int(img.max().item())
+            if low < 0 or top > 65535:
+                raise ValueError(f"image is {img.dtype} with values in {low} .. {top}: only 0 .. 65535 can be measured")
+        img = img.to(torch.uint8 if img.dtype == torch.int8 else torch.uint16)
+    return img.contiguous(), int(img.element_size()), top
+
+
+def _image_shift(img: Tensor, elem_bytes: int, top, shift) -> int:
+    """The histogram's bin shift: 0 for 8-bit samples; for 16-bit samples the caller's, or the smallest one that brings
+    the largest sample below 256 (one pass over the image, through its int16 bit patterns with the sign bit flipped)"""
+    if shift is not None and (isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= 8):
+        raise ValueError(f"shift must be an integer in 0 .. 8, got {shift!r}")
+    if elem_bytes == 1:
+        if shift not in (None, 0):
+            raise ValueError(f"shift must be 0 for an 8-bit image, got {shift}")
+        return 0
+    if shift is not None:
+        return int(shift)
+    if top is None:
+        top = int((img.view(torch.int16) ^ -32768).max().item()) + 32768 if img.numel() else 0
+    return max(int(top).bit_length() - 8, 0)
+
+
+def _check_shift(extrema: Tensor, shift: int) -> None:
+    """A given shift is held against the largest sample the pass itself found under an instance: the kernel books a
+    sample beyond the last bin in the last bin, and quantiles read from that would be wrong without a word"""
+    top = int(extrema[:, 1].max().item()) if extrema.numel() else -1
+    if top >> shift >= N_BINS:
+        raise ValueError(f"shift = {shift} leaves the sample {top} outside the {N_BINS} bins: it needs at least "
+                         f"{max(top.bit_length() - 8, 0)}")
+
+
+def _intensity_launch(a, lut, max_id, N, img, elem_bytes, shift, want_hist):
+    dev = a.device
+    moments = torch.zeros((N, N_MOMENTS), dtype=torch.int64, device=dev)
+    extrema = torch.zeros((N, N_EXTREMA), dtype=torch.int32, device=dev)
+    hist = torch.zeros((N, N_BINS), dtype=torch.int64, device=dev) if want_hist else None
+    X, Y, Z = (int(v) for v in a.shape)
+    _ffi.check(_ffi.lib.sk_instance_intensity(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(img), elem_bytes,
+                                              shift, _ffi.ptr(moments), _ffi.ptr(extrema), _ffi.ptr(hist),
+                                              _ffi.stream_ptr(dev)))
+    return moments, extrema, hist
+
+
+def instance_intensity(x: Tensor, image: Tensor, rows=None, want_hist: bool = True, shift=None):
+    """(ids (N) int64 ascending, moments (N, 6) int64, extrema (N, 2) int32, hist (N, 256) int64 or None, shift) of the
+    positive ids of an (X, Y, Z) integer device tensor and an image of the same shape on the same device: the image
+    under every instance from one ``sk_instance_intensity`` launch (include/skoots_hip.h names the columns; DESIGN.md
+    §30).  ``moments`` is ``n, S v, S v^2, S v x, S v y, S v z`` with x, y, z the voxel indices, ``extrema`` the smallest
+    and largest sample, ``hist`` the voxels per bin ``v >> shift``.  ``x`` and ``rows`` are ``instance_sums``'.
+
+    ``image`` is uint8 or uint16, (X, Y, Z) or (1, X, Y, Z); a signed integer image whose values all lie in 0 .. 65535
+    is converted; floating, bool and complex images raise ``TypeError`` (``check_image``).  ``shift=None`` is 0 for an
+    8-bit image and the smallest shift with ``image.max() >> shift < 256`` for a 16-bit one, which costs a pass over the
+    image; a given shift that leaves a sample under an instance outside the 256 bins raises ``ValueError`` after the
+    launch.  ``want_hist=False`` skips the histogram work and returns ``None``
+    for it.  An empty mask returns empty tables."""
+    L = _ffi.lib
+    assert [L.sk_instance_intensity_row_values(k) for k in range(3)] == [N_MOMENTS, N_EXTREMA, N_BINS]
+    shape = _volume_shape(rows[0] if rows is not None else x)
+    if shape is not None:
+        check_image(image, shape)                            # before anything touches the device
+    if rows is None:
+        x = _as_volume(x, "x")
+        check_intensity_shape(x.shape, 1 if image.dtype in (torch.uint8, torch.int8) else 2)
+        rows = (x, _id_rows(x))
+    x, rows = rows
+    dev = x.device
+    img, elem_bytes, top = _as_image(image, x.shape, dev)
+    check_intensity_shape(x.shape, elem_bytes)
+    given = shift is not None
+    shift = _image_shift(img, elem_bytes, top, shift)
+    if rows is None:
+        return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_MOMENTS), dtype=torch.int64, device=dev),
+                torch.empty((0, N_EXTREMA), dtype=torch.int32, device=dev),
+                torch.empty((0, N_BINS), dtype=torch.int64, device=dev) if want_hist else None, shift)
+    a, ids, lut, max_id = rows
+    moments, extrema, hist = _intensity_launch(a, lut, max_id, int(ids.numel()), img, elem_bytes, shift, bool(want_hist))
+    if given and want_hist:
+        _check_shift(extrema, shift)
+    return ids, moments, extrema, hist, shift
+
+
+def intensity_ring(x: Tensor, image: Tensor, distance, spacing=(1.0, 1.0, 1.0), rows=None) -> Tuple[Tensor, Tensor]:
+    """(moments (N, 6) int64, extrema (N, 2) int32) of the image over the RING of every instance: the voxels with a mask
+    value <= 0 whose nearest instance it is, as ``lib.morphology.nearest_label(x, spacing, max_distance=distance)``
+    decides it, its tie rule included.  The same kernel as ``instance_intensity`` measures the ring
+    volume, without a histogram.  The rows are those of the mask's N instances; an instance with an empty ring has
+    ``n = 0`` (and the extrema ``INT32_MAX`` / -1).  ``distance`` is a positive finite number in the units of
+    ``spacing``; ``rows`` is ``id_rows(x)`` when the caller already has it."""
+    from ..lib.morphology import nearest_label
+    try:
+        d = float(distance)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if isinstance(distance, bool) or not (0.0 < d < float("inf")):
+        raise ValueError(f"distance must be a positive finite number, got {distance!r}")
+    shape = _volume_shape(rows[0] if rows is not None else x)
+    if shape is not None:
+        check_image(image, shape)
+    x, rows = id_rows(x) if rows is None else rows
+    dev = x.device
+    img, elem_bytes, _ = _as_image(image, x.shape, dev)
+    check_intensity_shape(x.shape, elem_bytes)
+    if rows is None:
+        return (torch.empty((0, N_MOMENTS), dtype=torch.int64, device=dev),
+                torch.empty((0, N_EXTREMA), dtype=torch.int32, device=dev))
+    ids = rows[1]
+    N = int(ids.numel())
+    nearest = nearest_label(x, spacing, d, None, (x, rows))[0]
+    ring = torch.where(x > 0, torch.zeros_like(nearest), nearest)
+    del nearest
+    # ids -> rows 1 .. N (every non-zero value of the ring is one of ids), 0 stays 0
+    ring = torch.where(ring > 0, torch.searchsorted(ids, ring) + 1, torch.zeros_like(ring)).to(torch.int32).contiguous()
+    lut = torch.arange(N + 1, dtype=torch.int32, device=dev)
+    moments, extrema, _ = _intensity_launch(ring, lut, N, N, img, elem_bytes, 0, False)
+    return moments, extrema
 
 
 MESH_BUDGET = 4 << 30          # bytes of vertex and triangle records instance_meshes may ask for

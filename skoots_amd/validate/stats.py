@@ -19,6 +19,9 @@ path of ``compare.stats_per_instance(thickness=...)``.
 
 ``get_local_thickness`` is the mask's local-thickness map, the radius of the largest ball inside the mask that holds the
 voxel, on the path of ``compare.stats_per_instance(local_thickness=...)``.
+
+``get_intensity`` is the mean of an image under every instance of a mask, on the path of
+``compare.stats_per_instance(image=...)``.
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ import torch
 from torch import Tensor
 
 from .compare import _spacing, mesh_area, skeleton_columns, thickness_columns
-from .lib import (instance_local_thickness, instance_mesh_cells, instance_meshes, instance_skeleton_graph, instance_sums,
+from .lib import (instance_intensity, instance_local_thickness, instance_mesh_cells, instance_meshes, instance_skeleton_graph, instance_sums,
                   instance_thickness)
 
 
@@ -122,3 +125,16 @@ def get_local_thickness(x: Tensor, spacing: Union[List[float], Tensor], closed: 
     if not isinstance(x, Tensor) or not x.is_cuda:
         raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
     return torch.sqrt(instance_local_thickness((x > 0).to(torch.int32), _spacing(spacing), closed)[2])
+
+
+def get_intensity(x: Tensor, image: Tensor) -> Tensor:
+    """The mean of ``image`` under every instance of the (X, Y, Z) mask ``x``: (N) float64 on x's device, one value per
+    positive id in ascending order -- one value for a binary mask -- ``S v / n`` of exact integer sums
+    (``compare.intensity_columns``).  ``image`` is uint8 or uint16 of the mask's shape on its device
+    (``lib.instance_intensity``); the histogram is not computed.  A mask without foreground gives an empty tensor."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    _, moments, _, _, _ = instance_intensity(x, image, want_hist=False)
+    n = moments[:, 0].cpu().tolist()
+    sv = moments[:, 1].cpu().tolist()
+    return torch.tensor([b / a for a, b in zip(n, sv)], dtype=torch.float64).to(x.device)
