@@ -21,7 +21,7 @@
 //     writes nothing else.  A run whose key finds no LDS slot goes to the global table directly.
 //   * A second kernel compacts the used slots into rows.  Integer atomics only, no loop without a bound, no workgroup
 //     waits for another: the counts are exact and the set of rows is the same on every run.
-#include "common.h"
+#include "instance_rows.h"
 
 namespace {
 
@@ -140,17 +140,8 @@ __global__ void __launch_bounds__(kThreads) contacts_kernel(const int* __restric
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int z0 = (int)(tile % tiles_z) * kTZ, y0 = (int)(tile / tiles_z % tiles_y) * kTY;
         const int x0 = (int)(tile / ((long long)tiles_z * tiles_y)) * kTX;
-        for (int i = tid; i < kStaged; i += kThreads) {    // the previous tile's s_row is read before its flush barrier
-            const int wz = i % kWZ, wy = i / kWZ % kWY, wx = i / (kWZ * kWY);
-            const int gx = x0 + wx, gy = y0 + wy, gz = z0 + wz;
-            int r = -1;
-            if (gx < X && gy < Y && gz < Z) {
-                const int v = lab[((long long)gx * Y + gy) * Z + gz];
-                r = (v > 0 && v <= max_id) ? lut[v] : 0;
-                r = (r >= 1 && r <= N) ? r : 0;            // a row outside 1..N is background
-            }
-            s_row[i] = r;
-        }
+        // the previous tile's s_row is read before its flush barrier
+        sk::stage_rows<kWX, kWY, kWZ, kThreads, false>(s_row, lab, lut, max_id, N, sk::Extents{X, Y, Z, 0}, x0, y0, z0, tid);
         __syncthreads();
 
         for (int r = wave; r < kTX * kTY; r += kThreads / 64) {   // wave-uniform: every lane reaches the ballots
@@ -244,10 +235,9 @@ size_t sk_instance_contacts_workspace_bytes(int64_t capacity) {
 int sk_instance_contacts(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
                          int connectivity, int background, int64_t* rows, int64_t capacity, int64_t* counts,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "sk_instance_contacts: extents %d x %d x %d must not be negative", X, Y, Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "sk_instance_contacts: N = %d, max_id = %d must not be negative", N, max_id);
-    SK_CHECK_ARG((unsigned __int128)X * Y * Z < ((unsigned __int128)1 << 62),
-                 "sk_instance_contacts: extents %d x %d x %d: X Y Z must stay below 2^62", X, Y, Z);
+    const char* who = "sk_instance_contacts";
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 62);
+    if (rc != SK_OK) return rc;
     SK_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26,
                  "sk_instance_contacts: connectivity %d must be 6, 18 or 26", connectivity);
     SK_CHECK_ARG(background == 0 || background == 1, "sk_instance_contacts: background %d must be 0 or 1", background);
@@ -256,14 +246,12 @@ int sk_instance_contacts(const int32_t* labels, int X, int Y, int Z, const int32
     SK_CHECK_ARG(workspace_bytes >= sk_instance_contacts_workspace_bytes(capacity),
                  "sk_instance_contacts: workspace too small (%zu < %zu)", workspace_bytes,
                  sk_instance_contacts_workspace_bytes(capacity));
-    SK_CHECK_ARG(rows && counts && workspace, "sk_instance_contacts: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)rows & 7) == 0 && ((uintptr_t)counts & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
-                 "sk_instance_contacts: a pointer is not aligned to its elements");
-    const bool empty = (long long)X * Y * Z == 0 || N == 0;
+    rc = sk::check_pointers(who, {{rows, 8}, {counts, 8}, {workspace, 8}});   // the outputs are written in an empty call too
+    if (rc != SK_OK) return rc;
+    const bool empty = sk::mask_empty(X, Y, Z, N);
     if (!empty) {
-        SK_CHECK_ARG(labels && lut, "sk_instance_contacts: NULL pointer");
-        SK_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0,
-                     "sk_instance_contacts: a pointer is not aligned to its elements");
+        rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}});
+        if (rc != SK_OK) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
@@ -271,19 +259,15 @@ int sk_instance_contacts(const int32_t* labels, int X, int Y, int Z, const int32
     SK_CHECK_HIP(hipMemsetAsync(workspace, 0, sk_instance_contacts_workspace_bytes(capacity), st));
     u64* keys = (u64*)workspace;
     u64* hits = keys + capacity;
-    const int tiles_x = (X + kTX - 1) / kTX, tiles_y = (Y + kTY - 1) / kTY, tiles_z = (Z + kTZ - 1) / kTZ;
-    const long long ntiles = (long long)tiles_x * tiles_y * tiles_z;
-    const unsigned grid = (unsigned)(ntiles < 256 * 8 ? ntiles : 256 * 8);
+    const sk::TileGrid tg = sk::tile_grid(X, Y, Z, kTX, kTY, kTZ);
     const int floor = background ? 0 : 1;
-    if (connectivity == 6)
-        contacts_kernel<6><<<grid, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, floor, ntiles, tiles_y, tiles_z, keys,
-                                                      hits, capacity, (u64*)counts);
-    else if (connectivity == 18)
-        contacts_kernel<18><<<grid, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, floor, ntiles, tiles_y, tiles_z, keys,
-                                                       hits, capacity, (u64*)counts);
-    else
-        contacts_kernel<26><<<grid, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, floor, ntiles, tiles_y, tiles_z, keys,
-                                                       hits, capacity, (u64*)counts);
+#define SK_CONTACTS_LAUNCH(C)                                                                                              \
+    contacts_kernel<C><<<tg.blocks, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, floor, tg.ntiles, tg.tiles_y,     \
+                                                       tg.tiles_z, keys, hits, capacity, (u64*)counts)
+    if (connectivity == 6) SK_CONTACTS_LAUNCH(6);
+    else if (connectivity == 18) SK_CONTACTS_LAUNCH(18);
+    else SK_CONTACTS_LAUNCH(26);
+#undef SK_CONTACTS_LAUNCH
     SK_CHECK_LAUNCH();
     contacts_compact_kernel<<<sk::stream_grid(capacity, kThreads), kThreads, 0, st>>>(keys, hits, capacity,
                                                                                       (long long*)rows, (u64*)counts);

@@ -21,18 +21,13 @@
 //     pattern (non-negative doubles order like unsigned integers, +inf last): the lanes of a wave that hold one row
 //     reduce by shuffles first, and the atomic is skipped where a plain load already shows a value as large -- the
 //     value only grows.
-#include "common.h"
+#include "instance_rows.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 
 typedef unsigned long long u64;
-
-__device__ inline int edt_row(int v, const int* __restrict__ lut, int max_id, int N) {
-    int r = (v > 0 && v <= max_id) ? lut[v] : 0;
-    return (r >= 1 && r <= N) ? r : 0;                     // a row outside the outputs is background
-}
 
 // The walk of voxel p (coordinate c along the pass's axis of extent E and element stride S), whose id is vp and row rp.
 template <bool kFirst>
@@ -50,7 +45,7 @@ __device__ inline double edt_walk(const int* __restrict__ lab, const int* __rest
             } else {
                 const long long q = p + d * S;
                 const int v = lab[q];
-                if (v == vp || edt_row(v, lut, max_id, N) == rp) {
+                if (v == vp || sk::row_of(v, lut, max_id, N) == rp) {
                     if (!kFirst) best = fmin(best, wd + g[q]);
                 } else {
                     best = wd;
@@ -65,7 +60,7 @@ __device__ inline double edt_walk(const int* __restrict__ lab, const int* __rest
             } else {
                 const long long q = p - d * S;
                 const int v = lab[q];
-                if (v == vp || edt_row(v, lut, max_id, N) == rp) {
+                if (v == vp || sk::row_of(v, lut, max_id, N) == rp) {
                     if (!kFirst) best = fmin(best, wd + g[q]);
                 } else {
                     best = fmin(best, wd);
@@ -92,7 +87,7 @@ __global__ void __launch_bounds__(kThreads) edt_pass_kernel(const int* __restric
         double best = 0.0;
         if (p < total) {
             const int vp = lab[p];
-            rp = edt_row(vp, lut, max_id, N);
+            rp = sk::row_of(vp, lut, max_id, N);
             if (rp > 0) {
                 const int z = (int)(p % Z), y = (int)(p / Z % Y), x = (int)(p / ((long long)Z * Y));
                 const int c = kAxis == 2 ? z : kAxis == 1 ? y : x;
@@ -123,22 +118,17 @@ __global__ void __launch_bounds__(kThreads) edt_pass_kernel(const int* __restric
 int edt_check(const char* who, const void* labels, int X, int Y, int Z, const void* lut, int max_id, int N, double wx,
               double wy, double wz, int closed, const void* a, bool a_is_read, const void* b, const void* row_max,
               bool* empty) {
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "%s: extents %d x %d x %d must not be negative", who, X, Y, Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "%s: N = %d, max_id = %d must not be negative", who, N, max_id);
-    SK_CHECK_ARG(X <= (1 << 26) && Y <= (1 << 26) && Z <= (1 << 26),
-                 "%s: extents %d x %d x %d: every extent must stay at or below 2^26 (d^2 exact in double)", who, X, Y, Z);
-    const unsigned __int128 voxels = (unsigned __int128)X * Y * Z;                                        // below 2^78
-    SK_CHECK_ARG(voxels < ((unsigned __int128)1 << 62), "%s: extents %d x %d x %d: X Y Z must stay below 2^62", who, X,
-                 Y, Z);
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 0);
+    if (rc == SK_OK) rc = sk::check_exact_squares(who, X, Y, Z);
+    if (rc == SK_OK) rc = sk::check_voxels(who, X, Y, Z, 62);
+    if (rc != SK_OK) return rc;
     SK_CHECK_ARG(closed == 0 || closed == 1, "%s: closed = %d must be 0 or 1", who, closed);
-    SK_CHECK_ARG(std::isfinite(wx) && std::isfinite(wy) && std::isfinite(wz) && wx > 0 && wy > 0 && wz > 0,
-                 "%s: the weights %g, %g, %g (squared spacing) must be finite and positive", who, wx, wy, wz);
-    *empty = voxels == 0 || N == 0;
+    rc = sk::check_weights(who, wx, wy, wz);
+    if (rc != SK_OK) return rc;
+    *empty = sk::mask_empty(X, Y, Z, N);
     if (*empty) return SK_OK;
-    SK_CHECK_ARG(labels && lut && (a || !a_is_read) && b, "%s: NULL pointer", who);
-    SK_CHECK_ARG(((uintptr_t)a & 7) == 0 && ((uintptr_t)b & 7) == 0 && ((uintptr_t)row_max & 7) == 0 &&
-                     ((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0,
-                 "%s: a pointer is not aligned to its elements", who);
+    rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}, {a, 8, !a_is_read}, {b, 8}, {row_max, 8, true}});
+    if (rc != SK_OK) return rc;
     SK_CHECK_ARG(a != b, "%s: a pass cannot run in place: source and destination are one buffer", who);
     return SK_OK;
 }

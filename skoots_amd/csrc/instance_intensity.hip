@@ -28,7 +28,7 @@
 // gfx950 build (hipcc -O3, ROCm 7.0), VGPRs / LDS bytes / scratch bytes per kernel:
 //   8-bit  with histogram  80 / 22400 / 0     without  70 /  6016 / 0
 //   16-bit with histogram  80 / 26496 / 0     without  72 / 10112 / 0
-#include "common.h"
+#include "instance_rows.h"
 
 #include <limits.h>
 
@@ -57,18 +57,6 @@ __device__ inline unsigned pk_max_u16(unsigned a, unsigned b) {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
 }
 
-// slot of `row` in the tile's table, or -1 when kProbes probes found neither the row nor a free slot
-__device__ inline int claim_slot(int* s_key, int row) {
-    const unsigned h = ((unsigned)row * 2654435761u) >> (32 - kSlotBits);
-    for (int p = 0; p < kProbes; ++p) {
-        const int s = (int)((h + p) & (kSlots - 1));
-        int k = ((volatile int*)s_key)[s];                 // a key never changes once set within a tile
-        if (k == 0) k = atomicCAS(&s_key[s], 0, row);
-        if (k == 0 || k == row) return s;
-    }
-    return -1;
-}
-
 template <typename T, bool kHist>
 __global__ void __launch_bounds__(kThreads) instance_intensity_kernel(
     const int* __restrict__ lab, int X, int Y, int Z, const int* __restrict__ lut, int max_id, int N, long long ntiles,
@@ -94,13 +82,7 @@ __global__ void __launch_bounds__(kThreads) instance_intensity_kernel(
 #pragma unroll
         for (int k = 0; k < kPerWave; ++k) {
             const int x = x0 + (k >> 2), y = y0 + wave + 4 * (k & 3), z = tz0 + lane;
-            int r = 0;
-            if (x < X && y < Y && z < Z) {
-                const int v = lab[((long long)x * Y + y) * Z + z];
-                r = (v > 0 && v <= max_id) ? lut[v] : 0;
-                r = (r >= 1 && r <= N) ? r : 0;            // a row outside the outputs is background
-            }
-            a[k] = r;
+            a[k] = (x < X && y < Y && z < Z) ? sk::row_of(lab[((long long)x * Y + y) * Z + z], lut, max_id, N) : 0;
         }
         // the previous tile's readers of s_img passed the barrier before its flush
         if (wide) {                                        // rows start on 4-byte boundaries: whole words
@@ -138,7 +120,7 @@ __global__ void __launch_bounds__(kThreads) instance_intensity_kernel(
             const int head = 63 - __builtin_clzll((starts & upto) | 1ull);     // of this lane's run, if it is in one
             const bool last = valid && (lane == 63 || !((cmask >> (lane + 1)) & 1ull));
             int s = -1;
-            if (valid && !cont) s = claim_slot(s_key, av);
+            if (valid && !cont) s = sk::claim_slot<kSlotBits, kProbes>(s_key, av);
             s = __shfl(s, head);                           // the run shares its first lane's slot
             // Segmented inclusive scans.  Bit L of `reach` says that lane L - d lies in lane L's run: cmask at d = 1, and
             // reach & (reach << d) at 2 d.  It is wave-uniform, so the steps end with the longest run of the row.  The
@@ -256,8 +238,9 @@ int sk_instance_intensity_row_values(int which) { return which == 0 ? kMom : whi
 int sk_instance_intensity(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
                           const void* image, int elem_bytes, int shift, int64_t* moments, int32_t* extrema,
                           int64_t* hist, void* stream) {
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "sk_instance_intensity: extents %d x %d x %d must not be negative", X, Y, Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "sk_instance_intensity: N = %d, max_id = %d must not be negative", N, max_id);
+    const char* who = "sk_instance_intensity";
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 0);    // the guard below covers X Y Z itself
+    if (rc != SK_OK) return rc;
     SK_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2, "sk_instance_intensity: elem_bytes = %d must be 1 or 2", elem_bytes);
     SK_CHECK_ARG(shift >= 0 && shift <= 8 && (elem_bytes == 2 || shift == 0),
                  "sk_instance_intensity: shift = %d must lie in 0 .. 8, and be 0 for 1-byte samples", shift);
@@ -273,10 +256,8 @@ int sk_instance_intensity(const int32_t* labels, int X, int Y, int Z, const int3
                  "sk_instance_intensity: an output pointer is not aligned to its elements");
     const bool empty = (long long)X * Y * Z == 0;
     if (!empty) {
-        SK_CHECK_ARG(labels && lut && image, "sk_instance_intensity: NULL pointer");
-        SK_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0 &&
-                         ((uintptr_t)image & (uintptr_t)(elem_bytes - 1)) == 0,
-                     "sk_instance_intensity: a pointer is not aligned to its elements");
+        rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}, {image, (unsigned)elem_bytes}});
+        if (rc != SK_OK) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(moments, 0, (size_t)N * kMom * sizeof(int64_t), st));
@@ -285,15 +266,13 @@ int sk_instance_intensity(const int32_t* labels, int X, int Y, int Z, const int3
         extrema, (long long)N * kExt);
     SK_CHECK_LAUNCH();
     if (empty) return SK_OK;
-    const int tiles_x = (X + kTX - 1) / kTX, tiles_y = (Y + kTY - 1) / kTY, tiles_z = (Z + kTZ - 1) / kTZ;
-    const long long ntiles = (long long)tiles_x * tiles_y * tiles_z;
-    const unsigned grid = (unsigned)(ntiles < 256 * 8 ? ntiles : 256 * 8);
+    const sk::TileGrid tg = sk::tile_grid(X, Y, Z, kTX, kTY, kTZ);
     // whole 32-bit words of image when every z row starts on a 4-byte boundary
     const int wide = ((uintptr_t)image & 3) == 0 && ((long long)Z * elem_bytes) % 4 == 0;
-#define SK_II_LAUNCH(T, H)                                                                                            \
-    instance_intensity_kernel<T, H><<<grid, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, ntiles, tiles_y,      \
-                                                               tiles_z, (const T*)image, wide, shift, (u64*)moments, \
-                                                               extrema, (u64*)hist)
+#define SK_II_LAUNCH(T, H)                                                                                           \
+    instance_intensity_kernel<T, H><<<tg.blocks, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, tg.ntiles,      \
+                                                                    tg.tiles_y, tg.tiles_z, (const T*)image, wide,   \
+                                                                    shift, (u64*)moments, extrema, (u64*)hist)
     if (elem_bytes == 1) {
         if (hist) SK_II_LAUNCH(uint8_t, true);
         else SK_II_LAUNCH(uint8_t, false);

@@ -20,7 +20,7 @@
 //     row (kSlots slots of 32 32-bit counters, open addressing, at most kProbes probes).  The table is flushed once
 //     per tile with 64-bit global atomics; a row that finds no slot adds to global memory directly.
 //   * Integer atomics only: every result is exact and independent of the order of arrival.
-#include "common.h"
+#include "instance_rows.h"
 
 namespace {
 
@@ -36,19 +36,6 @@ static_assert(kTZ == 64, "one lane per z of the tile");
 static_assert(kTX == kThreads / 64, "one wave per x plane of the tile");
 
 typedef unsigned long long u64;
-
-// slot of `row` in the tile's table, or -1 when kProbes probes found neither the row nor a free slot
-// (instance_stats.hip has the same table)
-__device__ inline int claim_slot(int* s_key, int row) {
-    const unsigned h = ((unsigned)row * 2654435761u) >> (32 - kSlotBits);
-    for (int p = 0; p < kProbes; ++p) {
-        const int s = (int)((h + p) & (kSlots - 1));
-        int k = ((volatile int*)s_key)[s];                 // a key never changes once set within a tile
-        if (k == 0) k = atomicCAS(&s_key[s], 0, row);
-        if (k == 0 || k == row) return s;
-    }
-    return -1;
-}
 
 // lo: the first cell of every axis (0 open, -1 closed); ncx, ncy, ncz: cells per axis, all positive
 __global__ void __launch_bounds__(kThreads) instance_mesh_kernel(const int* __restrict__ lab, int X, int Y, int Z,
@@ -67,17 +54,7 @@ __global__ void __launch_bounds__(kThreads) instance_mesh_kernel(const int* __re
         const long long cx = (t / ((long long)tiles_z * tiles_y)) * kTX, cy = (t / tiles_z % tiles_y) * (long long)kTY;
         const long long cz = (t % tiles_z) * (long long)kTZ;           // the tile's first cell, counted from lo
         __syncthreads();                                   // the previous tile's flush has read the table
-        for (int i = tid; i < kStaged; i += kThreads) {
-            const int wz = i % kWZ, wy = i / kWZ % kWY, wx = i / (kWZ * kWY);
-            const long long gx = cx + lo + wx, gy = cy + lo + wy, gz = cz + lo + wz;
-            int r = -1;
-            if (gx >= 0 && gx < X && gy >= 0 && gy < Y && gz >= 0 && gz < Z) {
-                const int v = lab[(gx * Y + gy) * Z + gz];
-                r = (v > 0 && v <= max_id) ? lut[v] : 0;
-                r = (r >= 1 && r <= N) ? r : 0;            // a row outside the outputs is background
-            }
-            s_row[i] = r;
-        }
+        sk::stage_rows<kWX, kWY, kWZ, kThreads, true>(s_row, lab, lut, max_id, N, sk::Extents{X, Y, Z, lo}, cx, cy, cz, tid);
         for (int i = tid; i < kSlots * kClasses; i += kThreads) s_cnt[i] = 0;
         if (tid < kSlots) s_key[tid] = 0;
         __syncthreads();
@@ -117,7 +94,7 @@ __global__ void __launch_bounds__(kThreads) instance_mesh_kernel(const int* __re
                         if ((cfg & (0u - cfg)) != (1u << b)) continue;   // an earlier corner has counted this row
                         const unsigned cls = s_class[cfg];               // cfg != 255: the corners are not all equal
                         if (cls >= (unsigned)n_classes) continue;        // a wrong table cannot leave the row
-                        const int s = claim_slot(s_key, a);
+                        const int s = sk::claim_slot<kSlotBits, kProbes>(s_key, a);
                         if (s >= 0)
                             atomicAdd(&s_cnt[s * kClasses + cls], 1u);
                         else                               // the table is full for this row: global memory directly
@@ -145,30 +122,24 @@ extern "C" {
 
 int sk_instance_mesh_cells(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
                            const uint8_t* class_of, int n_classes, int closed, int64_t* cells, void* stream) {
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "sk_instance_mesh_cells: extents %d x %d x %d must not be negative", X, Y,
-                 Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "sk_instance_mesh_cells: N = %d, max_id = %d must not be negative", N, max_id);
-    const unsigned __int128 voxels = (unsigned __int128)X * Y * Z;                                        // below 2^93
-    SK_CHECK_ARG(voxels < ((unsigned __int128)1 << 62),
-                 "sk_instance_mesh_cells: extents %d x %d x %d: X Y Z must stay below 2^62", X, Y, Z);
+    const char* who = "sk_instance_mesh_cells";
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 62);
+    if (rc != SK_OK) return rc;
     SK_CHECK_ARG(n_classes >= 1 && n_classes <= kClasses, "sk_instance_mesh_cells: n_classes = %d must be in 1..%d",
                  n_classes, kClasses);
     SK_CHECK_ARG(closed == 0 || closed == 1, "sk_instance_mesh_cells: closed = %d must be 0 or 1", closed);
-    if (voxels == 0 || N == 0) return SK_OK;
-    SK_CHECK_ARG(labels && lut && class_of && cells, "sk_instance_mesh_cells: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)cells & 7) == 0 && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0,
-                 "sk_instance_mesh_cells: a pointer is not aligned to its elements");
+    if (sk::mask_empty(X, Y, Z, N)) return SK_OK;
+    rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}, {class_of, 1}, {cells, 8}});
+    if (rc != SK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(cells, 0, (size_t)N * n_classes * sizeof(int64_t), st));
     const int lo = closed ? -1 : 0;
     const long long ncx = (long long)X + (closed ? 1 : -1), ncy = (long long)Y + (closed ? 1 : -1);
     const long long ncz = (long long)Z + (closed ? 1 : -1);
     if (ncx <= 0 || ncy <= 0 || ncz <= 0) return SK_OK;    // open mode, an extent of 1: no cell, the zeros stand
-    const long long tiles_x = (ncx + kTX - 1) / kTX, tiles_y = (ncy + kTY - 1) / kTY, tiles_z = (ncz + kTZ - 1) / kTZ;
-    const long long ntiles = tiles_x * tiles_y * tiles_z;  // at most 2^62 / 4096 + lower-order terms
-    const unsigned grid = (unsigned)(ntiles < 256 * 8 ? ntiles : 256 * 8);
-    instance_mesh_kernel<<<grid, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, class_of, n_classes, lo, ncx, ncy,
-                                                    ncz, ntiles, (int)tiles_y, (int)tiles_z, (u64*)cells);
+    const sk::TileGrid tg = sk::tile_grid(ncx, ncy, ncz, kTX, kTY, kTZ);   // at most 2^62 / 4096 tiles + lower-order terms
+    instance_mesh_kernel<<<tg.blocks, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, class_of, n_classes, lo, ncx,
+                                                         ncy, ncz, tg.ntiles, tg.tiles_y, tg.tiles_z, (u64*)cells);
     SK_CHECK_LAUNCH();
     return SK_OK;
 }

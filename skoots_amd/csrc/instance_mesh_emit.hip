@@ -30,7 +30,7 @@
 //     counters still advance, so the caller learns what was needed.
 //   * Integer atomics only.  Which slot a record lands in depends on the order of arrival; the set of records does
 //     not, and the host sorts them (skoots_amd/validate/lib.py: instance_meshes).
-#include "common.h"
+#include "instance_rows.h"
 
 namespace {
 
@@ -53,35 +53,6 @@ struct Geometry {
     long long ntiles;
     int tiles_y, tiles_z;
 };
-
-// slot of `row` in the tile's table, or -1 when kProbes probes found neither the row nor a free slot
-// (instance_mesh.hip has the same table)
-__device__ inline int claim_slot(int* s_key, int row) {
-    const unsigned h = ((unsigned)row * 2654435761u) >> (32 - kSlotBits);
-    for (int p = 0; p < kProbes; ++p) {
-        const int s = (int)((h + p) & (kSlots - 1));
-        int k = ((volatile int*)s_key)[s];                 // a key never changes once set within a tile
-        if (k == 0) k = atomicCAS(&s_key[s], 0, row);
-        if (k == 0 || k == row) return s;
-    }
-    return -1;
-}
-
-// the rows of the tile's corner voxels (the lut applied; -1 outside the volume), as in instance_mesh.hip
-__device__ inline void stage_rows(int* s_row, const int* __restrict__ lab, const int* __restrict__ lut, int max_id, int N,
-                                  const Geometry& g, long long cx, long long cy, long long cz, int tid) {
-    for (int i = tid; i < kStaged; i += kThreads) {
-        const int wz = i % kWZ, wy = i / kWZ % kWY, wx = i / (kWZ * kWY);
-        const long long gx = cx + g.lo + wx, gy = cy + g.lo + wy, gz = cz + g.lo + wz;
-        int r = -1;
-        if (gx >= 0 && gx < g.X && gy >= 0 && gy < g.Y && gz >= 0 && gz < g.Z) {
-            const int v = lab[(gx * g.Y + gy) * g.Z + gz];
-            r = (v > 0 && v <= max_id) ? lut[v] : 0;
-            r = (r >= 1 && r <= N) ? r : 0;                // a row outside the outputs is background
-        }
-        s_row[i] = r;
-    }
-}
 
 // The records of this thread's column of positions (plane x = wave, z = lane, every y of the tile).
 //   on_vertex(row, iy, axis): the edge that starts at position iy along `axis` is a vertex of `row`
@@ -177,12 +148,12 @@ __global__ void __launch_bounds__(kThreads) instance_mesh_count_kernel(const int
         long long cx, cy, cz;
         tile_origin(g, t, cx, cy, cz);
         __syncthreads();                                   // the previous tile's flush has read the table
-        stage_rows(s_row, lab, lut, max_id, N, g, cx, cy, cz, tid);
+        sk::stage_rows<kWX, kWY, kWZ, kThreads, true>(s_row, lab, lut, max_id, N, g, cx, cy, cz, tid);
         if (tid < kSlots * 2) s_cnt[tid] = 0;
         if (tid < kSlots) s_key[tid] = 0;
         __syncthreads();
         auto add = [&](int row, int which, unsigned n) {
-            const int s = claim_slot(s_key, row);
+            const int s = sk::claim_slot<kSlotBits, kProbes>(s_key, row);
             if (s >= 0)
                 atomicAdd(&s_cnt[s * 2 + which], n);
             else                                           // the table is full for this row: global memory directly
@@ -223,7 +194,7 @@ __global__ void __launch_bounds__(kThreads) instance_mesh_emit_kernel(const int*
         long long cx, cy, cz;
         tile_origin(g, t, cx, cy, cz);
         __syncthreads();                                   // the previous tile has read s_row, s_total and s_first
-        stage_rows(s_row, lab, lut, max_id, N, g, cx, cy, cz, tid);
+        sk::stage_rows<kWX, kWY, kWZ, kThreads, true>(s_row, lab, lut, max_id, N, g, cx, cy, cz, tid);
         if (tid < 2) s_total[tid] = 0;
         __syncthreads();
 
@@ -279,28 +250,23 @@ __global__ void __launch_bounds__(kThreads) instance_mesh_emit_kernel(const int*
 int prepare(const char* who, const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
             const uint64_t* tri_table, int closed, Geometry* g, bool* run) {
     *run = false;
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "%s: extents %d x %d x %d must not be negative", who, X, Y, Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "%s: N = %d, max_id = %d must not be negative", who, N, max_id);
-    const unsigned __int128 voxels = (unsigned __int128)X * Y * Z;                                        // below 2^93
-    SK_CHECK_ARG(voxels < ((unsigned __int128)1 << 62), "%s: extents %d x %d x %d: X Y Z must stay below 2^62", who, X, Y,
-                 Z);
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 62);
+    if (rc != SK_OK) return rc;
     const unsigned __int128 padded = (unsigned __int128)((long long)X + 2) * ((long long)Y + 2) * ((long long)Z + 2);
     SK_CHECK_ARG(padded < ((unsigned __int128)1 << 60),
                  "%s: extents %d x %d x %d: (X + 2) (Y + 2) (Z + 2) must stay below 2^60, or the keys leave int64", who, X,
                  Y, Z);
     SK_CHECK_ARG(closed == 0 || closed == 1, "%s: closed = %d must be 0 or 1", who, closed);
-    if (voxels == 0 || N == 0) return SK_OK;
-    SK_CHECK_ARG(labels && lut && tri_table, "%s: NULL pointer", who);
-    SK_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0 && ((uintptr_t)tri_table & 7) == 0,
-                 "%s: a pointer is not aligned to its elements", who);
+    if (sk::mask_empty(X, Y, Z, N)) return SK_OK;
+    rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}, {tri_table, 8}});
+    if (rc != SK_OK) return rc;
     g->X = X, g->Y = Y, g->Z = Z, g->lo = closed ? -1 : 0;
     g->ncx = (long long)X + (closed ? 1 : -1), g->ncy = (long long)Y + (closed ? 1 : -1);
     g->ncz = (long long)Z + (closed ? 1 : -1);
     if (g->ncx <= 0 || g->ncy <= 0 || g->ncz <= 0) return SK_OK;   // open mode, an extent of 1: no cell, no mesh
     // tiles of POSITIONS: one more per axis than cells
-    const long long tiles_x = (g->ncx + kTX) / kTX, tiles_y = (g->ncy + kTY) / kTY, tiles_z = (g->ncz + kTZ) / kTZ;
-    g->ntiles = tiles_x * tiles_y * tiles_z;
-    g->tiles_y = (int)tiles_y, g->tiles_z = (int)tiles_z;
+    const sk::TileGrid tg = sk::tile_grid(g->ncx + 1, g->ncy + 1, g->ncz + 1, kTX, kTY, kTZ);
+    g->ntiles = tg.ntiles, g->tiles_y = tg.tiles_y, g->tiles_z = tg.tiles_z;
     *run = true;
     return SK_OK;
 }
@@ -313,16 +279,16 @@ int sk_instance_mesh_count(const int32_t* labels, int X, int Y, int Z, const int
                            const uint64_t* tri_table, int closed, int64_t* counts, void* stream) {
     Geometry g;
     bool run;
-    const int rc = prepare("sk_instance_mesh_count", labels, X, Y, Z, lut, max_id, N, tri_table, closed, &g, &run);
+    int rc = prepare("sk_instance_mesh_count", labels, X, Y, Z, lut, max_id, N, tri_table, closed, &g, &run);
     if (rc != SK_OK) return rc;
-    if ((long long)X * Y * Z == 0 || N == 0) return SK_OK;
-    SK_CHECK_ARG(counts, "sk_instance_mesh_count: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)counts & 7) == 0, "sk_instance_mesh_count: a pointer is not aligned to its elements");
+    if (sk::mask_empty(X, Y, Z, N)) return SK_OK;
+    rc = sk::check_pointers("sk_instance_mesh_count", {{counts, 8}});
+    if (rc != SK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)N * 2 * sizeof(int64_t), st));
     if (!run) return SK_OK;
-    const unsigned grid = (unsigned)(g.ntiles < 256 * 8 ? g.ntiles : 256 * 8);
-    instance_mesh_count_kernel<<<grid, kThreads, 0, st>>>(labels, lut, max_id, N, (const u64*)tri_table, g, (u64*)counts);
+    instance_mesh_count_kernel<<<sk::tile_blocks(g.ntiles), kThreads, 0, st>>>(labels, lut, max_id, N,
+                                                                               (const u64*)tri_table, g, (u64*)counts);
     SK_CHECK_LAUNCH();
     return SK_OK;
 }
@@ -332,7 +298,7 @@ int sk_instance_mesh_emit(const int32_t* labels, int X, int Y, int Z, const int3
                           int64_t* triangles, int64_t triangle_capacity, int64_t* produced, void* stream) {
     Geometry g;
     bool run;
-    const int rc = prepare("sk_instance_mesh_emit", labels, X, Y, Z, lut, max_id, N, tri_table, closed, &g, &run);
+    int rc = prepare("sk_instance_mesh_emit", labels, X, Y, Z, lut, max_id, N, tri_table, closed, &g, &run);
     if (rc != SK_OK) return rc;
     SK_CHECK_ARG(vertex_capacity >= 0 && triangle_capacity >= 0,
                  "sk_instance_mesh_emit: capacities %lld, %lld must not be negative", (long long)vertex_capacity,
@@ -340,19 +306,16 @@ int sk_instance_mesh_emit(const int32_t* labels, int X, int Y, int Z, const int3
     SK_CHECK_ARG(vertex_capacity < ((int64_t)1 << 58) && triangle_capacity < ((int64_t)1 << 58),
                  "sk_instance_mesh_emit: capacities %lld, %lld must stay below 2^58", (long long)vertex_capacity,
                  (long long)triangle_capacity);
-    if ((long long)X * Y * Z == 0 || N == 0) return SK_OK;
-    SK_CHECK_ARG(produced && (vertices || vertex_capacity == 0) && (triangles || triangle_capacity == 0),
-                 "sk_instance_mesh_emit: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)produced & 7) == 0 && ((uintptr_t)vertices & 7) == 0 && ((uintptr_t)triangles & 7) == 0,
-                 "sk_instance_mesh_emit: a pointer is not aligned to its elements");
+    if (sk::mask_empty(X, Y, Z, N)) return SK_OK;
+    rc = sk::check_pointers("sk_instance_mesh_emit", {{produced, 8}, {vertices, 8, vertex_capacity == 0},
+                                                      {triangles, 8, triangle_capacity == 0}});
+    if (rc != SK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(produced, 0, 2 * sizeof(int64_t), st));
     if (!run) return SK_OK;
-    const unsigned grid = (unsigned)(g.ntiles < 256 * 8 ? g.ntiles : 256 * 8);
-    instance_mesh_emit_kernel<<<grid, kThreads, 0, st>>>(labels, lut, max_id, N, (const u64*)tri_table, g,
-                                                         (long long*)vertices, (long long)vertex_capacity,
-                                                         (long long*)triangles, (long long)triangle_capacity,
-                                                         (u64*)produced);
+    instance_mesh_emit_kernel<<<sk::tile_blocks(g.ntiles), kThreads, 0, st>>>(
+        labels, lut, max_id, N, (const u64*)tri_table, g, (long long*)vertices, (long long)vertex_capacity,
+        (long long*)triangles, (long long)triangle_capacity, (u64*)produced);
     SK_CHECK_LAUNCH();
     return SK_OK;
 }

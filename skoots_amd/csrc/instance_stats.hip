@@ -16,7 +16,7 @@
 //     at most kProbes probes), with LDS integer atomics.  The table is flushed once per tile with 64-bit global
 //     atomic add and 32-bit atomic min / max.  A run whose row finds no slot adds to global memory directly.
 //   * Integer atomics only: every result is exact and independent of the order of arrival.
-#include "common.h"
+#include "instance_rows.h"
 
 #include <limits.h>
 
@@ -63,18 +63,6 @@ __device__ inline RunSums run_sums(int x, int y, int z0, int L, unsigned faces) 
     return r;
 }
 
-// slot of `row` in the tile's table, or -1 when kProbes probes found neither the row nor a free slot
-__device__ inline int claim_slot(int* s_key, int row) {
-    const unsigned h = ((unsigned)row * 2654435761u) >> (32 - kSlotBits);
-    for (int p = 0; p < kProbes; ++p) {
-        const int s = (int)((h + p) & (kSlots - 1));
-        int k = ((volatile int*)s_key)[s];                 // a key never changes once set within a tile
-        if (k == 0) k = atomicCAS(&s_key[s], 0, row);
-        if (k == 0 || k == row) return s;
-    }
-    return -1;
-}
-
 __global__ void __launch_bounds__(kThreads) instance_stats_kernel(const int* __restrict__ lab, int X, int Y, int Z,
                                                                   const int* __restrict__ lut, int max_id, int N,
                                                                   long long ntiles, int tiles_y, int tiles_z,
@@ -88,17 +76,7 @@ __global__ void __launch_bounds__(kThreads) instance_stats_kernel(const int* __r
         const int z0 = (int)(t % tiles_z) * kTZ, y0 = (int)(t / tiles_z % tiles_y) * kTY;
         const int x0 = (int)(t / ((long long)tiles_z * tiles_y)) * kTX;
         __syncthreads();                                   // the previous tile's flush has read the table
-        for (int i = tid; i < kStaged; i += kThreads) {
-            const int wz = i % kWZ, wy = i / kWZ % kWY, wx = i / (kWZ * kWY);
-            const int gx = x0 + wx - 1, gy = y0 + wy - 1, gz = z0 + wz - 1;
-            int r = -1;
-            if (gx >= 0 && gx < X && gy >= 0 && gy < Y && gz >= 0 && gz < Z) {
-                const int v = lab[((long long)gx * Y + gy) * Z + gz];
-                r = (v > 0 && v <= max_id) ? lut[v] : 0;
-                r = (r >= 1 && r <= N) ? r : 0;            // a row outside the outputs is background
-            }
-            s_row[i] = r;
-        }
+        sk::stage_rows<kWX, kWY, kWZ, kThreads, true, 1>(s_row, lab, lut, max_id, N, sk::Extents{X, Y, Z, 0}, x0, y0, z0, tid);
         for (int i = tid; i < kSlots * kSums; i += kThreads) s_sum[i] = 0;
         for (int i = tid; i < kSlots * kBox; i += kThreads) s_box[i] = (i % kBox) < 3 ? INT_MAX : -1;
         if (tid < kSlots) s_key[tid] = 0;
@@ -130,7 +108,7 @@ __global__ void __launch_bounds__(kThreads) instance_stats_kernel(const int* __r
             if (!valid || cont) continue;
             const int x = x0 + ix, y = y0 + iy, z = z0 + lane;
             const RunSums rs = run_sums(x, y, z, L, scan_end - scan + f);
-            const int s = claim_slot(s_key, a);
+            const int s = sk::claim_slot<kSlotBits, kProbes>(s_key, a);
             if (s >= 0) {
 #pragma unroll
                 for (int k = 0; k < kSums; ++k) atomicAdd(&s_sum[s * kSums + k], rs.v[k]);
@@ -183,27 +161,25 @@ int sk_instance_stats_row_values(int which) { return which == 0 ? kSums : which 
 
 int sk_instance_stats(const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N, int64_t* sums,
                       int32_t* boxes, void* stream) {
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "sk_instance_stats: extents %d x %d x %d must not be negative", X, Y, Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "sk_instance_stats: N = %d, max_id = %d must not be negative", N, max_id);
+    const char* who = "sk_instance_stats";
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 0);    // the guard below covers X Y Z itself
+    if (rc != SK_OK) return rc;
     const int m = X > Y ? (X > Z ? X : Z) : (Y > Z ? Y : Z);
     const unsigned __int128 voxels = (unsigned __int128)X * Y * Z, lim = (unsigned __int128)1 << 63;   // below 2^93
     SK_CHECK_ARG(voxels < lim && voxels * ((unsigned __int128)m * m) < lim,                               // below 2^125
                  "sk_instance_stats: extents %d x %d x %d: X Y Z max(X, Y, Z)^2 must stay below 2^63 (int64 second "
                  "moments)", X, Y, Z);
-    if ((long long)X * Y * Z == 0 || N == 0) return SK_OK;
-    SK_CHECK_ARG(labels && lut && sums && boxes, "sk_instance_stats: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)sums & 7) == 0 && ((uintptr_t)boxes & 3) == 0 && ((uintptr_t)labels & 3) == 0 &&
-                     ((uintptr_t)lut & 3) == 0, "sk_instance_stats: a pointer is not aligned to its elements");
+    if (sk::mask_empty(X, Y, Z, N)) return SK_OK;
+    rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}, {sums, 8}, {boxes, 4}});
+    if (rc != SK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(sums, 0, (size_t)N * kSums * sizeof(int64_t), st));
     instance_stats_init_kernel<<<sk::stream_grid((long long)N * kBox, kThreads), kThreads, 0, st>>>(
         boxes, (long long)N * kBox);
     SK_CHECK_LAUNCH();
-    const int tiles_x = (X + kTX - 1) / kTX, tiles_y = (Y + kTY - 1) / kTY, tiles_z = (Z + kTZ - 1) / kTZ;
-    const long long ntiles = (long long)tiles_x * tiles_y * tiles_z;
-    const unsigned grid = (unsigned)(ntiles < 256 * 8 ? ntiles : 256 * 8);
-    instance_stats_kernel<<<grid, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, ntiles, tiles_y, tiles_z,
-                                                     (u64*)sums, boxes);
+    const sk::TileGrid tg = sk::tile_grid(X, Y, Z, kTX, kTY, kTZ);
+    instance_stats_kernel<<<tg.blocks, kThreads, 0, st>>>(labels, X, Y, Z, lut, max_id, N, tg.ntiles, tg.tiles_y,
+                                                          tg.tiles_z, (u64*)sums, boxes);
     SK_CHECK_LAUNCH();
     return SK_OK;
 }

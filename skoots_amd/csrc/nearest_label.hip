@@ -23,16 +23,11 @@
 //     2 floor(sqrt(limit2 / w)) positions per voxel; with limit2 = +inf it is O(extent) per voxel.
 //   * The x pass, the last one, applies limit2 and `where`; the z and y passes answer every voxel, because other lines
 //     read them.
-#include "common.h"
+#include "instance_rows.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ inline int nl_row(int v, const int* __restrict__ lut, int max_id, int N) {
-    int r = (v > 0 && v <= max_id) ? lut[v] : 0;
-    return (r >= 1 && r <= N) ? r : 0;                     // a row outside the outputs is background
-}
 
 // The walk of voxel p (coordinate c along the pass's axis of extent E and element stride S) from (best, row), its own
 // position's offer.  kFirst: the z pass, where a position offers w d^2 if it is a site and nothing otherwise.
@@ -46,7 +41,7 @@ __device__ inline void nl_walk(const int* __restrict__ lab, const int* __restric
         if (c - d >= 0) {
             const long long q = p - d * S;
             if (kFirst) {
-                const int r = nl_row(lab[q], lut, max_id, N);
+                const int r = sk::row_of(lab[q], lut, max_id, N);
                 if (r > 0) { best = wd; row = r; }         // wd <= best
             } else {
                 const double v = wd + g[q];
@@ -56,7 +51,7 @@ __device__ inline void nl_walk(const int* __restrict__ lab, const int* __restric
         if (c + d < E && wd < best) {
             const long long q = p + d * S;
             if (kFirst) {
-                const int r = nl_row(lab[q], lut, max_id, N);
+                const int r = sk::row_of(lab[q], lut, max_id, N);
                 if (r > 0) { best = wd; row = r; }         // wd < best
             } else {
                 const double v = wd + g[q];
@@ -77,7 +72,7 @@ __global__ void __launch_bounds__(kThreads) nl_pass_kernel(const int* __restrict
                                                            long long total) {
     for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < total;
          p += (long long)gridDim.x * kThreads) {
-        const int rp = nl_row(lab[p], lut, max_id, N);
+        const int rp = sk::row_of(lab[p], lut, max_id, N);
         double best = (double)INFINITY;
         int row = 0;
         if (rp > 0) {                                      // a site: nothing is nearer, and `where` does not apply
@@ -117,26 +112,18 @@ int nl_check(const char* who, const void* labels, int X, int Y, int Z, const voi
              double wy, double wz, double limit2, const void* where, const void* const* d2, const void* const* row,
              int n2, int first_required, bool* empty) {
     (void)where;                                           // bytes: any address is aligned, and NULL means "everywhere"
-    SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "%s: extents %d x %d x %d must not be negative", who, X, Y, Z);
-    SK_CHECK_ARG(N >= 0 && max_id >= 0, "%s: N = %d, max_id = %d must not be negative", who, N, max_id);
-    SK_CHECK_ARG(X <= (1 << 26) && Y <= (1 << 26) && Z <= (1 << 26),
-                 "%s: extents %d x %d x %d: every extent must stay at or below 2^26 (d^2 exact in double)", who, X, Y, Z);
-    const unsigned __int128 voxels = (unsigned __int128)X * Y * Z;                                        // below 2^78
-    SK_CHECK_ARG(voxels < ((unsigned __int128)1 << 62), "%s: extents %d x %d x %d: X Y Z must stay below 2^62", who, X,
-                 Y, Z);
-    SK_CHECK_ARG(std::isfinite(wx) && std::isfinite(wy) && std::isfinite(wz) && wx > 0 && wy > 0 && wz > 0,
-                 "%s: the weights %g, %g, %g (squared spacing) must be finite and positive", who, wx, wy, wz);
+    int rc = sk::check_mask_header(who, X, Y, Z, max_id, N, 0);
+    if (rc == SK_OK) rc = sk::check_exact_squares(who, X, Y, Z);
+    if (rc == SK_OK) rc = sk::check_voxels(who, X, Y, Z, 62);
+    if (rc == SK_OK) rc = sk::check_weights(who, wx, wy, wz);
+    if (rc != SK_OK) return rc;
     SK_CHECK_ARG(limit2 >= 0, "%s: limit2 = %g must be a number and not negative (+inf: no limit)", who, limit2);
-    *empty = voxels == 0;
+    *empty = (long long)X * Y * Z == 0;                    // N = 0 is no empty call here: every voxel is answered +inf
     if (*empty) return SK_OK;
-    SK_CHECK_ARG(labels && lut, "%s: NULL pointer", who);
-    SK_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0, "%s: a pointer is not aligned to its elements",
-                 who);
-    for (int i = 0; i < n2; ++i) {
-        SK_CHECK_ARG((d2[i] && row[i]) || i < first_required, "%s: NULL pointer", who);
-        SK_CHECK_ARG(((uintptr_t)d2[i] & 7) == 0 && ((uintptr_t)row[i] & 3) == 0,
-                     "%s: a pointer is not aligned to its elements", who);
-    }
+    rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}});
+    for (int i = 0; i < n2 && rc == SK_OK; ++i)
+        rc = sk::check_pointers(who, {{d2[i], 8, i < first_required}, {row[i], 4, i < first_required}});
+    if (rc != SK_OK) return rc;
     const void* all[4] = {d2[0], row[0], d2[1], row[1]};
     for (int i = 0; i < 4; ++i)
         for (int j = i + 1; j < 4; ++j)

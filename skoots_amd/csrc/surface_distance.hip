@@ -27,7 +27,7 @@
 //     in, so the best is small before the far tiles are looked at.  A minimum does not depend on the order: the result
 //     is the definition's bits however the search is tiled, ordered or pruned.
 //   * Integer atomics only, every d2 element has one writer, nothing accumulates in floating point.
-#include "common.h"
+#include "instance_rows.h"
 
 #include <limits.h>
 
@@ -70,43 +70,25 @@ __device__ inline void decode(u64 lin, const Vol& g, int& x, int& y, int& z) {
     }
 }
 
-__device__ inline int row_of(int v, const int* __restrict__ lut, int max_id, int N) {
-    int r = (v > 0 && v <= max_id) ? lut[v] : 0;
-    return (r >= 1 && r <= N) ? r : 0;                // a row outside the outputs is background
-}
-
 // the row of voxel v when it is a surface voxel of that row, else 0
 template <bool kSmall>
 __device__ inline int surface_row(const int* __restrict__ lab, const int* __restrict__ lut, int max_id, int N,
                                   const Vol& g, u64 v) {
     const int label = lab[v];
-    const int a = row_of(label, lut, max_id, N);
+    const int a = sk::row_of(label, lut, max_id, N);
     if (a == 0) return 0;
     int x, y, z;
     decode<kSmall>(v, g, x, y, z);
     // a neighbour with the same label has the same row; another label goes through the table
     auto differs = [&](u64 n) {
         const int nl = lab[n];
-        return nl != label && row_of(nl, lut, max_id, N) != a;
+        return nl != label && sk::row_of(nl, lut, max_id, N) != a;
     };
     const u64 sy = (u64)g.Z, sx = g.YZ;
     if (x == 0 || x == g.X - 1 || y == 0 || y == g.Y - 1 || z == 0 || z == g.Z - 1) return a;   // outside is row 0
     if (differs(v - 1) || differs(v + 1) || differs(v - sy) || differs(v + sy) || differs(v - sx) || differs(v + sx))
         return a;
     return 0;
-}
-
-// slot of `row` in the tile's table, or -1 when kProbes probes found neither the row nor a free slot
-// (instance_mesh.hip has the same table)
-__device__ inline int claim_slot(int* s_key, int row) {
-    const unsigned h = ((unsigned)row * 2654435761u) >> (32 - kSlotBits);
-    for (int p = 0; p < kProbes; ++p) {
-        const int s = (int)((h + p) & (kSlots - 1));
-        int k = ((volatile int*)s_key)[s];                 // a key never changes once set within a tile
-        if (k == 0) k = atomicCAS(&s_key[s], 0, row);
-        if (k == 0 || k == row) return s;
-    }
-    return -1;
 }
 
 template <bool kSmall>
@@ -126,7 +108,7 @@ __global__ void __launch_bounds__(kThreads) surface_count_kernel(const int* __re
             if (v >= g.V) break;
             const int a = surface_row<kSmall>(lab, lut, max_id, N, g, v);
             if (a == 0) continue;
-            const int s = claim_slot(s_key, a);
+            const int s = sk::claim_slot<kSlotBits, kProbes>(s_key, a);
             if (s >= 0)
                 atomicAdd(&s_cnt[s], 1u);
             else                                           // the table is full for this row: global memory directly
@@ -269,6 +251,7 @@ __global__ void __launch_bounds__(kThreads) surface_distances_kernel(
 int prepare_surface(const char* who, const int32_t* labels, int X, int Y, int Z, const int32_t* lut, int max_id, int N,
                     Vol* g, long long* ntiles, bool* run) {
     *run = false;
+    // not sk::check_mask_header: the extent limit stands between its two checks here
     SK_CHECK_ARG(X >= 0 && Y >= 0 && Z >= 0, "%s: extents %d x %d x %d must not be negative", who, X, Y, Z);
     SK_CHECK_ARG(X <= kMaxExtent && Y <= kMaxExtent && Z <= kMaxExtent, "%s: extents %d x %d x %d must not exceed 2^26", who,
                  X, Y, Z);
@@ -278,16 +261,13 @@ int prepare_surface(const char* who, const int32_t* labels, int X, int Y, int Z,
                  "%s: N = %d rows of %d x %d x %d voxels: N X Y Z must stay below 2^63, or the keys leave int64", who, N, X,
                  Y, Z);
     if (voxels == 0 || N == 0) return SK_OK;
-    SK_CHECK_ARG(labels && lut, "%s: NULL pointer", who);
-    SK_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)lut & 3) == 0, "%s: a pointer is not aligned to its elements",
-                 who);
+    const int rc = sk::check_pointers(who, {{labels, 4}, {lut, 4}});
+    if (rc != SK_OK) return rc;
     g->X = X, g->Y = Y, g->Z = Z, g->YZ = (u64)Y * Z, g->V = (u64)voxels;
     *ntiles = (long long)((g->V + (u64)(kThreads * kPer) - 1) / (u64)(kThreads * kPer));
     *run = true;
     return SK_OK;
 }
-
-unsigned grid_of(long long n) { return (unsigned)(n < 256 * 8 ? n : 256 * 8); }
 
 bool finite_positive(double w) { return w > 0.0 && w < INFINITY; }
 
@@ -302,14 +282,13 @@ int sk_instance_surface_count(const int32_t* labels, int X, int Y, int Z, const 
     Vol g;
     long long ntiles = 0;
     bool run;
-    const int rc = prepare_surface("sk_instance_surface_count", labels, X, Y, Z, lut, max_id, N, &g, &ntiles, &run);
+    int rc = prepare_surface("sk_instance_surface_count", labels, X, Y, Z, lut, max_id, N, &g, &ntiles, &run);
+    if (rc != SK_OK || !run) return rc;
+    rc = sk::check_pointers("sk_instance_surface_count", {{counts, 8}});
     if (rc != SK_OK) return rc;
-    if (!run) return SK_OK;
-    SK_CHECK_ARG(counts, "sk_instance_surface_count: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)counts & 7) == 0, "sk_instance_surface_count: a pointer is not aligned to its elements");
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)N * sizeof(int64_t), st));
-    const unsigned grid = grid_of(ntiles);
+    const unsigned grid = sk::tile_blocks(ntiles);
     if (g.V < (1ull << 32))
         surface_count_kernel<true><<<grid, kThreads, 0, st>>>(labels, lut, max_id, N, g, ntiles, (u64*)counts);
     else
@@ -323,18 +302,17 @@ int sk_instance_surface_emit(const int32_t* labels, int X, int Y, int Z, const i
     Vol g;
     long long ntiles = 0;
     bool run;
-    const int rc = prepare_surface("sk_instance_surface_emit", labels, X, Y, Z, lut, max_id, N, &g, &ntiles, &run);
+    int rc = prepare_surface("sk_instance_surface_emit", labels, X, Y, Z, lut, max_id, N, &g, &ntiles, &run);
     if (rc != SK_OK) return rc;
     SK_CHECK_ARG(capacity >= 0, "sk_instance_surface_emit: capacity %lld must not be negative", (long long)capacity);
     SK_CHECK_ARG(capacity < ((int64_t)1 << 60), "sk_instance_surface_emit: capacity %lld must stay below 2^60",
                  (long long)capacity);
     if (!run) return SK_OK;
-    SK_CHECK_ARG(produced && (keys || capacity == 0), "sk_instance_surface_emit: NULL pointer");
-    SK_CHECK_ARG(((uintptr_t)produced & 7) == 0 && ((uintptr_t)keys & 7) == 0,
-                 "sk_instance_surface_emit: a pointer is not aligned to its elements");
+    rc = sk::check_pointers("sk_instance_surface_emit", {{produced, 8}, {keys, 8, capacity == 0}});
+    if (rc != SK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     SK_CHECK_HIP(hipMemsetAsync(produced, 0, sizeof(int64_t), st));
-    const unsigned grid = grid_of(ntiles);
+    const unsigned grid = sk::tile_blocks(ntiles);
     if (g.V < (1ull << 32))
         surface_emit_kernel<true><<<grid, kThreads, 0, st>>>(labels, lut, max_id, N, g, ntiles, (long long*)keys,
                                                              (long long)capacity, (u64*)produced);
@@ -405,7 +383,7 @@ int sk_surface_distances(const int64_t* q_keys, const int64_t* q_offsets, int q_
     SK_CHECK_ARG((unsigned __int128)X * Y * Z < ((unsigned __int128)1 << 63), "%s: X Y Z must stay below 2^63", who);
     Vol g;
     g.X = X, g.Y = Y, g.Z = Z, g.YZ = (u64)Y * Z, g.V = (u64)X * g.YZ;
-    const unsigned grid = grid_of((total + kThreads - 1) / kThreads);
+    const unsigned grid = sk::tile_blocks((total + kThreads - 1) / kThreads);
     if (g.V < (1ull << 32))
         surface_distances_kernel<true><<<grid, kThreads, 0, st>>>(
             (const long long*)q_keys, (const long long*)q_offsets, (const long long*)t_keys, (const long long*)t_offsets,

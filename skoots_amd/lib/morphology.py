@@ -137,6 +137,23 @@ def skeleton_graph(labels: Tensor, ids, boxes, want_points: bool = False):
     return graph, counts.cpu().numpy().astype(np.int64), points
 
 
+def squared_spacing(spacing) -> Tuple[float, float, float]:
+    """(wx, wy, wz) = (sx sx, sy sy, sz sz) in float64, the weights of the distance kernels: the spacing must be three
+    positive finite numbers whose squares are positive and finite too."""
+    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
+    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
+        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
+    return s[0] * s[0], s[1] * s[1], s[2] * s[2]
+
+
+def check_transform_shape(shape, what: str) -> None:
+    """The guard of the distance transforms (``what`` names one): d^2 must stay exact in float64."""
+    X, Y, Z = (int(v) for v in shape)
+    if max(X, Y, Z) > 2 ** 26 or X * Y * Z >= 2 ** 62:
+        raise ValueError(f"a volume of shape {(X, Y, Z)} is too large for {what}: every extent must stay at or below "
+                         "2^26 and X*Y*Z below 2^62")
+
+
 def label_edt(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, rows=None) -> Tuple[Tensor, Tensor]:
     """Exact squared Euclidean distance transform of every instance of an (X, Y, Z) or (1, X, Y, Z) integer device
     tensor at the voxel spacing ``spacing`` (sx, sy, sz): ``(dist2, row_max)``, both float64 on the device.
@@ -151,26 +168,16 @@ def label_edt(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, row
     ``closed=False`` is scipy's meaning: only voxels of the volume count, and an id that is the only value of the whole
     volume gets ``inf``.  ``closed=True`` measures the volume padded with one layer of background.  ``rows`` is
     ``validate.lib.id_rows(labels)`` when the caller already has it."""
-    from ..validate.lib import id_rows
-    x, rows = id_rows(labels) if rows is None else rows
-    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
-    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
-        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
-    X, Y, Z = (int(v) for v in x.shape)
-    if max(X, Y, Z) > 2 ** 26 or X * Y * Z >= 2 ** 62:
-        raise ValueError(f"a volume of shape {(X, Y, Z)} is too large for the distance transform: every extent must stay "
-                         "at or below 2^26 and X*Y*Z below 2^62")
-    dev = x.device
-    dist2 = torch.zeros((X, Y, Z), dtype=torch.float64, device=dev)
-    if rows is None or dist2.numel() == 0:
-        return dist2, torch.zeros(0, dtype=torch.float64, device=dev)
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
+    from ..validate.lib import _Rows
+    m = _Rows(labels, rows)
+    w = squared_spacing(spacing)
+    check_transform_shape(m.shape, "the distance transform")
+    dist2 = torch.zeros(m.shape, dtype=torch.float64, device=m.dev)
+    if m.empty or dist2.numel() == 0:
+        return dist2, torch.zeros(0, dtype=torch.float64, device=m.dev)
     scratch = torch.empty_like(dist2)
-    row_max = torch.zeros(N, dtype=torch.int64, device=dev)
-    _ffi.check(_ffi.lib.sk_label_edt(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, s[0] * s[0], s[1] * s[1], s[2] * s[2],
-                                     int(bool(closed)), _ffi.ptr(dist2), _ffi.ptr(scratch), _ffi.ptr(row_max),
-                                     _ffi.stream_ptr(dev)))
+    row_max = torch.zeros(m.N, dtype=torch.int64, device=m.dev)
+    m.call(_ffi.lib.sk_label_edt, *w, int(bool(closed)), _ffi.ptr(dist2), _ffi.ptr(scratch), _ffi.ptr(row_max))
     return dist2, row_max.view(torch.float64)
 
 
@@ -193,17 +200,12 @@ def nearest_label(labels: Tensor, spacing=(1.0, 1.0, 1.0), max_distance=None, wh
     get ``inf`` and 0 unless they hold an id themselves.  It never restricts which voxels count as nearest: distances
     are Euclidean, through anything, not geodesic.  ``rows`` is ``validate.lib.id_rows(labels)`` when the caller
     already has it; sparse or huge ids go through its relabelled volume, and ``nearest_id`` still names the ids."""
-    from ..validate.lib import id_rows
-    x, rows = id_rows(labels) if rows is None else rows
-    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
-    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
-        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
+    from ..validate.lib import _Rows
+    m = _Rows(labels, rows)
+    w = squared_spacing(spacing)
     limit2 = max_distance_squared(max_distance)
-    X, Y, Z = (int(v) for v in x.shape)
-    if max(X, Y, Z) > 2 ** 26 or X * Y * Z >= 2 ** 62:
-        raise ValueError(f"a volume of shape {(X, Y, Z)} is too large for the nearest-instance transform: every extent "
-                         "must stay at or below 2^26 and X*Y*Z below 2^62")
-    dev = x.device
+    check_transform_shape(m.shape, "the nearest-instance transform")
+    dev, ids, (X, Y, Z) = m.dev, m.ids, m.shape
     if where is not None:
         if not isinstance(where, Tensor) or where.device != dev or where.is_floating_point() or where.is_complex():
             raise ValueError("where must be a bool or integer tensor on the device of labels")
@@ -212,15 +214,12 @@ def nearest_label(labels: Tensor, spacing=(1.0, 1.0, 1.0), max_distance=None, wh
             raise ValueError(f"where must have the volume's shape {(X, Y, Z)}, got {tuple(where.shape)}")
         where = (where != 0).to(torch.uint8).contiguous()
     dist2 = torch.full((X, Y, Z), float("inf"), dtype=torch.float64, device=dev)
-    if rows is None or dist2.numel() == 0:
+    if m.empty or dist2.numel() == 0:
         return torch.zeros((X, Y, Z), dtype=torch.int64, device=dev), dist2
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
     nearest = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
     scratch_d2, scratch_row = torch.empty_like(dist2), torch.empty_like(nearest)
-    _ffi.check(_ffi.lib.sk_nearest_label(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, s[0] * s[0], s[1] * s[1],
-                                         s[2] * s[2], limit2, _ffi.ptr(where), _ffi.ptr(dist2), _ffi.ptr(nearest),
-                                         _ffi.ptr(scratch_d2), _ffi.ptr(scratch_row), _ffi.stream_ptr(dev)))
+    m.call(_ffi.lib.sk_nearest_label, *w, limit2, _ffi.ptr(where), _ffi.ptr(dist2), _ffi.ptr(nearest),
+           _ffi.ptr(scratch_d2), _ffi.ptr(scratch_row))
     return torch.cat((ids.new_zeros(1), ids))[nearest.long()], dist2
 
 
@@ -269,22 +268,19 @@ def local_thickness(labels: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = Fals
     more than itself is a centre, and a centre costs its bounding box: a compact object of radius R voxels costs about
     R^6 tests, so the centre list is painted in consecutive launches of at most ``budget`` box voxels each (a centre
     whose own box is larger goes alone).  The result does not depend on ``budget``."""
-    from ..validate.lib import id_rows
+    from ..validate.lib import _Rows
     budget = int(budget)
     if budget < 1:
         raise ValueError(f"budget must be a positive number of box voxels, got {budget}")
     if dist2 is None:
-        x, rows = id_rows(labels) if rows is None else rows
-        dist2, row_max = label_edt(x, spacing, closed, (x, rows))
+        m = _Rows(labels, rows)
+        dist2, row_max = label_edt(m.x, spacing, closed, m.pair)
     else:
         dist2, row_max = dist2
         if not isinstance(dist2, Tensor) or not dist2.is_cuda or dist2.dtype != torch.float64 or dist2.ndim != 3:
             raise ValueError("dist2 must be label_edt's pair (dist2 (X, Y, Z) float64 on the device, row_max)")
         dist2 = dist2.contiguous()
-    s = tuple(float(v) for v in (spacing.detach().cpu().tolist() if isinstance(spacing, Tensor) else spacing))
-    if len(s) != 3 or not all(0 < v < float("inf") for v in s) or not all(0 < v * v < float("inf") for v in s):
-        raise ValueError(f"spacing must be three positive finite numbers (x, y, z), got {spacing}")
-    w = (s[0] * s[0], s[1] * s[1], s[2] * s[2])
+    w = squared_spacing(spacing)
     X, Y, Z = (int(v) for v in dist2.shape)
     thick2 = dist2.clone()
     if thick2.numel() == 0:
@@ -372,28 +368,16 @@ def label_components(labels: Tensor, connectivity: int = 6, background: bool = F
     The numbers are exact and the same on every run.  Negative values raise ``ValueError``; ``X*Y*Z`` must stay below
     2^31.  ``rows`` is ``validate.lib.id_rows(labels)`` when the caller already has it; sparse or huge ids go through its
     relabelled volume, and the ``value`` column still names the ids themselves."""
-    from ..validate.lib import _as_volume, _id_rows
+    from ..validate.lib import _Rows
     if connectivity not in CONNECTIVITIES or isinstance(connectivity, bool):
         raise ValueError(f"connectivity must be one of {CONNECTIVITIES}, got {connectivity!r}")
-    if rows is None:
-        x = _as_volume(labels, "labels")
-        check_piece_shape(x.shape)
-        if x.numel() and int(x.min().item()) < 0:
-            raise ValueError(f"labels holds the negative value {int(x.min().item())}: instance ids are positive and 0 is "
-                             "the background")
-        rows = _id_rows(x)
-    else:
-        x, rows = rows
-        check_piece_shape(x.shape)
-    dev = x.device
-    if rows is None:                                         # no positive id: one call on the zeros themselves
-        a, ids, max_id = torch.zeros(tuple(x.shape), dtype=torch.int32, device=dev), None, 0
-    else:
-        a, ids, _, max_id = rows
+    m = _Rows(labels, rows, check_piece_shape, "labels", nonnegative=True)
+    # no positive id: one call on the zeros themselves
+    a = torch.zeros(m.shape, dtype=torch.int32, device=m.dev) if m.empty else m.a
     piece, table = _label_pieces(a, int(connectivity), 0 if background else 1)
-    if ids is not None and int(ids[-1].item()) != max_id and table.shape[0]:
+    if m.N and int(m.ids[-1].item()) != m.max_id and table.shape[0]:
         # _id_rows relabelled the mask: `a` holds the rows 1..N, and the columns that name ids hold rows
-        back = torch.cat((ids.new_zeros(1), ids))
+        back = torch.cat((m.ids.new_zeros(1), m.ids))
         for col in (0, 4, 5):
             table[:, col] = back[table[:, col]]
     return piece, table

@@ -168,23 +168,19 @@ def clean(mask: Tensor, *, components: str = "keep", connectivity: int = 6, min_
     Ids beyond int32 -- in the mask, or made by ``"split"`` -- raise ``ValueError`` unless ``renumber`` is set.  Every
     step is exact integer work: two runs give identical tensors and reports.  HIP kernels only, no CPU fallback."""
     from ..lib.morphology import CONNECTIVITIES, _label_pieces, check_piece_shape, label_components
-    from ..validate.lib import _as_volume, _id_rows
+    from ..validate.lib import _Rows, _as_volume
     from .renumber import renumber_first_seen
     x = _as_volume(mask, "mask")
     check_piece_shape(x.shape)
     if connectivity not in CONNECTIVITIES or isinstance(connectivity, bool):
         raise ValueError(f"connectivity must be one of {CONNECTIVITIES}, got {connectivity!r}")
     plan_relabel(np.zeros((0, 6), np.int64), 0, components, min_voxels, clear_border)      # the argument checks
-    if x.numel() and int(x.min().item()) < 0:
-        raise ValueError(f"mask holds the negative value {int(x.min().item())}: instance ids are positive and 0 is the "
-                         "background")
-    dev = x.device
-    out = torch.zeros(tuple(x.shape), dtype=torch.int32, device=dev)
-    rows = _id_rows(x)
-    if rows is None:
+    m = _Rows(x, name="mask", nonnegative=True)           # x is a volume already: it passes through
+    out = torch.zeros(m.shape, dtype=torch.int32, device=m.dev)
+    if m.empty:
         return out, CleanReport()
-    piece, table = label_components(x, connectivity, rows=(x, rows))
-    lut, fields = plan_relabel(table, int(rows[1][-1].item()), components, min_voxels, clear_border, renumber)
+    piece, table = label_components(m.x, connectivity, rows=m.pair)
+    lut, fields = plan_relabel(table, int(m.ids[-1].item()), components, min_voxels, clear_border, renumber)
     k = fields["instances_out"]
     if renumber:                                             # ranks among the surviving ids: 1..K, in int32 whatever they were
         uniq = np.unique(lut[lut > 0])

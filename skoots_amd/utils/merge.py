@@ -139,27 +139,23 @@ def merge(mask: Tensor, *, spacing=(1.0, 1.0, 1.0), connectivity: int = 6, min_c
     work on the device and a pure function of a small table on the host: two runs give identical tensors and reports.
     HIP kernels only, no CPU fallback."""
     from ..validate.compare import _spacing, derive
-    from ..validate.lib import _as_volume, _id_rows, check_shape, instance_contacts, instance_sums
+    from ..validate.lib import _Rows, _as_volume, check_shape, instance_contacts, instance_sums
     from .renumber import renumber_first_seen
     x = _as_volume(mask, "mask")
     check_shape(x.shape)
     spacing = _spacing(spacing)
     _request(min_contact_area, min_contact_fraction, pairs)                 # the argument checks
-    if x.numel() and int(x.min().item()) < 0:
-        raise ValueError(f"mask holds the negative value {int(x.min().item())}: instance ids are positive and 0 is the "
-                         "background")
-    dev = x.device
-    rows = _id_rows(x)
-    if rows is None:
+    m = _Rows(x, name="mask", nonnegative=True)           # x is a volume already: it passes through
+    dev, a, ids, lut = m.dev, m.a, m.ids, m.lut
+    if m.empty:
         if len(_pairs(pairs)):                                # ids that are not in the mask: raises
             plan_merge(np.zeros((0, 9), np.int64), np.zeros(0, np.int64), np.zeros(0), spacing, pairs=pairs)
-        return torch.zeros(tuple(x.shape), dtype=torch.int32, device=dev), MergeReport()
-    a, ids, lut, _ = rows
+        return torch.zeros(m.shape, dtype=torch.int32, device=dev), MergeReport()
     top = int(ids[-1].item())
     if top > _INT32_MAX and not renumber:
         raise ValueError(f"the mask holds the id {top}, beyond int32; pass renumber=True to number the result 1..K")
-    _, table = instance_contacts(x, connectivity, False, (x, rows))
-    _, sums, boxes = instance_sums(x, (x, rows))
+    _, table = instance_contacts(x, connectivity, False, m.pair)
+    _, sums, boxes = instance_sums(x, m.pair)
     face_area = derive(sums.cpu(), boxes.cpu(), tuple(x.shape), spacing)["face_area"].numpy()
     ids_h = ids.cpu().numpy()
     t = table.cpu().numpy()

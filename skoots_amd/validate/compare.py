@@ -60,7 +60,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .lib import (check_shape, id_rows, instance_contacts, instance_intensity, instance_local_thickness,
+from .lib import (_Rows, check_shape, id_rows, instance_contacts, instance_intensity, instance_local_thickness,
                   instance_mesh_cells, instance_mesh_counts, instance_meshes, instance_skeleton_graph, instance_sums,
                   instance_thickness, nearest_rank)
 from .lib import intensity_ring as _intensity_ring
@@ -631,7 +631,7 @@ def compare(ground_truth: Tensor, predictions: Tensor, anisotropy=(1.0, 1.0, 1.0
     cen_p = derive(sums_p.cpu(), boxes_p.cpu(), shape, spacing)["centroid"].numpy()
     if N and M:
         # every voxel's row, 1..N / 1..M and 0 for the rest; int32 indices and results: no 8-byte-per-voxel temporary
-        rg, rp = grows[2][grows[0]], prows[2][prows[0]]
+        rg, rp = _Rows(g, (g, grows)).row_volume(), _Rows(p, (p, prows)).row_volume()
         iou = mask_iou(rg, rp)                                          # rows ascend with the ids: the same matrix
     else:
         iou = torch.zeros((N, M), dtype=torch.float32, device=dev)

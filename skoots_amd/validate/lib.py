@@ -221,29 +221,66 @@ def id_rows(x: Tensor):
     return x, _id_rows(x)
 
 
+def check_voxels(shape) -> None:
+    """X Y Z < 2^62: the library's guard where a pass keeps no sums over the voxels."""
+    X, Y, Z = (int(v) for v in shape)
+    if X * Y * Z >= 2 ** 62:
+        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure: X*Y*Z must stay below 2^62")
+
+
+class _Rows:
+    """The prologue of every per-instance function, done once.  ``rows`` is the caller's ``id_rows(x)``; without it ``x``
+    goes through ``_as_volume`` and ``_id_rows``.  ``guard`` is the function's size guard (``check_shape``,
+    ``check_voxels``, ...): it sees the shape before anything touches the device.  ``nonnegative`` refuses a mask with a
+    negative value.  ``x`` is the (X, Y, Z) view, ``shape`` its extents, ``dev`` its device, ``pair`` what to hand on
+    as ``rows=``; ``a``, ``ids``, ``lut``, ``max_id`` are ``_id_rows``' and ``N`` the number of instances.  A mask
+    without a positive id is ``empty``: N = 0, ``ids`` an empty tensor, no ``a`` and no ``lut``."""
+
+    def __init__(self, x, rows=None, guard=None, name: str = "x", nonnegative: bool = False):
+        x = _as_volume(x, name) if rows is None else rows[0]
+        if guard is not None:
+            guard(x.shape)
+        if rows is None:
+            if nonnegative and x.numel() and int(x.min().item()) < 0:
+                raise ValueError(f"{name} holds the negative value {int(x.min().item())}: instance ids are positive and "
+                                 "0 is the background")
+            rows = (x, _id_rows(x))
+        self.x, r = self.pair = rows
+        self.shape = tuple(int(v) for v in x.shape)
+        self.dev = x.device
+        self.empty = r is None
+        if self.empty:
+            r = (None, torch.empty(0, dtype=torch.int64, device=self.dev), None, 0)
+        self.a, self.ids, self.lut, self.max_id = r
+        self.N = int(self.ids.numel())
+
+    def call(self, fn, *args) -> None:
+        """``fn(labels, X, Y, Z, lut, max_id, N, *args, stream)``, checked: the mask header every per-instance entry
+        point of the library begins with, and the stream it ends with."""
+        _ffi.check(fn(_ffi.ptr(self.a), *self.shape, _ffi.ptr(self.lut), self.max_id, self.N, *args,
+                      _ffi.stream_ptr(self.dev)))
+
+    def values(self) -> Tensor:
+        """(N) int64: the value ``a`` holds for row k + 1 -- the id itself, or the row where ``_id_rows`` relabelled."""
+        return torch.nonzero(self.lut)[:, 0]
+
+    def row_volume(self) -> Tensor:
+        """(X, Y, Z) int32: every voxel's row 1..N, 0 for the background and for negative values; int32 indices and
+        results, so no 8-byte-per-voxel temporary."""
+        return self.lut[self.a.clamp(min=0)]
+
+
 def instance_sums(x: Tensor, rows=None) -> Tuple[Tensor, Tensor, Tensor]:
     """(ids (N) int64 ascending, sums (N, 13) int64, boxes (N, 6) int32) of the positive ids of an (X, Y, Z) integer
     device tensor: one ``sk_instance_stats`` launch for every instance (include/skoots_hip.h names the columns).
     ``_id_rows`` says how the ids reach the kernel; ``rows`` is ``id_rows(x)`` when the caller already has it."""
     assert _ffi.lib.sk_instance_stats_row_values(0) == N_SUMS and _ffi.lib.sk_instance_stats_row_values(1) == N_BOX
-    if rows is None:
-        x = _as_volume(x, "x")
-        check_shape(x.shape)                                 # before anything touches the device
-        rows = (x, _id_rows(x))
-    x, rows = rows
-    check_shape(x.shape)
-    dev = x.device
-    if rows is None:
-        return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_SUMS), dtype=torch.int64, device=dev),
-                torch.empty((0, N_BOX), dtype=torch.int32, device=dev))
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
-    sums = torch.zeros((N, N_SUMS), dtype=torch.int64, device=dev)
-    boxes = torch.zeros((N, N_BOX), dtype=torch.int32, device=dev)
-    X, Y, Z = (int(v) for v in a.shape)
-    _ffi.check(_ffi.lib.sk_instance_stats(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(sums),
-                                          _ffi.ptr(boxes), _ffi.stream_ptr(dev)))
-    return ids, sums, boxes
+    m = _Rows(x, rows, check_shape)
+    sums = torch.zeros((m.N, N_SUMS), dtype=torch.int64, device=m.dev)
+    boxes = torch.zeros((m.N, N_BOX), dtype=torch.int32, device=m.dev)
+    if not m.empty:
+        m.call(_ffi.lib.sk_instance_stats, _ffi.ptr(sums), _ffi.ptr(boxes))
+    return m.ids, sums, boxes
 
 
 def instance_mesh_cells(x: Tensor, closed: bool = False, rows=None) -> Tuple[Tensor, Tensor]:
@@ -256,22 +293,13 @@ def instance_mesh_cells(x: Tensor, closed: bool = False, rows=None) -> Tuple[Ten
     volume stays open there.  ``closed=True`` measures the mask padded with one layer of background.  ``rows`` is
     ``id_rows(x)`` when the caller already has it."""
     from .mc_table import CLASS_OF, CLASS_TRIANGLES
-    x, rows = id_rows(x) if rows is None else rows
-    X, Y, Z = (int(v) for v in x.shape)
-    if X * Y * Z >= 2 ** 62:
-        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure: X*Y*Z must stay below 2^62")
-    dev = x.device
+    m = _Rows(x, rows, check_voxels)
     n_classes = len(CLASS_TRIANGLES)
-    if rows is None:
-        return (torch.empty(0, dtype=torch.int64, device=dev),
-                torch.empty((0, n_classes), dtype=torch.int64, device=dev))
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
-    cells = torch.zeros((N, n_classes), dtype=torch.int64, device=dev)
-    class_of = torch.tensor(CLASS_OF, dtype=torch.uint8, device=dev)
-    _ffi.check(_ffi.lib.sk_instance_mesh_cells(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(class_of),
-                                               n_classes, int(bool(closed)), _ffi.ptr(cells), _ffi.stream_ptr(dev)))
-    return ids, cells
+    cells = torch.zeros((m.N, n_classes), dtype=torch.int64, device=m.dev)
+    if not m.empty:
+        class_of = torch.tensor(CLASS_OF, dtype=torch.uint8, device=m.dev)
+        m.call(_ffi.lib.sk_instance_mesh_cells, _ffi.ptr(class_of), n_classes, int(bool(closed)), _ffi.ptr(cells))
+    return m.ids, cells
 
 
 CONTACT_CONNECTIVITIES = (6, 18, 26)
@@ -301,16 +329,10 @@ def instance_contacts(x: Tensor, connectivity: int = 6, background: bool = False
     assert _ffi.lib.sk_instance_contacts_row_values() == N_CONTACT
     if connectivity not in CONTACT_CONNECTIVITIES or isinstance(connectivity, bool):
         raise ValueError(f"connectivity must be one of {CONTACT_CONNECTIVITIES}, got {connectivity!r}")
-    x, rows = id_rows(x) if rows is None else rows
-    X, Y, Z = (int(v) for v in x.shape)
-    if X * Y * Z >= 2 ** 62:
-        raise ValueError(f"a mask of shape {(X, Y, Z)} is too large to measure: X*Y*Z must stay below 2^62")
-    dev = x.device
-    if rows is None:
-        return (torch.empty(0, dtype=torch.int64, device=dev),
-                torch.empty((0, N_CONTACT), dtype=torch.int64, device=dev))
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
+    m = _Rows(x, rows, check_voxels)
+    dev, N, (X, Y, Z) = m.dev, m.N, m.shape
+    if m.empty:
+        return m.ids, torch.empty((0, N_CONTACT), dtype=torch.int64, device=dev)
     if capacity is None:
         capacity = _pow2_at_least(max(1024, 8 * N))
     capacity = int(capacity)
@@ -324,9 +346,8 @@ def instance_contacts(x: Tensor, connectivity: int = 6, background: bool = False
         ws_bytes = int(_ffi.lib.sk_instance_contacts_workspace_bytes(capacity))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         out = torch.empty((capacity, N_CONTACT), dtype=torch.int64, device=dev)
-        _ffi.check(_ffi.lib.sk_instance_contacts(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, int(connectivity),
-                                                 int(bool(background)), _ffi.ptr(out), capacity, _ffi.ptr(counts),
-                                                 _ffi.ptr(ws), ws_bytes, _ffi.stream_ptr(dev)))
+        m.call(_ffi.lib.sk_instance_contacts, int(connectivity), int(bool(background)), _ffi.ptr(out), capacity,
+               _ffi.ptr(counts), _ffi.ptr(ws), ws_bytes)
         stored, refused = (int(v) for v in counts.tolist())
         if refused == 0:
             break
@@ -334,7 +355,7 @@ def instance_contacts(x: Tensor, connectivity: int = 6, background: bool = False
         capacity = max(2 * capacity, _pow2_at_least(2 * min(stored + refused, most)))
     table = out[:stored]
     order = torch.argsort(table[:, 0] * (N + 1) + table[:, 1])     # lo, hi <= N: one int64 key
-    return ids, table[order].contiguous()
+    return m.ids, table[order].contiguous()
 
 
 # ---- the image under every instance ----
@@ -420,15 +441,14 @@ def _check_shift(extrema: Tensor, shift: int) -> None:
                          f"{max(top.bit_length() - 8, 0)}")
 
 
-def _intensity_launch(a, lut, max_id, N, img, elem_bytes, shift, want_hist):
-    dev = a.device
-    moments = torch.zeros((N, N_MOMENTS), dtype=torch.int64, device=dev)
-    extrema = torch.zeros((N, N_EXTREMA), dtype=torch.int32, device=dev)
-    hist = torch.zeros((N, N_BINS), dtype=torch.int64, device=dev) if want_hist else None
-    X, Y, Z = (int(v) for v in a.shape)
-    _ffi.check(_ffi.lib.sk_instance_intensity(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(img), elem_bytes,
-                                              shift, _ffi.ptr(moments), _ffi.ptr(extrema), _ffi.ptr(hist),
-                                              _ffi.stream_ptr(dev)))
+def _intensity_launch(m: _Rows, img, elem_bytes, shift, want_hist):
+    """(moments, extrema, hist or None) of the image under the rows of ``m``; empty tables for an empty mask"""
+    moments = torch.zeros((m.N, N_MOMENTS), dtype=torch.int64, device=m.dev)
+    extrema = torch.zeros((m.N, N_EXTREMA), dtype=torch.int32, device=m.dev)
+    hist = torch.zeros((m.N, N_BINS), dtype=torch.int64, device=m.dev) if want_hist else None
+    if not m.empty:
+        m.call(_ffi.lib.sk_instance_intensity, _ffi.ptr(img), elem_bytes, shift, _ffi.ptr(moments), _ffi.ptr(extrema),
+               _ffi.ptr(hist))
     return moments, extrema, hist
 
 
@@ -450,25 +470,15 @@ def instance_intensity(x: Tensor, image: Tensor, rows=None, want_hist: bool = Tr
     shape = _volume_shape(rows[0] if rows is not None else x)
     if shape is not None:
         check_image(image, shape)                            # before anything touches the device
-    if rows is None:
-        x = _as_volume(x, "x")
-        check_intensity_shape(x.shape, 1 if image.dtype in (torch.uint8, torch.int8) else 2)
-        rows = (x, _id_rows(x))
-    x, rows = rows
-    dev = x.device
-    img, elem_bytes, top = _as_image(image, x.shape, dev)
-    check_intensity_shape(x.shape, elem_bytes)
+    # the guard before anything touches the device; a signed image is measured as what _as_image makes of it
+    m = _Rows(x, rows, lambda s: check_intensity_shape(s, 1 if image.dtype in (torch.uint8, torch.int8) else 2))
+    img, elem_bytes, top = _as_image(image, m.shape, m.dev)
     given = shift is not None
     shift = _image_shift(img, elem_bytes, top, shift)
-    if rows is None:
-        return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_MOMENTS), dtype=torch.int64, device=dev),
-                torch.empty((0, N_EXTREMA), dtype=torch.int32, device=dev),
-                torch.empty((0, N_BINS), dtype=torch.int64, device=dev) if want_hist else None, shift)
-    a, ids, lut, max_id = rows
-    moments, extrema, hist = _intensity_launch(a, lut, max_id, int(ids.numel()), img, elem_bytes, shift, bool(want_hist))
+    moments, extrema, hist = _intensity_launch(m, img, elem_bytes, shift, bool(want_hist))
     if given and want_hist:
         _check_shift(extrema, shift)
-    return ids, moments, extrema, hist, shift
+    return m.ids, moments, extrema, hist, shift
 
 
 def intensity_ring(x: Tensor, image: Tensor, distance, spacing=(1.0, 1.0, 1.0), rows=None) -> Tuple[Tensor, Tensor]:
@@ -488,23 +498,18 @@ def intensity_ring(x: Tensor, image: Tensor, distance, spacing=(1.0, 1.0, 1.0), 
     shape = _volume_shape(rows[0] if rows is not None else x)
     if shape is not None:
         check_image(image, shape)
-    x, rows = id_rows(x) if rows is None else rows
-    dev = x.device
-    img, elem_bytes, _ = _as_image(image, x.shape, dev)
-    check_intensity_shape(x.shape, elem_bytes)
-    if rows is None:
-        return (torch.empty((0, N_MOMENTS), dtype=torch.int64, device=dev),
-                torch.empty((0, N_EXTREMA), dtype=torch.int32, device=dev))
-    ids = rows[1]
-    N = int(ids.numel())
-    nearest = nearest_label(x, spacing, d, None, (x, rows))[0]
-    ring = torch.where(x > 0, torch.zeros_like(nearest), nearest)
-    del nearest
-    # ids -> rows 1 .. N (every non-zero value of the ring is one of ids), 0 stays 0
-    ring = torch.where(ring > 0, torch.searchsorted(ids, ring) + 1, torch.zeros_like(ring)).to(torch.int32).contiguous()
-    lut = torch.arange(N + 1, dtype=torch.int32, device=dev)
-    moments, extrema, _ = _intensity_launch(ring, lut, N, N, img, elem_bytes, 0, False)
-    return moments, extrema
+    m = _Rows(x, rows)
+    x, ids, N = m.x, m.ids, m.N
+    img, elem_bytes, _ = _as_image(image, m.shape, m.dev)
+    check_intensity_shape(m.shape, elem_bytes)
+    if not m.empty:
+        nearest = nearest_label(x, spacing, d, None, m.pair)[0]
+        ring = torch.where(x > 0, torch.zeros_like(nearest), nearest)
+        del nearest
+        # ids -> rows 1 .. N (every non-zero value of the ring is one of ids), 0 stays 0
+        ring = torch.where(ring > 0, torch.searchsorted(ids, ring) + 1, torch.zeros_like(ring)).to(torch.int32).contiguous()
+        m = _Rows(None, (ring, (ring, ids, torch.arange(N + 1, dtype=torch.int32, device=m.dev), N)))
+    return _intensity_launch(m, img, elem_bytes, 0, False)[:2]
 
 
 MESH_BUDGET = 4 << 30          # bytes of vertex and triangle records instance_meshes may ask for
@@ -543,29 +548,23 @@ def _mesh_prologue(x: Tensor, rows, ids):
         if have.numel() == 0 or not bool((have[at] == want).all()):
             missing = want.tolist() if have.numel() == 0 else want[have[at] != want].tolist()
             raise ValueError(f"ids {missing} are not in the mask")
-        a, _, lut, max_id = rows
-        # the value that `a` holds for each wanted instance: the id itself, or the row where _id_rows relabelled
-        values = torch.nonzero(lut)[:, 0][at]
-        sub = torch.zeros_like(lut)
-        sub[values] = torch.arange(1, want.numel() + 1, dtype=torch.int32, device=x.device)
-        rows = (a, want, sub, max_id)
+        m = _Rows(None, (x, rows))
+        sub = torch.zeros_like(m.lut)                        # every other instance is background
+        sub[m.values()[at]] = torch.arange(1, want.numel() + 1, dtype=torch.int32, device=x.device)
+        rows = (m.a, want, sub, m.max_id)
     return x, rows, (X, Y, Z)
 
 
 def instance_mesh_counts(x: Tensor, closed: bool = True, rows=None, ids=None) -> Tuple[Tensor, Tensor]:
     """(ids (N) int64 ascending, counts (N, 2) int64): vertices and triangles of the marching-cubes mesh of every
     instance, from one ``sk_instance_mesh_count`` launch.  The arguments are ``instance_meshes``'."""
-    x, rows, (X, Y, Z) = _mesh_prologue(x, rows, ids)
-    dev = x.device
-    if rows is None:
-        return torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, 2), dtype=torch.int64, device=dev)
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
-    counts = torch.zeros((N, 2), dtype=torch.int64, device=dev)
-    table = torch.from_numpy(packed_triangle_table().view(np.int64)).to(dev)
-    _ffi.check(_ffi.lib.sk_instance_mesh_count(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(table),
-                                               int(bool(closed)), _ffi.ptr(counts), _ffi.stream_ptr(dev)))
-    return ids, counts
+    x, rows, _ = _mesh_prologue(x, rows, ids)
+    m = _Rows(None, (x, rows))
+    counts = torch.zeros((m.N, 2), dtype=torch.int64, device=m.dev)
+    if not m.empty:
+        table = torch.from_numpy(packed_triangle_table().view(np.int64)).to(m.dev)
+        m.call(_ffi.lib.sk_instance_mesh_count, _ffi.ptr(table), int(bool(closed)), _ffi.ptr(counts))
+    return m.ids, counts
 
 
 def instance_meshes(x: Tensor, closed: bool = True, rows=None, ids=None,
@@ -594,13 +593,13 @@ def instance_meshes(x: Tensor, closed: bool = True, rows=None, ids=None,
     ``budget_bytes`` (16 bytes per vertex, 40 per triangle; sorting needs about as much again), or when
     N * 8 * (X+2)(Y+2)(Z+2) reaches 2^63 and the sort keys would leave int64."""
     x, rows, (X, Y, Z) = _mesh_prologue(x, rows, ids)
-    dev = x.device
-    N = int(rows[1].numel()) if rows is not None else 0
+    m = _Rows(None, (x, rows))
+    dev, N = m.dev, m.N
     padded = (X + 2) * (Y + 2) * (Z + 2)
     if N * 8 * padded >= 2 ** 63:
         raise ValueError(f"{N} instances in a mask of shape {(X, Y, Z)}: N * 8 * (X+2)(Y+2)(Z+2) = {N * 8 * padded} "
                          "must stay below 2^63 for the sort keys; mesh fewer instances at a time with ids=[...]")
-    ids_out, counts = instance_mesh_counts(x, closed, (x, rows))
+    ids_out, counts = instance_mesh_counts(x, closed, m.pair)
     out = {"ids": ids_out}
     V, F = (int(v) for v in counts.sum(0).tolist()) if N else (0, 0)
     need = V * _VERTEX_BYTES + F * _TRIANGLE_BYTES
@@ -617,14 +616,12 @@ def instance_meshes(x: Tensor, closed: bool = True, rows=None, ids=None,
                    faces=torch.empty((0, 3), dtype=torch.int32, device=dev), vertex_offsets=zeros,
                    face_offsets=zeros.clone())
         return out
-    a, _, lut, max_id = rows
     vrec = torch.empty((V, 2), dtype=torch.int64, device=dev)
     trec = torch.empty((F, 5), dtype=torch.int64, device=dev)
     produced = torch.zeros(2, dtype=torch.int64, device=dev)
     table = torch.from_numpy(packed_triangle_table().view(np.int64)).to(dev)
-    _ffi.check(_ffi.lib.sk_instance_mesh_emit(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(table),
-                                              int(bool(closed)), _ffi.ptr(vrec), V, _ffi.ptr(trec), F,
-                                              _ffi.ptr(produced), _ffi.stream_ptr(dev)))
+    m.call(_ffi.lib.sk_instance_mesh_emit, _ffi.ptr(table), int(bool(closed)), _ffi.ptr(vrec), V, _ffi.ptr(trec), F,
+           _ffi.ptr(produced))
     if produced.tolist() != [V, F]:
         raise RuntimeError(f"sk_instance_mesh_emit produced {produced.tolist()} records where the count pass gave "
                            f"{[V, F]}")
@@ -691,17 +688,14 @@ def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int 
     instance's id before anything is launched.  ``want_volume`` adds a volume that is 0 outside the skeletons and the
     instance's row (1 .. N) on its skeleton voxels."""
     from ..lib.morphology import skeleton_graph
-    x, rows = id_rows(x) if rows is None else rows
-    check_shape(x.shape)
-    dev = x.device
-    volume = torch.zeros(tuple(x.shape), dtype=torch.int32, device=dev) if want_volume else None
-    if rows is None:
-        out = (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, N_GRAPH), dtype=torch.int64, device=dev))
+    m = _Rows(x, rows, check_shape)
+    a, ids, N, dev = m.a, m.ids, m.N, m.dev
+    volume = torch.zeros(m.shape, dtype=torch.int32, device=dev) if want_volume else None
+    if m.empty:
+        out = (ids, torch.empty((0, N_GRAPH), dtype=torch.int64, device=dev))
         return out + (volume,) if want_volume else out
-    a, ids, lut, _ = rows
-    N = int(ids.numel())
     if boxes is None:
-        boxes = instance_sums(x, (x, rows))[2]
+        boxes = instance_sums(m.x, m.pair)[2]
     b = boxes.cpu().numpy().astype(np.int64).reshape(N, N_BOX)
     b[:, 3:] += 1                                            # inclusive -> [x0, x1 + 1)
     ext = b[:, 3:] - b[:, :3]
@@ -712,8 +706,7 @@ def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int 
         raise ValueError(f"instance {int(ids[i].item())} has a box of {tuple(int(v) for v in ext[i])} voxels, too large "
                          "to thin: a crop must stay below 2^30 voxels (and 2^31 / 6 words of padded bit plane)")
     b = np.ascontiguousarray(b.astype(np.int32))
-    # the value that `a` holds for row k: the id itself, or the row where _id_rows relabelled the mask
-    values = torch.nonzero(lut)[:, 0].to(torch.int32).cpu().numpy()
+    values = m.values().to(torch.int32).cpu().numpy()
     assert values.shape[0] == N
     graph = torch.empty((N, N_GRAPH), dtype=torch.int64, device=dev)
     for first, last in _skeleton_batches(b, int(budget_bytes)):
@@ -741,16 +734,14 @@ def instance_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False,
     order with numpy, so the mean is the same on every run (a plain left-to-right sum over the count, kept inside
     [minimum, maximum]); a row without skeleton voxels has 0.0 in all three columns (no real radius is 0)."""
     from ..lib.morphology import label_edt
-    x, rows = id_rows(x) if rows is None else rows
-    dev = x.device
-    if skeleton is not None and (tuple(skeleton.shape) != tuple(x.shape) or skeleton.device != dev):
-        raise ValueError(f"skeleton must be the {tuple(x.shape)} row volume of instance_skeleton_graph on {dev}, got "
+    m = _Rows(x, rows)
+    ids, N = m.ids, m.N
+    if skeleton is not None and (tuple(skeleton.shape) != m.shape or skeleton.device != m.dev):
+        raise ValueError(f"skeleton must be the {m.shape} row volume of instance_skeleton_graph on {m.dev}, got "
                          f"shape {tuple(skeleton.shape)} on {skeleton.device}")
-    dist2, max_d2 = label_edt(x, spacing, closed, (x, rows))
-    ids = rows[1] if rows is not None else torch.empty(0, dtype=torch.int64, device=dev)
+    dist2, max_d2 = label_edt(m.x, spacing, closed, m.pair)
     if skeleton is None:
         return ids, max_d2, dist2
-    N = int(ids.numel())
     at = torch.nonzero(skeleton.reshape(-1))[:, 0]           # raster order
     row = skeleton.reshape(-1)[at].cpu().numpy().astype(np.int64)
     radius = np.sqrt(dist2.reshape(-1)[at].cpu().numpy())
@@ -782,20 +773,18 @@ def instance_local_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = 
     ``row * n_values + inverse`` -- so it is exact and the same on every run; ``compare.local_thickness_columns`` turns
     it into the columns on the host."""
     from ..lib.morphology import local_thickness
-    x, rows = id_rows(x) if rows is None else rows
-    dev = x.device
-    thick2, _, max_d2 = local_thickness(x, spacing, closed, (x, rows), dist2)
-    if rows is None:
-        return torch.empty(0, dtype=torch.int64, device=dev), np.zeros((0, 3), np.int64), thick2, max_d2
-    a, ids, lut, _ = rows
-    row = lut[a.reshape(-1).long().clamp_(min=0)].long()     # 1..N, 0 for the background and for negative values
+    m = _Rows(x, rows)
+    thick2, _, max_d2 = local_thickness(m.x, spacing, closed, m.pair, dist2)
+    if m.empty:
+        return m.ids, np.zeros((0, 3), np.int64), thick2, max_d2
+    row = m.row_volume().reshape(-1).long()
     fg = torch.nonzero(row)[:, 0]
     values, inverse = torch.unique(thick2.reshape(-1)[fg].view(torch.int64), return_inverse=True)
     n_values = int(values.numel())
     keys, counts = torch.unique(row[fg] * n_values + inverse, return_counts=True)
     table = torch.stack((torch.div(keys, max(n_values, 1), rounding_mode="floor"), values[keys % max(n_values, 1)],
                          counts), 1)
-    return ids, table.cpu().numpy().astype(np.int64), thick2, max_d2
+    return m.ids, table.cpu().numpy().astype(np.int64), thick2, max_d2
 
 
 # ---- compare(): surfaces, matching and surface distances (DESIGN.md §25) ----
@@ -829,31 +818,25 @@ def instance_surfaces(x: Tensor, rows=None) -> Tuple[Tensor, Tensor, Tensor]:
     ``keys[offsets[k]:offsets[k + 1]]``, its voxels in x-major order.  One count pass, one emit pass
     (``sk_instance_surface_count``, ``sk_instance_surface_emit``) and one ``torch.sort``.  ``rows`` is ``id_rows(x)``
     when the caller already has it."""
-    x, rows = id_rows(x) if rows is None else rows
-    X, Y, Z = (int(v) for v in x.shape)
-    dev = x.device
-    if rows is None:
-        return (torch.empty(0, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
-                torch.empty(0, dtype=torch.int64, device=dev))
-    a, ids, lut, max_id = rows
-    N = int(ids.numel())
+    m = _Rows(x, rows)
+    dev, N, (X, Y, Z) = m.dev, m.N, m.shape
+    if m.empty:
+        return m.ids, torch.zeros(1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
     if max(X, Y, Z) > _MAX_EXTENT or N * X * Y * Z >= 2 ** 63:
         raise ValueError(f"{N} instances in a mask of shape {(X, Y, Z)}: every extent must stay within 2^26 and "
                          "N*X*Y*Z below 2^63, or the surface keys leave int64")
     counts = torch.zeros(N, dtype=torch.int64, device=dev)
-    _ffi.check(_ffi.lib.sk_instance_surface_count(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, _ffi.ptr(counts),
-                                                  _ffi.stream_ptr(dev)))
+    m.call(_ffi.lib.sk_instance_surface_count, _ffi.ptr(counts))
     total = int(counts.sum().item())
     keys = torch.empty(total, dtype=torch.int64, device=dev)
     produced = torch.zeros(1, dtype=torch.int64, device=dev)
-    _ffi.check(_ffi.lib.sk_instance_surface_emit(_ffi.ptr(a), X, Y, Z, _ffi.ptr(lut), max_id, N, total, _ffi.ptr(keys),
-                                                 _ffi.ptr(produced), _ffi.stream_ptr(dev)))
+    m.call(_ffi.lib.sk_instance_surface_emit, total, _ffi.ptr(keys), _ffi.ptr(produced))
     if int(produced.item()) != total:
         raise RuntimeError(f"sk_instance_surface_emit produced {int(produced.item())} keys where the count pass gave "
                            f"{total}")
     keys = torch.sort(keys)[0]
     offsets = torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))
-    return ids, offsets, keys
+    return m.ids, offsets, keys
 
 
 def _launches(qo: np.ndarray, to: np.ndarray, pairs: np.ndarray, budget: int):

@@ -80,6 +80,7 @@ namespace sk { static unsigned stream_grid(long long n, int block) { return n > 
 static char g_err[512];
 #define SK_CHECK_ARG(cond, ...) do { if (!(cond)) { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return SK_ERR_ARG; } } while (0)
 #define SK_CHECK_HIP(expr) do { if ((expr) != 0) return SK_ERR_HIP; } while (0)
+static int atomicCAS(int* p, int expect, int v) { __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED); return expect; }   // instance_rows.h: claim_slot
 #define SK_CHECK_LAUNCH() do {} while (0)
 #define LAUNCH(kernel, grid, ...) \
     do for (unsigned b_ = 0, g_ = (grid); b_ < g_; ++b_) { \
@@ -177,6 +178,8 @@ int main(int argc, char** argv) {
 def build(workdir):
     with open(os.path.join(ROOT, "skoots_amd", "csrc", "edt.hip")) as f:
         text = f.read()
+    with open(os.path.join(ROOT, "skoots_amd", "csrc", "instance_rows.h")) as f:   # the shared header, in place
+        text = text.replace('#include "instance_rows.h"', f.read().replace("#pragma once", ""))
     text = text.replace('#include "common.h"', '#include "shim.h"')
     text, n = re.subn(r"(edt_pass_kernel<\d>)<<<grid, kThreads, 0, st>>>\(", r"LAUNCH(\1, grid, ", text)
     if n != 3:

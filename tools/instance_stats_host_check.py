@@ -124,6 +124,8 @@ int main(int argc, char** argv) {   // lab.bin X Y Z lut.bin max_id N sums.bin b
 def build(workdir):
     with open(os.path.join(ROOT, "skoots_amd", "csrc", "instance_stats.hip")) as f:
         text = f.read()
+    with open(os.path.join(ROOT, "skoots_amd", "csrc", "instance_rows.h")) as f:   # the shared header, in place
+        text = text.replace('#include "instance_rows.h"', f.read().replace("#pragma once", ""))
     text = text.replace('#include "common.h"', '#include "shim.h"')
     text, n = re.subn(r"(instance_stats\w*_kernel)<<<([^;]*?), kThreads, 0, st>>>\(", r"LAUNCH(\1, \2, kThreads, ", text,
                       flags=re.S)

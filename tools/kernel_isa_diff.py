@@ -3,8 +3,8 @@
 
     python tools/kernel_isa_diff.py <tree A> <tree B> [--work DIR] [--jobs N] [--out FILE]
 
-For conv3d.hip, conv3d_up.hip, unet_misc.hip and train.hip of both trees: hipcc with tree B's Makefile flags plus
---offload-device-only -S, in the builds release, -DSK_BF16 (the twin-built sources only), -DSK_TUNING and
+For every source in SOURCES (the conv3 and training sources, and the per-instance passes that share instance_rows.h)
+of both trees: hipcc with tree B's Makefile flags plus --offload-device-only -S, in the builds release, -DSK_BF16 (the twin-built sources only), -DSK_TUNING and
 -DSK_TUNING -DSK_TIMING.  The assembly is split per function symbol (instruction stream + its .amdhsa_kernel resource
 block); the __hip_cuid_* symbol, comments and the function index inside local labels are ignored.  One line per kernel:
 identical, or DIFFERENT with the number of differing lines.  Exit status 1 if any differs.  An up-to-date .s file in
@@ -19,7 +19,10 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-SOURCES = ["conv3d.hip", "conv3d_up.hip", "unet_misc.hip", "train.hip"]
+SOURCES = ["conv3d.hip", "conv3d_up.hip", "unet_misc.hip", "train.hip",
+           # the per-instance passes that share instance_rows.h
+           "instance_stats.hip", "instance_mesh.hip", "instance_mesh_emit.hip", "instance_intensity.hip",
+           "surface_distance.hip", "contacts.hip", "edt.hip", "nearest_label.hip"]
 TWINS = {"conv3d.hip", "unet_misc.hip", "train.hip"}
 BUILDS = [("release", []), ("bf16", ["-DSK_BF16"]), ("tuning", ["-DSK_TUNING"]), ("timing", ["-DSK_TUNING", "-DSK_TIMING"])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

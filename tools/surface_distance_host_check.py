@@ -215,6 +215,8 @@ int main(int argc, char** argv) {
 def build(workdir):
     with open(os.path.join(ROOT, "skoots_amd", "csrc", "surface_distance.hip")) as f:
         text = f.read()
+    with open(os.path.join(ROOT, "skoots_amd", "csrc", "instance_rows.h")) as f:   # the shared header, in place
+        text = text.replace('#include "instance_rows.h"', f.read().replace("#pragma once", ""))
     text = text.replace('#include "common.h"', '#include "shim.h"')
     text, n = re.subn(r"(surface_\w+_kernel<\w+>)<<<grid, kThreads, 0, st>>>\(", r"LAUNCH(\1, grid, kThreads, ", text)
     if n != 6:
