@@ -733,6 +733,58 @@ int sk_skeleton_graph_row_values(void);
 int sk_skeleton_graph(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
                       int64_t* graph, void* stream);
 
+/* Every skeleton branch traced (ABI 26; no reference counterpart): the skeletons in the thinning
+ * workspace read as nodes and branches, one workgroup per object, integers only, the same bytes on every run.
+ *
+ * Definitions, per object.  A link is an unordered pair of 26-neighbouring skeleton voxels, the degree of a voxel the
+ * number of its links, a chain voxel one of degree 2.  A NODE is an isolated voxel (type 0), an endpoint (type 1, degree
+ * 1), a junction (type 2: a 26-connected component of voxels of degree >= 3, of any size) or a ring anchor (type 3: the
+ * first voxel, lexicographically in (x, y, z), of a cycle of chain voxels only).  A node's first voxel is its
+ * lexicographically smallest; the links between two of its own voxels are internal and belong to no branch.  A BRANCH
+ * is a maximal run of >= 1 chain voxels with the two links that end it at node voxels, or a single link between voxels
+ * of two different nodes, or a ring from its anchor round and back (n - 1 chain voxels, n links).  Both ends may lie in
+ * one node or be one voxel (a self-loop).  End a is the end with the smaller (rank of the end voxel in (x, y, z) order,
+ * direction code of the branch's first link there); the direction code is the bit index 9 (dx + 1) + 3 (dy + 1) +
+ * (dz + 1) of the 27-bit neighbourhood code.  A ring has a = b = its anchor and the smaller of the anchor's two codes.
+ *
+ * nodes (Nn, 8) int32: [0] object index, [1] type, [2] voxels, [3] internal links, [4..6] first voxel in volume
+ * coordinates (crop origin added), [7] branch ends attached (a self-loop counts 2, a ring anchor has 2).
+ * branches (Nb, 18) int32: [0] object index, [1] node row of end a, [2] node row of end b (rows of `nodes`), [3] chain
+ * voxels, [4..10] links by the direction classes of sk_skeleton_graph, terminal links included, [11..13] end voxel a,
+ * [14..16] end voxel b, volume coordinates, [17] direction code at a.
+ * owner (n_points) int32, aligned with the points of sk_skeletonize_emit: a chain voxel holds its branch row, a node
+ * voxel -1 - its node row.  Rows come object by object; within an object nodes by first voxel and branches by (end
+ * voxel a, direction code at a), rings too.
+ *
+ * sk_skeleton_pack: the arguments of sk_skeletonize; writes the crops of `labels == ids[i]` into the workspace WITHOUT
+ * thinning them -- `labels` holds skeletons already (or any binary objects) -- and fills counts; stats and *error are
+ * zeroed.  After it sk_skeleton_graph, sk_skeletonize_emit and the calls below work on the workspace as after
+ * sk_skeletonize.  Synchronises `stream`.
+ * sk_skeleton_branches_scratch_bytes: bytes of scratch for these boxes and counts (host arrays; 44 per skeleton voxel
+ * + 16); 0 if a box is refused, a count is negative or exceeds its crop, or the counts sum to 2^31 or more.
+ * sk_skeleton_branches_count: node_branch_counts (n, 2) int32 = nodes and branches of every object; offsets (n + 1)
+ * int32 on the device is the exclusive prefix sum of counts, as for sk_skeletonize_emit.  An object whose plane does
+ * not hold exactly offsets[i + 1] - offsets[i] voxels inside its crop gets (-1, -1) and is not traced.
+ * sk_skeleton_branches_emit: the rows, at node_offsets / branch_offsets (n + 1) int32 on the device, the exclusive
+ * prefix sums of the counts; no node row at or beyond n_nodes, no branch row at or beyond n_branches and no owner at or
+ * beyond n_points is written.  The scratch is working memory: the passes do not hand anything to each other in it.
+ * Every argument is checked before anything is launched (SK_ERR_ARG): null pointers, sizes of workspace and scratch,
+ * alignment (workspace 16 bytes, everything else 4), totals below 2^31.
+ * sk_skeleton_nodes_row_values: 8; sk_skeleton_branches_row_values: 18. */
+int sk_skeleton_pack(const int32_t* labels, int X, int Y, int Z, const int32_t* ids, const int32_t* boxes_host, int n,
+                     void* workspace, size_t workspace_bytes, int32_t* counts, int32_t* stats, int32_t* error,
+                     void* stream);
+int sk_skeleton_nodes_row_values(void);
+int sk_skeleton_branches_row_values(void);
+size_t sk_skeleton_branches_scratch_bytes(const int32_t* boxes_host, const int32_t* counts_host, int n);
+int sk_skeleton_branches_count(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
+                               const int32_t* offsets, int64_t n_points, void* scratch, size_t scratch_bytes,
+                               int32_t* node_branch_counts, void* stream);
+int sk_skeleton_branches_emit(const int32_t* boxes_host, int n, const void* workspace, size_t workspace_bytes,
+                              const int32_t* offsets, int64_t n_points, void* scratch, size_t scratch_bytes,
+                              const int32_t* node_offsets, const int32_t* branch_offsets, int64_t n_nodes,
+                              int64_t n_branches, int32_t* nodes, int32_t* branches, int32_t* owner, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * Validation metrics (skoots/validate/lib.py:190-229 mask_iou): iou (N, M) fp32 of the N
  * ground-truth and M predicted instances, intersection / union of voxel counts, 0 for pairs that do not touch.

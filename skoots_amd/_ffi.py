@@ -191,6 +191,12 @@ _SIGS = {
     "sk_skeletonize_emit": (i32, [ip, i32, vp, sz, vp, i64, vp, vp]),
     "sk_skeleton_graph_row_values": (i32, []),
     "sk_skeleton_graph": (i32, [ip, i32, vp, sz, vp, vp]),
+    "sk_skeleton_pack": (i32, [vp, i32, i32, i32, vp, ip, i32, vp, sz, vp, vp, vp, vp]),
+    "sk_skeleton_nodes_row_values": (i32, []),
+    "sk_skeleton_branches_row_values": (i32, []),
+    "sk_skeleton_branches_scratch_bytes": (sz, [ip, ip, i32]),
+    "sk_skeleton_branches_count": (i32, [ip, i32, vp, sz, vp, i64, vp, sz, vp, vp]),
+    "sk_skeleton_branches_emit": (i32, [ip, i32, vp, sz, vp, i64, vp, sz, vp, vp, i64, i64, vp, vp, vp, vp]),
     "sk_u8_histogram": (i32, [vp, i64, vp, vp]),
     "sk_deflate_bound": (sz, [i64]),
     "sk_deflate_workspace_bytes": (sz, [i32, i64]),

@@ -1,7 +1,8 @@
 """``skoots.lib.morphology`` dilations on the MI355X
 (reference: skoots/lib/morphology.py:155-175 ``binary_dilation``, :178-199 ``binary_dilation_2d``), and the Lee
 thinning that skoots/train/generate_skeletons.py takes from scikit-image (``skeletonize``, ``thin_objects``) with the
-skeletons read as graphs (``skeleton_graph``); ``label_edt`` is the exact Euclidean distance
+skeletons read as graphs (``skeleton_graph``) and traced into node and branch tables
+(``skeleton_branches``); ``label_edt`` is the exact Euclidean distance
 transform of every instance of a label volume, which the reference does not have, and
 ``label_components`` the connected pieces of every instance at once, which it does not have
 either, nor ``nearest_label``, the nearest instance of every voxel and its distance, nor
@@ -46,9 +47,10 @@ def binary_dilation_2d(image: Tensor) -> Tensor:
 THIN_ERRORS = {1: "a re-check round bound was hit", 2: "the pass bound was hit"}
 
 
-def _thin(labels: Tensor, ids, boxes):
-    """The ``sk_skeletonize`` launch of ``thin_objects`` and ``skeleton_graph``: ``None`` without a box, else
-    ``(boxes_p, n, work, nbytes, counts)`` and ``stats``, both still on the device, the skeletons in ``work``."""
+def _thin(labels: Tensor, ids, boxes, thin: bool = True):
+    """The ``sk_skeletonize`` launch of ``thin_objects``, ``skeleton_graph`` and ``skeleton_branches``: ``None`` without
+    a box, else ``(boxes, boxes_p, n, work, nbytes, counts)`` and ``stats``, both still on the device, the skeletons in
+    ``work``.  ``thin=False`` is the ``sk_skeleton_pack`` launch instead: ``labels`` holds skeletons already."""
     if labels.ndim != 3:
         raise ValueError("labels must be (X, Y, Z)")
     _ffi.require_gpu(labels, "labels")
@@ -71,9 +73,9 @@ def _thin(labels: Tensor, ids, boxes):
     stats = torch.empty((n, 2), dtype=torch.int32, device=dev)
     err = torch.empty(1, dtype=torch.int32, device=dev)
     X, Y, Z = labels.shape
-    _ffi.check(_ffi.lib.sk_skeletonize(_ffi.ptr(labels), X, Y, Z, _ffi.ptr(ids_d), boxes_p, n, _ffi.ptr(work),
-                                       C.c_size_t(nbytes), _ffi.ptr(counts), _ffi.ptr(stats), _ffi.ptr(err),
-                                       _ffi.stream_ptr(dev)))
+    launch = _ffi.lib.sk_skeletonize if thin else _ffi.lib.sk_skeleton_pack
+    _ffi.check(launch(_ffi.ptr(labels), X, Y, Z, _ffi.ptr(ids_d), boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes),
+                      _ffi.ptr(counts), _ffi.ptr(stats), _ffi.ptr(err), _ffi.stream_ptr(dev)))
     code = int(err.item())
     if code:
         msg = "; ".join(v for k, v in THIN_ERRORS.items() if code & k)
@@ -81,8 +83,9 @@ def _thin(labels: Tensor, ids, boxes):
     return (boxes, boxes_p, n, work, nbytes, counts), stats    # boxes: boxes_p points into it
 
 
-def _emit(thinned) -> Tensor:
-    """(sum(counts), 3) int32: the skeleton voxels that ``_thin`` left in its workspace, as crop coordinates"""
+def _emit(thinned, want_offsets: bool = False):
+    """(sum(counts), 3) int32: the skeleton voxels that ``_thin`` left in its workspace, as crop coordinates; with
+    ``want_offsets`` also the (n + 1) int32 exclusive prefix sum of the counts that placed them"""
     _, boxes_p, n, work, nbytes, counts = thinned
     dev = work.device
     offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
@@ -91,7 +94,7 @@ def _emit(thinned) -> Tensor:
     points = torch.empty((total, 3), dtype=torch.int32, device=dev)
     _ffi.check(_ffi.lib.sk_skeletonize_emit(boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes), _ffi.ptr(offsets), total,
                                             _ffi.ptr(points), _ffi.stream_ptr(dev)))
-    return points
+    return (points, offsets) if want_offsets else points
 
 
 def thin_objects(labels: Tensor, ids, boxes) -> Tuple[Tensor, np.ndarray, np.ndarray]:
@@ -135,6 +138,67 @@ def skeleton_graph(labels: Tensor, ids, boxes, want_points: bool = False):
                                           _ffi.stream_ptr(work.device)))
     points = _emit(thinned) if want_points else None
     return graph, counts.cpu().numpy().astype(np.int64), points
+
+
+N_NODE, N_BRANCH = 8, 18   # int32 values per row of sk_skeleton_branches_emit's tables (checked against the library below)
+
+
+def _offsets(counts: Tensor) -> Tensor:
+    out = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts, 0, out=out[1:])
+    return out
+
+
+def skeleton_branches(labels: Tensor, ids, boxes, thin: bool = True):
+    """Every skeleton of ``thin_objects(labels, ids, boxes)`` traced into nodes and branches, on
+    the workspace the thinning leaves them in: ``sk_skeletonize``, ``sk_skeleton_graph``, ``sk_skeletonize_emit``, then
+    ``sk_skeleton_branches_count`` and ``sk_skeleton_branches_emit``.  ``thin=False`` takes ``labels`` as skeletons
+    already (``sk_skeleton_pack``): object i is ``labels[box i] == ids[i]`` as it is, any binary object.
+
+    Returns ``(graph, counts, points, nodes, branches, owner)``: graph, counts and points as ``skeleton_graph`` gives
+    them with ``want_points``; nodes (Nn, 8) int32 -- object index, type (0 isolated voxel, 1 endpoint, 2 junction, 3
+    ring anchor), voxels, internal links, first voxel (x, y, z) in the coordinates of ``labels``, branch ends attached;
+    branches (Nb, 18) int32 -- object index, node rows of ends a and b, chain voxels, links by the seven direction
+    classes of ``skeleton_graph``, end voxels a and b, direction code at a; owner (sum(counts)) int32, aligned with
+    points -- a chain voxel's branch row, or -1 - the node row of a node voxel.  All on the GPU but counts; rows come
+    object by object, nodes by first voxel and branches by (end voxel a, direction code); the same bytes on every run."""
+    assert (_ffi.lib.sk_skeleton_graph_row_values(), _ffi.lib.sk_skeleton_nodes_row_values(),
+            _ffi.lib.sk_skeleton_branches_row_values()) == (N_GRAPH, N_NODE, N_BRANCH)
+    done = _thin(labels, ids, boxes, thin)
+    dev = labels.device
+    if done is None:
+        empty = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        return (torch.zeros((0, N_GRAPH), dtype=torch.int64, device=dev), np.zeros(0, np.int64), empty(0, 3),
+                empty(0, N_NODE), empty(0, N_BRANCH), empty(0))
+    thinned, _ = done
+    _, boxes_p, n, work, nbytes, counts = thinned
+    graph = torch.empty((n, N_GRAPH), dtype=torch.int64, device=dev)
+    stream = _ffi.stream_ptr(dev)
+    _ffi.check(_ffi.lib.sk_skeleton_graph(boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes), _ffi.ptr(graph), stream))
+    points, offsets = _emit(thinned, want_offsets=True)
+    total = int(points.shape[0])
+    counts_host = np.ascontiguousarray(counts.cpu().numpy().astype(np.int32))
+    sbytes = int(_ffi.lib.sk_skeleton_branches_scratch_bytes(boxes_p, counts_host.ctypes.data_as(_ffi.ip), n))
+    if sbytes == 0:
+        raise _ffi.SkootsHipError("sk_skeleton_branches_scratch_bytes refused the counts of the thinning")
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+    per_object = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    common = (boxes_p, n, _ffi.ptr(work), C.c_size_t(nbytes), _ffi.ptr(offsets), total, _ffi.ptr(scratch),
+              C.c_size_t(sbytes))
+    _ffi.check(_ffi.lib.sk_skeleton_branches_count(*common, _ffi.ptr(per_object), stream))
+    if bool((per_object < 0).any()):
+        raise _ffi.SkootsHipError("sk_skeleton_branches_count: the workspace does not hold the skeletons its counts name")
+    node_off, branch_off = _offsets(per_object[:, 0]), _offsets(per_object[:, 1])
+    n_nodes, n_branches = int(node_off[-1].item()), int(branch_off[-1].item())
+    if max(n_nodes, n_branches) >= 2 ** 31:
+        raise ValueError(f"{n_nodes} nodes and {n_branches} branches: rows are int32; trace fewer objects at a time")
+    nodes = torch.empty((n_nodes, N_NODE), dtype=torch.int32, device=dev)
+    branches = torch.empty((n_branches, N_BRANCH), dtype=torch.int32, device=dev)
+    owner = torch.empty(total, dtype=torch.int32, device=dev)
+    node_off, branch_off = node_off.to(torch.int32), branch_off.to(torch.int32)
+    _ffi.check(_ffi.lib.sk_skeleton_branches_emit(*common, _ffi.ptr(node_off), _ffi.ptr(branch_off), n_nodes, n_branches,
+                                                  _ffi.ptr(nodes), _ffi.ptr(branches), _ffi.ptr(owner), stream))
+    return graph, counts_host.astype(np.int64), points, nodes, branches, owner
 
 
 def squared_spacing(spacing) -> Tuple[float, float, float]:

@@ -15,6 +15,10 @@ cells per triangle class, integers again, and ``class_areas`` turns the counts i
 ``skeleton=True`` / ``--skeleton`` adds the centre line: every instance is Lee-thinned in its box and the skeleton is
 read as a graph (``sk_skeleton_graph``) -- voxels, endpoints, junction voxels and the links per direction
 class, integers once more -- and ``skeleton_columns`` turns the links into a length at the voxel spacing.
+``branches=True`` / ``--branches`` traces the skeletons instead of counting them (``sk_skeleton_branches_count`` /
+``_emit``): a node table and a branch table, from which ``branch_columns`` derives components, junction
+nodes, branches, rings, cycles and branch lengths per instance, and the command writes ``<mask>_branches.csv`` and
+``<mask>_nodes.csv``.
 
 ``thickness="open"`` / ``"closed"`` / ``--thickness`` adds the width: the exact Euclidean distance transform of every
 instance (``sk_label_edt``) and ``inscribed_radius``, the square root of its maximum; together with the
@@ -61,7 +65,8 @@ import torch
 from torch import Tensor
 
 from .lib import (_Rows, check_shape, id_rows, instance_contacts, instance_intensity, instance_local_thickness,
-                  instance_mesh_cells, instance_mesh_counts, instance_meshes, instance_skeleton_graph, instance_sums,
+                  instance_mesh_cells, instance_mesh_counts, instance_meshes, instance_skeleton_branches,
+                  instance_skeleton_graph, instance_sums,
                   instance_thickness, nearest_rank)
 from .lib import intensity_ring as _intensity_ring
 from .mc_table import CLASS_TRIANGLES, TRIANGLE_TYPES
@@ -87,6 +92,13 @@ CONTACT_CSV_COLUMNS = ("id_a,id_b,faces_x,faces_y,faces_z,edges_xy,edges_xz,edge
 INTENSITY_COLUMNS = ("intensity_mean,intensity_std,intensity_min,intensity_max,intensity_median,intensity_p05,"
                      "intensity_p95,wcx,wcy,wcz")                                          # appended with --image
 RING_COLUMNS = "ring_voxels,ring_mean,ring_std,contrast"                                  # --intensity-ring
+BRANCH_COLUMNS = ("graph_components,graph_endpoints,graph_junctions,graph_branches,graph_rings,graph_corner_loops,"
+                  "graph_cycles,graph_length,branch_length_mean,longest_branch")             # appended with --branches
+BRANCH_CSV_COLUMNS = "id,branch,kind,node_a,node_b,voxels,length,chord,tortuosity,ax,ay,az,bx,by,bz"
+BRANCH_RADIUS_COLUMNS = "radius_mean,radius_min,radius_max"                               # --branches with --thickness
+NODE_CSV_COLUMNS = "id,node,type,voxels,internal_links,x,y,z,branch_ends"
+NODE_TYPES = ("isolated", "endpoint", "junction", "ring-anchor")
+BRANCH_KINDS = ("endpoint-endpoint", "endpoint-junction", "junction-junction", "self-loop", "corner-loop", "ring")
 # (|dx|, |dy|, |dz|) of the link classes, columns 5 .. 11 of sk_skeleton_graph
 LINK_CLASSES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -207,6 +219,158 @@ def skeleton_columns(graph: Tensor, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor
         length += g[:, 5 + k].to(torch.float64) * math.sqrt((a * sx) ** 2 + (b * sy) ** 2 + (c * sz) ** 2)
     return {"skeleton_voxels": g[:, 0].clone(), "skeleton_length": length, "skeleton_endpoints": g[:, 2].clone(),
             "skeleton_junctions": g[:, 4].clone(), "skeleton_links": links, "skeleton_branches": links - g[:, 3]}
+
+
+def _link_steps(spacing):
+    sx, sy, sz = _spacing(spacing)
+    return [math.sqrt((a * sx) ** 2 + (b * sy) ** 2 + (c * sz) ** 2) for a, b, c in LINK_CLASSES]
+
+
+def branch_lengths(branches: Tensor, spacing=(1.0, 1.0, 1.0)) -> Tensor:
+    """(Nb) float64, host: the length of every row of the (Nb, 18) branch table at the voxel spacing -- its links per
+    direction class (columns 4 .. 10) times the class's step, summed class by class in the table's order"""
+    br = branches.cpu().to(torch.int64).reshape(-1, 18)
+    length = torch.zeros(br.shape[0], dtype=torch.float64)
+    for k, step in enumerate(_link_steps(spacing)):
+        length += br[:, 4 + k].to(torch.float64) * step
+    return length
+
+
+def branch_kinds(nodes: Tensor, branches: Tensor) -> np.ndarray:
+    """(Nb) int64: the place in ``BRANCH_KINDS`` of every row of the branch table.  A ring is the branch of a ring anchor;
+    a corner loop is a self-loop with exactly one chain voxel whose two end voxels are 26-neighbours -- a triangle of
+    pairwise adjacent voxels, which cannot enclose anything; any other branch with both ends in one node is a
+    self-loop; the rest go by the types of their two nodes."""
+    nd = nodes.cpu().numpy().astype(np.int64).reshape(-1, 8)
+    br = branches.cpu().numpy().astype(np.int64).reshape(-1, 18)
+    ta, tb = nd[br[:, 1], 1], nd[br[:, 2], 1]
+    same = br[:, 1] == br[:, 2]
+    gap = np.abs(br[:, 11:14] - br[:, 14:17]).max(1) if br.shape[0] else np.zeros(0, np.int64)
+    kind = (ta == 2).astype(np.int64) + (tb == 2)            # 0, 1 or 2 junction ends
+    kind[same] = 3
+    kind[same & (br[:, 3] == 1) & (gap == 1)] = 4
+    kind[ta == 3] = 5
+    return kind
+
+
+def branch_columns(nodes: Tensor, branches: Tensor, N: int, spacing=(1.0, 1.0, 1.0)) -> Dict[str, Tensor]:
+    """The traced-graph columns (host tensors, N rows) from the node and branch tables of
+    ``lib.instance_skeleton_branches`` -- column 0 of both the instance's index 0 .. N - 1 -- and the spacing; a pure
+    function of its arguments:
+
+    ``graph_components``: the connected pieces of the skeleton, from a union-find over the nodes along the branches (a
+    node's own voxels are connected, a branch joins its two nodes).  ``graph_endpoints``, ``graph_junctions``,
+    ``graph_rings``: the nodes of type 1, 2 and 3 -- junctions as NODES, however many voxels each has.
+    ``graph_branches``: the rows of the branch table.  ``graph_corner_loops``: ``branch_kinds`` says what they are.
+    ``graph_cycles`` = branches - nodes + components - corner loops: the independent loops of the traced graph, a
+    corner's triangle not counted.  All int64.
+
+    ``graph_length``, float64: the links of the instance's branches per direction class, summed as integers, times the
+    class's step, class by class in the table's order as ``skeleton_columns`` does; the internal links of junctions
+    are not in it.  ``branch_length_mean`` = ``graph_length / graph_branches`` and ``longest_branch``, the largest
+    ``branch_lengths`` value.  An empty skeleton gives zeros in every column, never NaN."""
+    N = int(N)
+    nd = nodes.cpu().numpy().astype(np.int64).reshape(-1, 8)
+    br = branches.cpu().numpy().astype(np.int64).reshape(-1, 18)
+    steps = _link_steps(spacing)
+    if nd.shape[0] and (nd[:, 0].min() < 0 or nd[:, 0].max() >= N):
+        raise ValueError(f"the node table names instance {int(nd[:, 0].max())} and there are {N}")
+    # union-find by minimum label: a branch pulls both of its nodes to the smaller label, then every label jumps
+    label = np.arange(nd.shape[0])
+    while br.shape[0]:
+        low = np.minimum(label[br[:, 1]], label[br[:, 2]])
+        new = label.copy()
+        np.minimum.at(new, br[:, 1], low)
+        np.minimum.at(new, br[:, 2], low)
+        new = new[new]
+        if np.array_equal(new, label):
+            break
+        label = new
+    count = lambda rows: torch.from_numpy(np.bincount(rows, minlength=N).astype(np.int64))  # noqa: E731
+    kinds = branch_kinds(nodes, branches)
+    out = {"graph_components": count(nd[label == np.arange(nd.shape[0]), 0]),
+           "graph_endpoints": count(nd[nd[:, 1] == 1, 0]), "graph_junctions": count(nd[nd[:, 1] == 2, 0]),
+           "graph_branches": count(br[:, 0]), "graph_rings": count(nd[nd[:, 1] == 3, 0]),
+           "graph_corner_loops": count(br[kinds == 4, 0])}
+    out["graph_cycles"] = out["graph_branches"] - count(nd[:, 0]) + out["graph_components"] - out["graph_corner_loops"]
+    length = torch.zeros(N, dtype=torch.float64)
+    for k, step in enumerate(steps):
+        links = np.zeros(N, np.int64)
+        np.add.at(links, br[:, 0], br[:, 4 + k])
+        length += torch.from_numpy(links).to(torch.float64) * step
+    out["graph_length"] = length
+    n_br = out["graph_branches"].to(torch.float64)
+    out["branch_length_mean"] = torch.where(n_br > 0, length / n_br.clamp(min=1.0), torch.zeros_like(length))
+    longest = np.zeros(N, np.float64)
+    np.maximum.at(longest, br[:, 0], branch_lengths(branches, spacing).numpy())
+    out["longest_branch"] = torch.from_numpy(longest)
+    return out
+
+
+def branch_radii(branches: Tensor, points: Tensor, owner: Tensor, dist2: Tensor) -> np.ndarray:
+    """(Nb, 3) float64: mean, minimum and maximum of ``sqrt(dist2)`` over every branch's end voxel a, its chain voxels in
+    the order of ``points`` and its end voxel b (once, where both ends are one voxel).  The values are gathered on the
+    device through ``owner`` and the end voxels of the table; the mean is a plain left-to-right sum over the count,
+    kept inside [minimum, maximum], as ``lib.instance_thickness`` forms it."""
+    br = branches.long().reshape(-1, 18)
+    at = lambda v: np.sqrt(dist2[v[:, 0], v[:, 1], v[:, 2]].cpu().numpy().astype(np.float64))  # noqa: E731
+    ra, rb = at(br[:, 11:14]), at(br[:, 14:17])
+    one_voxel = (br[:, 11:14] == br[:, 14:17]).all(1).cpu().numpy()
+    chain = torch.nonzero(owner >= 0)[:, 0]
+    row = owner[chain].cpu().numpy().astype(np.int64)
+    radius = at(points.long()[chain])
+    order = np.argsort(row, kind="stable")
+    row, radius = row[order], radius[order]
+    first = np.searchsorted(row, np.arange(br.shape[0] + 1))
+    out = np.zeros((br.shape[0], 3), np.float64)
+    for r in range(br.shape[0]):
+        v = [ra[r]] + radius[first[r]:first[r + 1]].tolist() + ([] if one_voxel[r] else [rb[r]])
+        total = 0.0
+        for t in v:
+            total += t
+        out[r] = (min(max(total / len(v), min(v)), max(v)), min(v), max(v))
+    return out
+
+
+def format_branches_csv(mask_path: str, ids, nodes: Tensor, branches: Tensor, spacing=(1.0, 1.0, 1.0), keep=None,
+                        radius=None) -> str:
+    """The text of ``_branches.csv``: two header lines (file, spacing), the column names ``BRANCH_CSV_COLUMNS`` and one
+    row per branch in table order: the instance's id, the branch's row in the table, its kind (``BRANCH_KINDS``), the
+    rows of its two nodes in ``_nodes.csv``, its chain voxels, its length (``branch_lengths``), the chord -- the
+    distance between its end voxels at the spacing -- the tortuosity ``length / chord`` (empty where the chord is 0:
+    rings and loops that return to their voxel) and both end voxels.  ``keep`` (N bools) leaves out the branches of
+    the instances it does not name; ``radius`` (Nb, 3; ``branch_radii``) appends ``BRANCH_RADIUS_COLUMNS``."""
+    spacing = _spacing(spacing)
+    ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
+    br = branches.cpu().numpy().astype(np.int64).reshape(-1, 18)
+    kinds = branch_kinds(nodes, branches).tolist()
+    length = branch_lengths(branches, spacing).tolist()
+    lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
+             BRANCH_CSV_COLUMNS + ("," + BRANCH_RADIUS_COLUMNS if radius is not None else "") + "\n"]
+    for r, row in enumerate(br.tolist()):
+        if keep is not None and not keep[row[0]]:
+            continue
+        chord = math.sqrt(sum(((a - b) * s) ** 2 for a, b, s in zip(row[11:14], row[14:17], spacing)))
+        cells = [int(ids[row[0]]), r, BRANCH_KINDS[kinds[r]], row[1], row[2], row[3], repr(length[r]), repr(chord),
+                 repr(length[r] / chord) if chord > 0 else "", *row[11:17]]
+        if radius is not None:
+            cells += [repr(float(v)) for v in radius[r]]
+        lines.append(",".join(str(c) for c in cells) + "\n")
+    return "".join(lines)
+
+
+def format_nodes_csv(mask_path: str, ids, nodes: Tensor, keep=None) -> str:
+    """The text of ``_nodes.csv``: a header line (file), the column names ``NODE_CSV_COLUMNS`` and one row per node in
+    table order: the instance's id, the node's row in the table (what ``_branches.csv`` names), its type
+    (``NODE_TYPES``), voxels, internal links, first voxel and the branch ends attached.  ``keep`` as in
+    ``format_branches_csv``."""
+    ids = ids.cpu().tolist() if isinstance(ids, Tensor) else list(ids)
+    lines = [f"Mask File: {mask_path}\n", NODE_CSV_COLUMNS + "\n"]
+    for r, row in enumerate(nodes.cpu().numpy().astype(np.int64).reshape(-1, 8).tolist()):
+        if keep is not None and not keep[row[0]]:
+            continue
+        lines.append(",".join(str(c) for c in [int(ids[row[0]]), r, NODE_TYPES[row[1]], *row[2:]]) + "\n")
+    return "".join(lines)
 
 
 def thickness_columns(max_d2: Tensor, skel_stats: Optional[Tensor] = None) -> Dict[str, Tensor]:
@@ -460,11 +624,22 @@ def format_histograms_csv(mask_path: str, ids, hist, shift: int) -> str:
     return "".join(lines)
 
 
+def points_volume(points: Tensor, graph: Tensor, shape) -> Tensor:
+    """(X, Y, Z) int32, the row volume of ``lib.instance_skeleton_graph(..., want_volume=True)`` from the points of
+    ``lib.instance_skeleton_branches``: 0 outside the skeletons, the instance's row 1 .. N on its skeleton voxels"""
+    volume = torch.zeros(tuple(int(v) for v in shape), dtype=torch.int32, device=points.device)
+    row = torch.repeat_interleave(torch.arange(1, graph.shape[0] + 1, device=points.device), graph[:, 0])
+    p = points.long()
+    volume[p[:, 0], p[:, 1], p[:, 2]] = row.to(torch.int32)
+    return volume
+
+
 def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[str] = None,
                        skeleton: bool = False, thickness: Optional[str] = None,
                        mesh: Optional[str] = None, pieces: Optional[int] = None,
                        local_thickness: Optional[str] = None, contacts: Optional[int] = None,
-                       image: Optional[Tensor] = None, intensity_ring=None) -> Dict[str, Tensor]:
+                       image: Optional[Tensor] = None, intensity_ring=None, branches: bool = False,
+                       skeleton_volume: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -520,7 +695,16 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     ``weighted_centroid``.  ``intensity_ring=D`` with it adds ``ring_moments`` (N, 6) int64, the image
     over the background within D (in the units of ``anisotropy``) that is nearest to this instance
     (``lib.intensity_ring``), and the columns of ``ring_columns``: ``ring_voxels``, ``ring_mean``, ``ring_std``,
-    ``contrast``.  ``intensity_ring`` without ``image`` raises ``ValueError``."""
+    ``contrast``.  ``intensity_ring`` without ``image`` raises ``ValueError``.
+
+    ``branches=True`` implies ``skeleton=True`` and adds the traced skeletons of ``lib.instance_skeleton_branches``
+    (DESIGN.md §32): ``skeleton_nodes`` (Nn, 8) and ``skeleton_branch_table`` (Nb, 18) int32, ``skeleton_points`` (P, 3)
+    and ``skeleton_owner`` (P) int32, and the columns of ``branch_columns``: ``graph_components``, ``graph_endpoints``,
+    ``graph_junctions``, ``graph_branches``, ``graph_rings``, ``graph_corner_loops``, ``graph_cycles``,
+    ``graph_length``, ``branch_length_mean``, ``longest_branch``.  ``skeleton_volume`` (an integer device volume with an
+    instance's id on its skeleton voxels, what ``--save-skeletons`` writes) is traced instead of thinning anything."""
+    if skeleton_volume is not None and not branches:
+        raise ValueError("skeleton_volume is what branches=True traces: it needs branches")
     if intensity_ring is not None and image is None:
         raise ValueError("intensity_ring measures the image around every instance: it needs image")
     if contacts not in CONTACT_MODES or isinstance(contacts, bool):
@@ -549,7 +733,14 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         out["mesh_cells"] = cells
         out.update({k: v.to(sums.device) for k, v in surface_columns(cells, out["volume"], spacing).items()})
     volume = None
-    if skeleton:
+    if branches:
+        _, graph, nodes, table, points, owner = instance_skeleton_branches(x, rows, boxes, skeleton=skeleton_volume)
+        out.update(skeleton_graph=graph, skeleton_nodes=nodes, skeleton_branch_table=table, skeleton_points=points,
+                   skeleton_owner=owner)
+        out.update({k: v.to(sums.device) for k, v in skeleton_columns(graph, spacing).items()})
+        out.update({k: v.to(sums.device) for k, v in branch_columns(nodes, table, int(ids.numel()), spacing).items()})
+        volume = [points_volume(points, graph, shape)] if thickness is not None else None
+    elif skeleton:
         _, graph, *volume = instance_skeleton_graph(x, rows, boxes, want_volume=thickness is not None)
         out["skeleton_graph"] = graph
         out.update({k: v.to(sums.device) for k, v in skeleton_columns(graph, spacing).items()})
@@ -717,7 +908,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
                mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None,
-               contact_table=None, intensity=None, ring=None) -> str:
+               contact_table=None, intensity=None, ring=None, branch_tables=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -737,7 +928,10 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     ``(moments, extrema, hist, shift)`` of ``instance_intensity``) ``intensity_mean,intensity_std,intensity_min,
     intensity_max,intensity_median,intensity_p05,intensity_p95,wcx,wcy,wcz`` follow, and with ``ring`` (the (N, 6) moments
     of ``intensity_ring``; it needs ``intensity``) ``ring_voxels,ring_mean,ring_std,contrast`` last, under the same rule
-    once more: floats with ``repr`` (``nan`` prints as ``nan``), integers as integers."""
+    once more: floats with ``repr`` (``nan`` prints as ``nan``), integers as integers.  With ``branch_tables`` (the
+    ``(nodes, branches)`` of ``instance_skeleton_branches``) the columns of ``branch_columns`` come last of all:
+    ``graph_components,graph_endpoints,graph_junctions,graph_branches,graph_rings,graph_corner_loops,graph_cycles,
+    graph_length,branch_length_mean,longest_branch``."""
     if ring is not None and intensity is None:
         raise ValueError("ring comes with intensity: the contrast needs both")
     spacing = _spacing(spacing)
@@ -765,6 +959,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         d.update(intensity_columns(*intensity, spacing))
     if ring is not None:
         d.update(ring_columns(ring, intensity[0]))
+    if branch_tables is not None:
+        d.update(branch_columns(*branch_tables, len(ids), spacing))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
@@ -775,7 +971,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + LOCAL_THICKNESS_COLUMNS if thickness_table is not None else "") +
              ("," + CONTACT_COLUMNS if contact_table is not None else "") +
              ("," + INTENSITY_COLUMNS if intensity is not None else "") +
-             ("," + RING_COLUMNS if ring is not None else "") + "\n"]
+             ("," + RING_COLUMNS if ring is not None else "") +
+             ("," + BRANCH_COLUMNS if branch_tables is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -804,6 +1001,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                       *(d[k][i] for k in INTENSITY_COLUMNS.split(",")[2:7]), *(repr(v) for v in d["weighted_centroid"][i])]
         if ring is not None:
             cells += [d["ring_voxels"][i], repr(d["ring_mean"][i]), repr(d["ring_std"][i]), repr(d["contrast"][i])]
+        if branch_tables is not None:
+            names = BRANCH_COLUMNS.split(",")
+            cells += [d[k][i] for k in names[:7]] + [repr(d[k][i]) for k in names[7:]]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -825,6 +1025,14 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--save-skeletons", action="store_true",
                         help="Also write <mask>_skeletons.tif, every skeleton voxel carrying its instance id, stored "
                              "[Z, X, Y] like the mask (implies --skeleton)")
+    parser.add_argument("--branches", action="store_true",
+                        help="Append " + BRANCH_COLUMNS + ": every skeleton traced into nodes and branches; also write "
+                             "<mask>_branches.csv, one row per branch (" + BRANCH_CSV_COLUMNS + "; with --thickness also " +
+                             BRANCH_RADIUS_COLUMNS + " along the branch) and <mask>_nodes.csv, one row per node (" +
+                             NODE_CSV_COLUMNS + ") (implies --skeleton)")
+    parser.add_argument("--skeleton-from", type=str, default=None, metavar="PATH",
+                        help="With --branches: trace the skeletons of PATH, a stack that --save-skeletons wrote for this "
+                             "mask, instead of thinning the instances again")
     parser.add_argument("--thickness", type=str, default=None, choices=("open", "closed"),
                         help="Append " + THICKNESS_COLUMNS + ": the largest distance from a voxel of the instance to the "
                              "nearest voxel outside it, from an exact Euclidean distance transform at the spacing, "
@@ -888,7 +1096,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
     args = parser.parse_args(argv)
-    args.skeleton = args.skeleton or args.save_skeletons
+    args.skeleton = args.skeleton or args.save_skeletons or args.branches
+    if args.skeleton_from is not None and not args.branches:
+        parser.error("--skeleton-from names the skeletons that --branches traces")
     if args.save_distance and args.thickness is None:
         args.thickness = "open"
     if args.save_thickness and args.local_thickness is None:
@@ -937,8 +1147,25 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
     rows = id_rows(dev_mask)                                # once, for both kernels
     ids, sums, boxes = instance_sums(dev_mask, rows)
     cells = instance_mesh_cells(dev_mask, args.surface_area == "closed", rows)[1] if args.surface_area else None
-    graph = None
-    if args.skeleton:
+    graph = branch_tables = None
+    if args.branches:
+        from .__main__ import load_mask as load_stack
+        saved = None
+        if args.skeleton_from is not None:
+            if not os.path.exists(args.skeleton_from):
+                raise RuntimeError(f"{args.skeleton_from} does not exist")
+            saved = load_stack(args.skeleton_from)
+            if tuple(saved.shape) != tuple(mask.shape):
+                raise ValueError(f"{args.skeleton_from} has the shape {tuple(saved.shape)} and {args.mask} "
+                                 f"{tuple(mask.shape)}: the skeletons of a mask have its shape")
+            saved = saved.to("cuda")
+        if args.save_skeletons and ids.numel() and int(ids.max().item()) > 2 ** 31 - 1:
+            raise ValueError(f"--save-skeletons writes int32 labels and {args.mask} has the id {int(ids.max().item())}, "
+                             "which does not fit; renumber the mask, or use --skeleton alone")
+        graph, nodes, branch_table, points, owner = instance_skeleton_branches(dev_mask, rows, boxes, skeleton=saved)[1:]
+        branch_tables = (nodes, branch_table)
+        volume = [points_volume(points, graph, mask.shape[-3:])]
+    elif args.skeleton:
         if args.save_skeletons and ids.numel() and int(ids.max().item()) > 2 ** 31 - 1:
             raise ValueError(f"--save-skeletons writes int32 labels and {args.mask} has the id {int(ids.max().item())}, "
                              "which does not fit; renumber the mask, or use --skeleton alone")
@@ -973,11 +1200,20 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
             ring = _intensity_ring(dev_mask, dev_image, args.intensity_ring, spacing, rows)[0]
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
                       max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table,
-                      contact_table, intensity, ring)
+                      contact_table, intensity, ring, branch_tables)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
     print(f"File Written: {out_path}")
+    if args.branches:
+        keep = (sums[:, 0] >= args.min_voxels).cpu().tolist()
+        radius = branch_radii(branch_table, points, owner, dist2) if args.thickness else None
+        for suffix, body in (("branches", format_branches_csv(args.mask, ids, nodes, branch_table, spacing, keep, radius)),
+                             ("nodes", format_nodes_csv(args.mask, ids, nodes, keep))):
+            path = f"{os.path.splitext(args.mask)[0]}_{suffix}.csv"
+            with open(path, "w") as file:
+                file.write(body)
+            print(f"File Written: {path}")
     if args.contacts:
         face_area = derive(sums.cpu(), boxes.cpu(), tuple(mask.shape[-3:]), spacing)["face_area"]
         contacts_path = f"{os.path.splitext(args.mask)[0]}_contacts.csv"

@@ -12,6 +12,7 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 ``instance_meshes`` writes those meshes out: vertices and faces of every instance from a count and an emit pass
 (DESIGN.md §24).
 ``instance_skeleton_graph`` thins every instance in its box and reads the skeletons as graphs.
+``instance_skeleton_branches`` traces them into node and branch tables, or traces saved skeletons.
 ``instance_thickness`` is the exact distance transform of every instance and its maximum per instance.
 ``instance_local_thickness`` is the local thickness of every instance voxel and its distribution per instance
 (DESIGN.md §28).
@@ -672,6 +673,28 @@ def _skeleton_batches(boxes: np.ndarray, budget_bytes: int):
     return out
 
 
+def _thinning_boxes(m: "_Rows", boxes):
+    """``(boxes (N, 6) int32 [x0, x1 + 1) on the host, values (N) int32)`` for the thinning of every instance of ``m``:
+    the inclusive boxes of ``instance_sums`` (computed when ``boxes`` is ``None``) opened by one, refused with
+    ``ValueError`` and the instance's id where the library would refuse the crop, and the value ``m.a`` holds per row."""
+    ids, N = m.ids, m.N
+    if boxes is None:
+        boxes = instance_sums(m.x, m.pair)[2]
+    b = boxes.cpu().numpy().astype(np.int64).reshape(N, N_BOX)
+    b[:, 3:] += 1                                            # inclusive -> [x0, x1 + 1)
+    ext = b[:, 3:] - b[:, :3]
+    words = (ext[:, 0] + 2) * (ext[:, 1] + 2) * ((ext[:, 2] + 2 + 31) >> 5)
+    refused = np.flatnonzero((ext.prod(1) >= 2 ** 30) | (words * 6 >= 2 ** 31))     # the guard of sk_skeletonize
+    if refused.size:
+        i = int(refused[0])
+        raise ValueError(f"instance {int(ids[i].item())} has a box of {tuple(int(v) for v in ext[i])} voxels, too large "
+                         "to thin: a crop must stay below 2^30 voxels (and 2^31 / 6 words of padded bit plane)")
+    b = np.ascontiguousarray(b.astype(np.int32))
+    values = m.values().to(torch.int32).cpu().numpy()
+    assert values.shape[0] == N
+    return b, values
+
+
 def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int = SKELETON_BUDGET,
                             want_volume: bool = False):
     """(ids (N) int64 ascending, graph (N, 12) int64[, skeleton (X, Y, Z) int32]) of the positive ids of an (X, Y, Z)
@@ -694,20 +717,7 @@ def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int 
     if m.empty:
         out = (ids, torch.empty((0, N_GRAPH), dtype=torch.int64, device=dev))
         return out + (volume,) if want_volume else out
-    if boxes is None:
-        boxes = instance_sums(m.x, m.pair)[2]
-    b = boxes.cpu().numpy().astype(np.int64).reshape(N, N_BOX)
-    b[:, 3:] += 1                                            # inclusive -> [x0, x1 + 1)
-    ext = b[:, 3:] - b[:, :3]
-    words = (ext[:, 0] + 2) * (ext[:, 1] + 2) * ((ext[:, 2] + 2 + 31) >> 5)
-    refused = np.flatnonzero((ext.prod(1) >= 2 ** 30) | (words * 6 >= 2 ** 31))     # the guard of sk_skeletonize
-    if refused.size:
-        i = int(refused[0])
-        raise ValueError(f"instance {int(ids[i].item())} has a box of {tuple(int(v) for v in ext[i])} voxels, too large "
-                         "to thin: a crop must stay below 2^30 voxels (and 2^31 / 6 words of padded bit plane)")
-    b = np.ascontiguousarray(b.astype(np.int32))
-    values = m.values().to(torch.int32).cpu().numpy()
-    assert values.shape[0] == N
+    b, values = _thinning_boxes(m, boxes)
     graph = torch.empty((N, N_GRAPH), dtype=torch.int64, device=dev)
     for first, last in _skeleton_batches(b, int(budget_bytes)):
         g, counts, points = skeleton_graph(a, values[first:last], b[first:last], want_points=want_volume)
@@ -718,6 +728,62 @@ def instance_skeleton_graph(x: Tensor, rows=None, boxes=None, budget_bytes: int 
             p = points.long() + torch.from_numpy(b[first:last, :3]).to(dev).long()[row - first]
             volume[p[:, 0], p[:, 1], p[:, 2]] = (row + 1).to(torch.int32)
     return (ids, graph, volume) if want_volume else (ids, graph)
+
+
+N_NODE, N_BRANCH = 8, 18     # int32 values per row of the node and branch tables (lib/morphology.py checks the library's)
+
+
+def instance_skeleton_branches(x: Tensor, rows=None, boxes=None, budget_bytes: int = SKELETON_BUDGET, skeleton=None):
+    """``(ids, graph, nodes, branches, points, owner)`` of the positive ids of an (X, Y, Z) integer device tensor: every
+    instance thinned as in ``instance_skeleton_graph`` and its skeleton traced into nodes and branches
+    (``lib.morphology.skeleton_branches``; include/skoots_hip.h states the definitions).
+
+    ``ids`` (N) int64 ascending and ``graph`` (N, 12) int64 are those of ``instance_skeleton_graph``.  ``nodes`` (Nn, 8)
+    and ``branches`` (Nb, 18) int32 are the library's tables with column 0 the instance's index into ``ids`` and the
+    node rows of a branch counted over the whole table; ``points`` (P, 3) int32 the skeleton voxels in volume
+    coordinates, instance by instance in (x, y, z) order, and ``owner`` (P) int32 a chain voxel's branch row or -1 - the
+    node row of a node voxel.  All device tensors.  The instances go in the batches of ``instance_skeleton_graph``; rows
+    are rebased across them, so the result does not depend on ``budget_bytes``.
+
+    ``skeleton`` is an (X, Y, Z) integer device volume that holds an instance's id on its skeleton voxels and 0
+    elsewhere, the kind ``--save-skeletons`` writes: it is traced as it is, inside every instance's box, and nothing is
+    thinned (thinning is the slow part).  Ids that ``x`` does not have are ignored."""
+    from ..lib.morphology import skeleton_branches
+    m = _Rows(x, rows, check_shape)
+    a, ids, N, dev = m.a, m.ids, m.N, m.dev
+    empty = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    if m.empty:
+        return (ids, torch.empty((0, N_GRAPH), dtype=torch.int64, device=dev), empty(0, N_NODE), empty(0, N_BRANCH),
+                empty(0, 3), empty(0))
+    b, values = _thinning_boxes(m, boxes)
+    if skeleton is not None:
+        skeleton = _as_volume(skeleton, "skeleton")
+        if tuple(skeleton.shape) != m.shape or skeleton.device != dev:
+            raise ValueError(f"skeleton must be a {m.shape} volume on {dev}, got shape {tuple(skeleton.shape)} on "
+                             f"{skeleton.device}")
+        # into the values of `a`: the id itself, or its row where _id_rows relabelled
+        at = torch.searchsorted(ids, skeleton.to(torch.int64).clamp(min=0)).clamp_(max=N - 1)
+        a = torch.where(ids[at] == skeleton, torch.from_numpy(values).to(dev)[at], 0).to(torch.int32).contiguous()
+    graph = torch.empty((N, N_GRAPH), dtype=torch.int64, device=dev)
+    parts = ([], [], [], [])
+    n_nodes = n_branches = 0
+    for first, last in _skeleton_batches(b, int(budget_bytes)):
+        g, counts, points, nodes, branches, owner = skeleton_branches(a, values[first:last], b[first:last],
+                                                                      thin=skeleton is None)
+        graph[first:last] = g
+        nodes[:, 0] += first
+        branches[:, 0] += first
+        branches[:, 1:3] += n_nodes
+        owner = torch.where(owner >= 0, owner + n_branches, owner - n_nodes)
+        which = torch.repeat_interleave(torch.arange(last - first, device=dev), torch.from_numpy(counts).to(dev))
+        points = points + torch.from_numpy(b[first:last, :3]).to(dev)[which]
+        n_nodes, n_branches = n_nodes + int(nodes.shape[0]), n_branches + int(branches.shape[0])
+        for part, t in zip(parts, (nodes, branches, points, owner)):
+            part.append(t)
+    if max(n_nodes, n_branches) >= 2 ** 31:
+        raise ValueError(f"{n_nodes} nodes and {n_branches} branches: rows are int32")
+    nodes, branches, points, owner = (torch.cat(part) for part in parts)
+    return ids, graph, nodes, branches, points, owner
 
 
 def instance_thickness(x: Tensor, spacing=(1.0, 1.0, 1.0), closed: bool = False, rows=None, skeleton=None):

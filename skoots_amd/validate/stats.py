@@ -20,6 +20,9 @@ path of ``compare.stats_per_instance(thickness=...)``.
 ``get_local_thickness`` is the mask's local-thickness map, the radius of the largest ball inside the mask that holds the
 voxel, on the path of ``compare.stats_per_instance(local_thickness=...)``.
 
+``get_branches`` is the mask's skeleton traced into nodes and branches, on the path of
+``compare.stats_per_instance(branches=True)``.
+
 ``get_intensity`` is the mean of an image under every instance of a mask, on the path of
 ``compare.stats_per_instance(image=...)``.
 """
@@ -30,8 +33,9 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor
 
-from .compare import _spacing, mesh_area, skeleton_columns, thickness_columns
-from .lib import (instance_intensity, instance_local_thickness, instance_mesh_cells, instance_meshes, instance_skeleton_graph, instance_sums,
+from .compare import _spacing, branch_columns, branch_lengths, mesh_area, skeleton_columns, thickness_columns
+from .lib import (instance_intensity, instance_local_thickness, instance_mesh_cells, instance_meshes, instance_skeleton_branches,
+                  instance_skeleton_graph, instance_sums,
                   instance_thickness)
 
 
@@ -99,6 +103,22 @@ def get_skeleton_length(x: Tensor, spacing: Union[List[float], Tensor]) -> Tenso
     _, graph = instance_skeleton_graph((x > 0).to(torch.int32))
     length = skeleton_columns(graph, spacing)["skeleton_length"]      # checks the spacing, also for an empty mask
     return (length[0] if length.numel() else torch.zeros((), dtype=torch.float64)).to(x.device)
+
+
+def get_branches(x: Tensor, spacing: Union[List[float], Tensor]):
+    """The skeleton of ``x > 0`` (one binary object, thinned as in ``get_skeleton_length``) traced into nodes and
+    branches: a dict with ``nodes`` (Nn, 8) and ``branches`` (Nb, 18) int32 on x's device (``lib.instance_skeleton_branches``
+    names the columns), ``lengths`` (Nb) float64, the length of every branch at the voxel spacing ``spacing``, and the
+    columns of ``compare.branch_columns`` as Python numbers: ``graph_components``, ``graph_endpoints``,
+    ``graph_junctions``, ``graph_branches``, ``graph_rings``, ``graph_corner_loops``, ``graph_cycles``,
+    ``graph_length``, ``branch_length_mean``, ``longest_branch``.  A mask without foreground gives empty tables and
+    zeros."""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise ValueError("x must be a tensor on the MI355X: the measurement is a HIP kernel and has no CPU fallback")
+    _, _, nodes, branches, _, _ = instance_skeleton_branches((x > 0).to(torch.int32))
+    out = {k: v[0].item() for k, v in branch_columns(nodes, branches, 1, spacing).items()}
+    out.update(nodes=nodes, branches=branches, lengths=branch_lengths(branches, spacing).to(x.device))
+    return out
 
 
 def get_inscribed_radius(x: Tensor, spacing: Union[List[float], Tensor], closed: bool = False) -> Tensor:

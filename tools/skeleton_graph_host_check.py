@@ -143,13 +143,13 @@ int main(int argc, char** argv) {   // lab.bin X Y Z ids.bin boxes.bin n graph.b
 """
 
 
-def build(workdir):
+def build(workdir, main=MAIN):
     with open(os.path.join(ROOT, "skoots_amd", "csrc", "skeletonize.hip")) as f:
         text = f.read()
     text = text.replace('#include "common.h"', '#include "shim.h"')
     text, n = re.subn(r"(\w+_kernel)<<<n, kThreads, [^>]*>>>\(", r"LAUNCH(\1, n, ", text)
-    if n != 3:
-        raise SystemExit(f"skeletonize.hip: expected 3 launches, found {n}: the shim needs an update")
+    if n != 6:
+        raise SystemExit(f"skeletonize.hip: expected 6 launches, found {n}: the shim needs an update")
     text, n = re.subn(r"extern __shared__ __attribute__\(\(aligned\(16\)\)\) uint32_t lds_planes\[\];",
                       "static uint32_t lds_planes[kLdsBytes / 4];", text)
     if n != 1:
@@ -157,7 +157,7 @@ def build(workdir):
     with open(os.path.join(workdir, "shim.h"), "w") as f:
         f.write(SHIM)
     with open(os.path.join(workdir, "skeletonize_host.cpp"), "w") as f:
-        f.write(text + MAIN)
+        f.write(text + main)
     clang = os.environ.get("CXX_HOST", "/opt/rocm/lib/llvm/bin/clang++")
     exe = os.path.join(workdir, "skeletonize_host")
     subprocess.check_call([clang, "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined",
