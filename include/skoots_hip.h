@@ -1184,6 +1184,50 @@ int sk_apply_piece_lut(const int32_t* piece, const int32_t* lut, int n_lut, int3
                        void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Geodesic assignment (ABI 27; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* What utils/split.py cuts a fused instance with.  Definition:
+ *   labels and seeds are (X, Y, Z) int32 volumes, Z fastest; costs = (cx, cy, cz) are integers in 1..255.
+ *   A path is a chain of 6-neighbours that all hold the same positive `labels` value.  Its cost is the sum of its steps,
+ *   cx for a step along x, cy along y, cz along z.
+ *   For every voxel v with labels[v] > 0, cost[v] is the smallest path cost to v from any voxel s that holds a seed
+ *   (seeds[s] > 0), and owner[v] the smallest `seeds` value among the seeds that attain that cost.
+ *   A voxel that is itself a seed has cost 0.
+ *   A voxel that no seed of its own value reaches has owner = 0 and cost = -1.  So does the background (and a seed that
+ *   lies on the background seeds nothing).
+ *   max_cost (-1 = none): a voxel further away than max_cost counts as unreached.
+ * This is the unique fixed point of key(v) = min(own seed, min over same-valued 6-neighbours u of key(u) + step) over the
+ * pair (cost, seed) compared lexicographically; adding to the cost alone keeps that order, so the result does not depend
+ * on the order of execution and is the same on every run.
+ *
+ * The state is one 64-bit key per voxel, cost << 32 | seed, all ones for "none", in TWO buffers of X Y Z words: a round
+ * reads one and writes the other, so a key is never read while it is written.  flags: 2 * sk_geodesic_tiles(X, Y, Z)
+ * int32 ("this tile changed in the round before", two alternating copies; a tile whose own flag and whose six face
+ * neighbours' flags are clear leaves at once).
+ *   sk_geodesic_init    keys <- the seeds, both copies of the flags, *error <- 0, or 1 when either volume holds a negative
+ *                       value (device word; the caller refuses the result);
+ *   sk_geodesic_rounds  rounds first_round .. first_round + n_rounds - 1, one launch each, 1 <= n_rounds <=
+ *                       sk_geodesic_max_rounds(); an even round reads keys_a and writes keys_b, an odd one the other way,
+ *                       so first_round continues where the call before stopped (0 after init, with the seeds in
+ *                       keys_a).  changed[k] (device, n_rounds int32, zeroed by the call) <- the tiles round
+ *                       first_round + k lowered a key in.  Once a round has changed nothing both buffers hold the
+ *                       answer and further rounds change nothing.  The caller loops: a round settles at least one more
+ *                       voxel for good, so X Y Z + 1 rounds always suffice; the tiles a shortest path crosses, re-entries
+ *                       counted, are what it takes.
+ *   sk_geodesic_finish  keys -> owner and cost as defined above.
+ * Refused before anything is launched (SK_ERR_ARG): extents not positive, X Y Z >= 2^31, a cost outside 1..255,
+ * max(costs) X Y Z >= 2^31 (every cost stays an int32), max_cost < -1, NULL or misaligned pointers, keys_a == keys_b.
+ * Stream-ordered, no allocation, no synchronisation; no workgroup waits for another. */
+int sk_geodesic_tiles(int X, int Y, int Z);
+int sk_geodesic_max_rounds(void);
+int sk_geodesic_init(const int32_t* labels, const int32_t* seeds, int X, int Y, int Z, uint64_t* keys, int32_t* flags,
+                     int32_t* error, void* stream);
+int sk_geodesic_rounds(const int32_t* labels, int X, int Y, int Z, int cx, int cy, int cz, int64_t max_cost, uint64_t* keys_a,
+                       uint64_t* keys_b, int32_t* flags, int first_round, int n_rounds, int32_t* changed, void* stream);
+int sk_geodesic_finish(const uint64_t* keys, int64_t n, int32_t* owner, int32_t* cost, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Nearest-instance transform (ABI 21; no reference counterpart)
  * ------------------------------------------------------------------------ */
 

@@ -230,6 +230,11 @@ _SIGS = {
     "sk_component_table_row_values": (i32, []),
     "sk_component_table": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "sk_apply_piece_lut": (i32, [vp, vp, i32, vp, i64, i32, vp]),
+    "sk_geodesic_tiles": (i32, [i32, i32, i32]),
+    "sk_geodesic_max_rounds": (i32, []),
+    "sk_geodesic_init": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "sk_geodesic_rounds": (i32, [vp, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, i32, i32, vp, vp]),
+    "sk_geodesic_finish": (i32, [vp, i64, vp, vp, vp]),
     "sk_nearest_label_pass": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
     "sk_nearest_label": (i32, [vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp,
                                vp, vp, vp]),

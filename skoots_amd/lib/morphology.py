@@ -6,7 +6,8 @@ skeletons read as graphs (``skeleton_graph``) and traced i
 transform of every instance of a label volume, which the reference does not have, and
 ``label_components`` the connected pieces of every instance at once, which it does not have
 either, nor ``nearest_label``, the nearest instance of every voxel and its distance, nor
-``local_thickness``, the radius of the largest ball inside the instance that holds the voxel."""
+``local_thickness``, the radius of the largest ball inside the instance that holds the voxel, nor
+``geodesic_assign``, the nearest seed of every voxel along paths inside its instance."""
 from __future__ import annotations
 
 import ctypes as C
@@ -445,6 +446,135 @@ def label_components(labels: Tensor, connectivity: int = 6, background: bool = F
         for col in (0, 4, 5):
             table[:, col] = back[table[:, col]]
     return piece, table
+
+
+GEODESIC_TILE = (4, 8, 64)  # the workgroup's tile of sk_geodesic_rounds
+GEODESIC_BATCH = 8          # rounds launched between two looks at the device's counters
+_INT32_MAX = 2 ** 31 - 1
+
+
+def geodesic_costs(costs) -> Tuple[int, int, int]:
+    """(cx, cy, cz) of ``geodesic_assign``: three integers in 1..255."""
+    try:
+        c = tuple(costs.detach().cpu().tolist() if isinstance(costs, Tensor) else costs)
+    except TypeError:
+        c = ()
+    if len(c) != 3 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and 1 <= v <= 255
+                              for v in c):
+        raise ValueError(f"costs must be three integers in 1..255 (x, y, z), got {costs!r}")
+    return tuple(int(v) for v in c)
+
+
+def geodesic_max_cost(max_cost) -> int:
+    """``max_cost`` of ``sk_geodesic_rounds``: -1 for ``None``, else a non-negative integer (above int32: no limit)."""
+    if max_cost is None:
+        return -1
+    if isinstance(max_cost, (bool, np.bool_)) or not isinstance(max_cost, (int, np.integer)) or max_cost < 0:
+        raise ValueError(f"max_cost must be None or a non-negative integer, got {max_cost!r}")
+    return min(int(max_cost), _INT32_MAX)
+
+
+def check_geodesic_shape(shape, costs=(1, 1, 1)) -> None:
+    """The library's guard, applied before anything touches the device: voxel indices and path costs stay in int32."""
+    X, Y, Z = (int(v) for v in shape)
+    if X * Y * Z >= 2 ** 31 or max(costs) * X * Y * Z >= 2 ** 31:
+        raise ValueError(f"a volume of shape {(X, Y, Z)} at costs {tuple(costs)} is too large for the geodesic assignment: "
+                         "max(costs)*X*Y*Z must stay below 2^31, the cost of a path is an int32")
+
+
+def geodesic_tiles(shape) -> int:
+    """The tiles of ``GEODESIC_TILE`` that cover a volume: the workgroups of one round."""
+    return int(np.prod([-(-int(n) // t) for n, t in zip(shape, GEODESIC_TILE)]))
+
+
+def geodesic_round_bound(shape) -> int:
+    """Rounds that always suffice: ``X Y Z + 1``.  Every round before the last settles for good at least the unsettled
+    voxel with the smallest true key (its predecessor on a shortest path has a smaller key and is settled), so the
+    voxels bound the rounds that change something, and one more finds nothing to change.  The rounds a volume really
+    takes are the tiles its longest shortest path crosses, re-entries counted."""
+    return int(np.prod([int(n) for n in shape])) + 1
+
+
+def geodesic_assign(labels: Tensor, seeds: Tensor, costs=(1, 1, 1), max_cost=None, rows=None,
+                    stats=None) -> Tuple[Tensor, Tensor]:
+    """Hands every voxel of an instance to the seed that is nearest along paths inside the instance:
+    ``(owner, cost)``, both (X, Y, Z) int32 on the device (the reference has no counterpart).
+
+    ``labels`` and ``seeds`` are integer device tensors of one shape, (X, Y, Z) or (1, X, Y, Z); ``costs = (cx, cy, cz)``
+    are integers in 1..255.  A path is a chain of 6-neighbours that all hold the same positive ``labels`` value; its cost
+    is the sum of its steps, ``cx`` for a step along x, and so on.  For every voxel v with ``labels[v] > 0``, ``cost[v]``
+    is the smallest path cost to v from any voxel that holds a seed (``seeds > 0``), and ``owner[v]`` the smallest
+    ``seeds`` value among the seeds that attain it.  A seed voxel has cost 0.  A voxel that no seed of its own value
+    reaches has ``owner = 0`` and ``cost = -1``, and so has the background.  With ``max_cost`` (a non-negative integer) a
+    voxel further away counts as unreached.  Each voxel has a neighbour of the same owner one step nearer, so the voxels
+    an owner gets inside an instance are one 6-connected piece whenever its seed voxels there are.
+
+    The numbers are exact and the same on every run, whatever the order of execution: include/skoots_hip.h has the
+    fixed-point form.  Negative values in either volume, ``seeds`` beyond int32 and ``max(costs)*X*Y*Z >= 2^31`` raise
+    ``ValueError`` before a kernel runs.  An empty volume, one without a positive label and one without a seed give
+    ``owner = 0`` and ``cost = -1`` everywhere.  ``rows`` is ``validate.lib.id_rows(labels)`` when the caller already has
+    it; only which voxels hold the same value matters, so sparse or huge ids go through its relabelled volume.
+
+    The host launches rounds in batches of ``GEODESIC_BATCH`` and reads the batch's counters once; it stops after a round
+    that changed nothing and raises ``SkootsHipError`` -- never a partial result -- should ``geodesic_round_bound``
+    rounds not suffice.  ``stats`` (a dict, optional) receives ``rounds`` (the rounds that changed a key), ``launched``,
+    ``bound`` and ``tiles``."""
+    from ..validate.lib import _Rows, _as_volume
+    costs = geodesic_costs(costs)
+    limit = geodesic_max_cost(max_cost)
+    m = _Rows(labels, rows, lambda shape: check_geodesic_shape(shape, costs), "labels", nonnegative=True)
+    s = _as_volume(seeds, "seeds")
+    if tuple(s.shape) != m.shape or s.device != m.dev:
+        raise ValueError(f"seeds must have the shape {m.shape} of labels and live on its device, got {tuple(s.shape)} on "
+                         f"{s.device}")
+    lo, hi = (int(s.min().item()), int(s.max().item())) if s.numel() else (0, 0)
+    if lo < 0 or hi > _INT32_MAX:
+        raise ValueError(f"seeds must lie in 0..2^31 - 1 (owners are int32), got values from {lo} to {hi}")
+    X, Y, Z = m.shape
+    dev = m.dev
+    owner = torch.zeros((X, Y, Z), dtype=torch.int32, device=dev)
+    cost = torch.full((X, Y, Z), -1, dtype=torch.int32, device=dev)
+    info = dict(rounds=0, launched=0, bound=geodesic_round_bound(m.shape), tiles=geodesic_tiles(m.shape))
+    if stats is not None:
+        stats.update(info)
+    if m.empty or owner.numel() == 0 or hi == 0:
+        return owner, cost
+    s = s.to(torch.int32).contiguous()
+    n = owner.numel()
+    tiles = int(_ffi.lib.sk_geodesic_tiles(X, Y, Z))
+    if tiles != info["tiles"]:
+        raise _ffi.SkootsHipError(f"sk_geodesic_tiles: {tiles} tiles, expected {info['tiles']}: " + _ffi.last_error())
+    batch = min(GEODESIC_BATCH, int(_ffi.lib.sk_geodesic_max_rounds()))
+    keys = torch.empty((2, n), dtype=torch.int64, device=dev)
+    flags = torch.empty(2 * tiles, dtype=torch.int32, device=dev)
+    words = torch.empty(1 + batch, dtype=torch.int32, device=dev)           # the error word, then a counter per round
+    stream = _ffi.stream_ptr(dev)
+    _ffi.check(_ffi.lib.sk_geodesic_init(_ffi.ptr(m.a), _ffi.ptr(s), X, Y, Z, _ffi.ptr(keys[0]), _ffi.ptr(flags),
+                                         _ffi.ptr(words), stream))
+    launched, rounds, done = 0, 0, False
+    while not done and launched < info["bound"]:
+        k = min(batch, info["bound"] - launched)
+        _ffi.check(_ffi.lib.sk_geodesic_rounds(_ffi.ptr(m.a), X, Y, Z, *costs, limit, _ffi.ptr(keys[0]), _ffi.ptr(keys[1]),
+                                               _ffi.ptr(flags), launched, k, _ffi.ptr(words[1:]), stream))
+        host = words.cpu().tolist()                                          # the one read-back of the batch
+        if host[0]:
+            raise ValueError("labels or seeds hold a negative value: ids are positive and 0 is the background")
+        launched += k
+        for c in host[1:1 + k]:
+            if c == 0:
+                done = True
+                break
+            rounds += 1
+    info.update(rounds=rounds, launched=launched)
+    if stats is not None:
+        stats.update(info)
+    if not done:
+        raise _ffi.SkootsHipError(f"geodesic_assign: {launched} rounds and keys still fall; the bound is "
+                                  f"{info['bound']}.  No result is returned")
+    # round r wrote keys[1] when r is even; after a round without a change both copies hold the answer
+    final = keys[1 if (launched - 1) % 2 == 0 else 0]
+    _ffi.check(_ffi.lib.sk_geodesic_finish(_ffi.ptr(final), n, _ffi.ptr(owner), _ffi.ptr(cost), stream))
+    return owner, cost
 
 
 def skeletonize(image: Tensor) -> Tensor:

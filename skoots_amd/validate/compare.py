@@ -83,6 +83,7 @@ MESH_COLUMNS = "mesh_vertices,mesh_triangles"            # appended with --mesh
 MESH_CLOSED_COLUMNS = "euler_characteristic"             # ... and behind them with --mesh closed
 MESH_MODES = (None, "open", "closed")
 PIECES_COLUMNS = "pieces,largest_piece_voxels"           # appended with --pieces
+CORES_COLUMNS = "cores"                                  # appended with --cores
 PIECES_MODES = (None, 6, 18, 26)
 LOCAL_THICKNESS_COLUMNS = "local_radius_mean,local_radius_std,local_radius_min"  # appended with --local-thickness
 CONTACT_COLUMNS = "neighbours,contact_area,contact_fraction,largest_contact_id,largest_contact_area"  # --contacts
@@ -463,6 +464,27 @@ def pieces_columns(table: Tensor, ids) -> Dict[str, Tensor]:
     return {"pieces": torch.from_numpy(count), "largest_piece_voxels": torch.from_numpy(largest)}
 
 
+def cores_columns(table: Tensor, ids) -> Dict[str, Tensor]:
+    """The column that ``stats_per_instance(cores=R)`` adds, from the (P, 6) table of ``utils.split.core_pieces``:
+    ``cores``, the 6-connected pieces that remain of the id at depth R.  An id with two or more is what
+    ``utils.split.split`` cuts at that radius; one with none is thinner than R everywhere."""
+    t = table.cpu().numpy() if isinstance(table, Tensor) else np.asarray(table)
+    ids = np.asarray(ids.cpu() if isinstance(ids, Tensor) else ids, dtype=np.int64).reshape(-1)
+    count = np.zeros(ids.size, np.int64)
+    if t.size:
+        np.add.at(count, np.searchsorted(ids, t[:, 0].astype(np.int64)), 1)
+    return {"cores": torch.from_numpy(count)}
+
+
+def _cores_radius(cores):
+    if cores is None:
+        return None
+    if isinstance(cores, (bool, np.bool_)) or not isinstance(cores, (int, float, np.integer, np.floating)) \
+            or not 0 <= float(cores) < float("inf"):
+        raise ValueError(f"cores must be None or a non-negative finite radius, got {cores!r}")
+    return float(cores)
+
+
 def _contact_table(table) -> np.ndarray:
     t = table.cpu().numpy() if isinstance(table, Tensor) else np.asarray(table)
     return t.astype(np.int64).reshape(-1, 9) if t.size else np.zeros((0, 9), np.int64)
@@ -639,7 +661,7 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
                        mesh: Optional[str] = None, pieces: Optional[int] = None,
                        local_thickness: Optional[str] = None, contacts: Optional[int] = None,
                        image: Optional[Tensor] = None, intensity_ring=None, branches: bool = False,
-                       skeleton_volume: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                       skeleton_volume: Optional[Tensor] = None, cores=None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -702,7 +724,13 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     and ``skeleton_owner`` (P) int32, and the columns of ``branch_columns``: ``graph_components``, ``graph_endpoints``,
     ``graph_junctions``, ``graph_branches``, ``graph_rings``, ``graph_corner_loops``, ``graph_cycles``,
     ``graph_length``, ``branch_length_mean``, ``longest_branch``.  ``skeleton_volume`` (an integer device volume with an
-    instance's id on its skeleton voxels, what ``--save-skeletons`` writes) is traced instead of thinning anything."""
+    instance's id on its skeleton voxels, what ``--save-skeletons`` writes) is traced instead of thinning anything.
+
+    ``cores=R`` (a radius in the units of ``anisotropy``) adds ``cores`` (int64): the 6-connected pieces that remain of
+    every id at depth R, steps 1 to 3 of ``utils.split.split`` (``utils.split.core_pieces``, ``cores_columns``, DESIGN.md
+    §33).  An id with two or more is what ``split`` would cut at that radius.  The depth is that of ``thickness`` when
+    that names "closed", else open."""
+    cores = _cores_radius(cores)
     if skeleton_volume is not None and not branches:
         raise ValueError("skeleton_volume is what branches=True traces: it needs branches")
     if intensity_ring is not None and image is None:
@@ -774,6 +802,10 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
             ring = _intensity_ring(x, image, intensity_ring, spacing, rows)[0]
             out["ring_moments"] = ring
             out.update({k: v.to(sums.device) for k, v in ring_columns(ring, moments).items()})
+    if cores is not None:
+        from ..utils.split import core_pieces
+        core_table = core_pieces(rows[0], cores, spacing, thickness == "closed", rows)[1]
+        out.update({k: v.to(sums.device) for k, v in cores_columns(core_table, ids).items()})
     return out
 
 
@@ -908,7 +940,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
                mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None,
-               contact_table=None, intensity=None, ring=None, branch_tables=None) -> str:
+               contact_table=None, intensity=None, ring=None, branch_tables=None, core_table=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -931,7 +963,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     once more: floats with ``repr`` (``nan`` prints as ``nan``), integers as integers.  With ``branch_tables`` (the
     ``(nodes, branches)`` of ``instance_skeleton_branches``) the columns of ``branch_columns`` come last of all:
     ``graph_components,graph_endpoints,graph_junctions,graph_branches,graph_rings,graph_corner_loops,graph_cycles,
-    graph_length,branch_length_mean,longest_branch``."""
+    graph_length,branch_length_mean,longest_branch``.  With ``core_table`` (the (P, 6) table of
+    ``utils.split.core_pieces``) ``cores`` comes behind even those; without it the text is byte for byte what it was."""
     if ring is not None and intensity is None:
         raise ValueError("ring comes with intensity: the contrast needs both")
     spacing = _spacing(spacing)
@@ -961,6 +994,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         d.update(ring_columns(ring, intensity[0]))
     if branch_tables is not None:
         d.update(branch_columns(*branch_tables, len(ids), spacing))
+    if core_table is not None:
+        d.update(cores_columns(core_table, ids))
     d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
@@ -972,7 +1007,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + CONTACT_COLUMNS if contact_table is not None else "") +
              ("," + INTENSITY_COLUMNS if intensity is not None else "") +
              ("," + RING_COLUMNS if ring is not None else "") +
-             ("," + BRANCH_COLUMNS if branch_tables is not None else "") + "\n"]
+             ("," + BRANCH_COLUMNS if branch_tables is not None else "") +
+             ("," + CORES_COLUMNS if core_table is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -1004,6 +1040,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         if branch_tables is not None:
             names = BRANCH_COLUMNS.split(",")
             cells += [d[k][i] for k in names[:7]] + [repr(d[k][i]) for k in names[7:]]
+        if core_table is not None:
+            cells += [d["cores"][i]]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -1067,6 +1105,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--pieces", type=int, default=None, choices=(6, 18, 26),
                         help="Append " + PIECES_COLUMNS + ": the connected pieces of every id at this connectivity and "
                              "the voxels of the largest (an id in several pieces is not one body)")
+    parser.add_argument("--cores", type=float, default=None, metavar="R",
+                        help="Append " + CORES_COLUMNS + ": the 6-connected pieces that remain of every id at depth R (in "
+                             "the units of --spacing; closed depth with --thickness closed): an id with two or more is "
+                             "what python -m skoots_amd.utils.split --radius R cuts")
     parser.add_argument("--contacts", type=int, default=None, choices=(6, 18, 26),
                         help="Append " + CONTACT_COLUMNS + ": the instances every id touches at this connectivity and the "
                              "area of the voxel faces it shares with them; also write <mask>_contacts.csv, one row per "
@@ -1113,6 +1155,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         args.iou_threshold = 0.1
     if args.image is None and (args.intensity_ring is not None or args.save_histograms):
         parser.error("--intensity-ring and --save-histograms belong to --image")
+    if args.cores is not None and not (0.0 <= args.cores < float("inf")):
+        parser.error("--cores takes a non-negative finite radius")
     if args.intensity_ring is not None and not (0.0 < args.intensity_ring < float("inf")):
         parser.error("--intensity-ring takes a positive finite distance")
     return args
@@ -1198,9 +1242,13 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         intensity = instance_intensity(dev_mask, dev_image, rows)[1:]
         if args.intensity_ring is not None:
             ring = _intensity_ring(dev_mask, dev_image, args.intensity_ring, spacing, rows)[0]
+    core_table = None
+    if args.cores is not None:
+        from ..utils.split import core_pieces
+        core_table = core_pieces(rows[0], args.cores, spacing, args.thickness == "closed", rows)[1]
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
                       max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table,
-                      contact_table, intensity, ring, branch_tables)
+                      contact_table, intensity, ring, branch_tables, core_table)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
