@@ -1329,6 +1329,40 @@ int sk_instance_contacts(const int32_t* labels, int X, int Y, int Z, const int32
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Overlaps between the instances of two masks (ABI 28; the reference declares the consumer,
+ * skoots/validate/lib.py: sparse_mask_iou, and raises NotImplementedError in it)
+ * ------------------------------------------------------------------------ */
+
+/* sk_instance_overlaps: which rows of one (X, Y, Z) int32 instance mask share voxels with which rows of another of the
+ * same shape, and how many.  Each mask has its own header as sk_instance_stats reads it -- (labels_a, lut_a, max_a, N)
+ * and (labels_b, lut_b, max_b, M); ra(v) is the row of voxel v in a (1 .. N, 0 for background: ids <= 0, ids above
+ * max_a, rows outside 1 .. N) and rb(v) its row in b (0 .. M).  rows receives one row of 3 int64 -- ra, rb, voxels --
+ * per pair (ra, rb) that at least one voxel carries, voxels being their number, in no particular order, and counts[0]
+ * the number of rows.  With background = 0 only pairs with ra >= 1 and rb >= 1 are produced; with background = 1 also
+ * the pairs with exactly one side 0.  The pair (0, 0) is never produced.  The count does not depend on the geometry:
+ * the volumes are read as one line of X Y Z voxels.
+ * The pairs are collected in an open-addressing table of `capacity` slots (a power of two) in `workspace`
+ * (sk_instance_overlaps_workspace_bytes(capacity) bytes, 0 for a capacity that is not in [1, 2^40]); rows holds
+ * capacity rows.  A key that finds no slot within a bounded number of probes is refused for the whole launch: nothing
+ * is written for it, and every refused insertion adds 1 to counts[1].  counts[1] == 0 says that rows is complete and
+ * exact, and then the set of rows is the same on every run; otherwise counts[0] + counts[1] is at least the number of
+ * distinct pairs, and the caller repeats the call with a larger table (validate/lib.py: instance_overlaps).  A refusal is
+ * never a fault.  Integer atomics only; one pass over the masks and one over the table, no workgroup waits for another.
+ * Checked before anything is launched or written (SK_ERR_ARG): extents, N, M, max_a and max_b not negative,
+ * X Y Z < 2^62, background in {0, 1}, capacity a power of two in [1, 2^40], workspace_bytes at least the query's, rows,
+ * counts and workspace not NULL and aligned to 8 bytes; then, unless the call is empty, the labels and lut of every
+ * side that has instances not NULL and aligned to 4 bytes (16-byte alignment of both labels pointers, or the same
+ * offset from it, lets the pass read 16 bytes per load; any other 4-byte alignment is read voxel by voxel).  A side
+ * without instances (N == 0 or M == 0) is all background: its labels and lut are not looked at and may be NULL.  An
+ * empty call -- X Y Z == 0, or N == 0 and M == 0, or background == 0 and either of them 0 -- writes counts = {0, 0} and
+ * returns SK_OK; no mask pointer is looked at.  sk_instance_overlaps_row_values() = 3. */
+int sk_instance_overlaps_row_values(void);
+size_t sk_instance_overlaps_workspace_bytes(int64_t capacity);
+int sk_instance_overlaps(const int32_t* labels_a, int X, int Y, int Z, const int32_t* lut_a, int max_a, int N,
+                         const int32_t* labels_b, const int32_t* lut_b, int max_b, int M, int background, int64_t* rows,
+                         int64_t capacity, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * The image under every instance (ABI 25; no reference counterpart)
  * ------------------------------------------------------------------------ */
 

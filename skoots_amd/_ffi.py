@@ -242,6 +242,9 @@ _SIGS = {
     "sk_instance_contacts_row_values": (i32, []),
     "sk_instance_contacts_workspace_bytes": (sz, [i64]),
     "sk_instance_contacts": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i64, vp, vp, sz, vp]),
+    "sk_instance_overlaps_row_values": (i32, []),
+    "sk_instance_overlaps_workspace_bytes": (sz, [i64]),
+    "sk_instance_overlaps": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp, i64, vp, vp, sz, vp]),
     "sk_instance_intensity_row_values": (i32, [i32]),
     "sk_instance_intensity": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
 }

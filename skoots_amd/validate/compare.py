@@ -50,7 +50,12 @@ than to any other (``lib.intensity_ring``): ``ring_voxels``, ``ring_mean``, ``ri
 ``compare(ground_truth, predictions)`` / ``--ground-truth GT`` matches every ground-truth instance to a predicted one
 by IoU and measures the pair: overlap, volume and centroid differences, and the distances between the two voxel
 surfaces -- Hausdorff, its 95th percentile, average symmetric surface distance, surface Dice -- from an exact
-nearest-neighbour search over all pairs at once (``sk_surface_distances``).
+nearest-neighbour search over all pairs at once (``sk_surface_distances``).  ``sparse=True`` /
+``--sparse-matching`` matches on the sparse table of overlapping pairs (``sk_instance_overlaps``) instead
+of the dense N x M matrix and returns the same.
+
+``parents=P`` / ``--parents P`` adds, for a second mask of other and larger objects, the object of P every instance
+lies in and the share of it inside: ``parent,inside_fraction``, as ``utils.relate`` decides them.
 """
 from __future__ import annotations
 
@@ -95,6 +100,7 @@ INTENSITY_COLUMNS = ("intensity_mean,intensity_std,intensity_min,intensity_max,i
 RING_COLUMNS = "ring_voxels,ring_mean,ring_std,contrast"                                  # --intensity-ring
 BRANCH_COLUMNS = ("graph_components,graph_endpoints,graph_junctions,graph_branches,graph_rings,graph_corner_loops,"
                   "graph_cycles,graph_length,branch_length_mean,longest_branch")             # appended with --branches
+PARENT_COLUMNS = "parent,inside_fraction"                                                   # appended with --parents
 BRANCH_CSV_COLUMNS = "id,branch,kind,node_a,node_b,voxels,length,chord,tortuosity,ax,ay,az,bx,by,bz"
 BRANCH_RADIUS_COLUMNS = "radius_mean,radius_min,radius_max"                               # --branches with --thickness
 NODE_CSV_COLUMNS = "id,node,type,voxels,internal_links,x,y,z,branch_ends"
@@ -661,7 +667,8 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
                        mesh: Optional[str] = None, pieces: Optional[int] = None,
                        local_thickness: Optional[str] = None, contacts: Optional[int] = None,
                        image: Optional[Tensor] = None, intensity_ring=None, branches: bool = False,
-                       skeleton_volume: Optional[Tensor] = None, cores=None) -> Dict[str, Tensor]:
+                       skeleton_volume: Optional[Tensor] = None, cores=None, parents: Optional[Tensor] = None,
+                       parent_min_fraction: float = 0.0) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -729,7 +736,12 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     ``cores=R`` (a radius in the units of ``anisotropy``) adds ``cores`` (int64): the 6-connected pieces that remain of
     every id at depth R, steps 1 to 3 of ``utils.split.split`` (``utils.split.core_pieces``, ``cores_columns``, DESIGN.md
     §33).  An id with two or more is what ``split`` would cut at that radius.  The depth is that of ``thickness`` when
-    that names "closed", else open."""
+    that names "closed", else open.
+
+    ``parents=P`` (an integer device volume of the mask's shape: a mask of other, larger objects) adds ``parent`` int64,
+    the id of P that holds most of the instance's voxels, 0 for none, and ``inside_fraction`` float64, the share of the
+    instance inside it: ``parent_id`` and ``inside_fraction`` of ``utils.relate.relate(x, P, parent_min_fraction)``
+    (DESIGN.md §34)."""
     cores = _cores_radius(cores)
     if skeleton_volume is not None and not branches:
         raise ValueError("skeleton_volume is what branches=True traces: it needs branches")
@@ -806,11 +818,15 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         from ..utils.split import core_pieces
         core_table = core_pieces(rows[0], cores, spacing, thickness == "closed", rows)[1]
         out.update({k: v.to(sums.device) for k, v in cores_columns(core_table, ids).items()})
+    if parents is not None:
+        from ..utils.relate import relate
+        child_table = relate(rows[0], parents, parent_min_fraction, spacing, rows_children=rows)[0]
+        out.update(parent=child_table["parent_id"], inside_fraction=child_table["inside_fraction"])
     return out
 
 
 def compare(ground_truth: Tensor, predictions: Tensor, anisotropy=(1.0, 1.0, 1.0), iou_threshold: float = 0.1,
-            tolerance: Optional[float] = None) -> Dict[str, Tensor]:
+            tolerance: Optional[float] = None, sparse: bool = False) -> Dict[str, Tensor]:
     """For each ground-truth instance, which predicted instance it is and how far apart their boundaries are
     (the reference's function of this name raises ``NotImplementedError``).  Both masks are device
     tensors of one shape, (X, Y, Z) or (1, X, Y, Z), of any integer dtype; ``anisotropy`` is the voxel spacing along x,
@@ -835,8 +851,14 @@ def compare(ground_truth: Tensor, predictions: Tensor, anisotropy=(1.0, 1.0, 1.0
 
     Memory: beside the two masks as int32 the call holds two int32 row volumes, and while it counts the intersections
     one more int32 volume and three bool ones -- about 15 bytes per voxel on top of the masks (``mask_iou`` adds its own
-    int32 copies while it runs)."""
-    from .lib import instance_surfaces, mask_iou, match_instances, pair_summaries, surface_distances
+    int32 copies while it runs), and ``mask_iou``'s (N + 1) x (M + 1) table, the (N, M) matrix and the (N, M) int64
+    temporaries of the matching.
+
+    ``sparse=True`` takes the IoU values, the match, ``intersection_voxels`` and ``unmatched_pred_best_iou`` from one
+    ``lib.instance_overlaps`` pass over the two masks instead: nothing of size N x M and none of the
+    volume-sized temporaries above exist, and the returned dict is the same, bit for bit."""
+    from .lib import (instance_overlaps, instance_surfaces, mask_iou, match_instances, match_instances_sparse,
+                      overlap_ious, pair_summaries, surface_distances)
     spacing = _spacing(anisotropy)
     tau = max(spacing) if tolerance is None else float(tolerance)
     if not (tau >= 0.0 and math.isfinite(tau)):
@@ -852,13 +874,17 @@ def compare(ground_truth: Tensor, predictions: Tensor, anisotropy=(1.0, 1.0, 1.0
     N, M = int(ids_g.numel()), int(ids_p.numel())
     cen_g = derive(sums_g.cpu(), boxes_g.cpu(), shape, spacing)["centroid"].numpy()
     cen_p = derive(sums_p.cpu(), boxes_p.cpu(), shape, spacing)["centroid"].numpy()
-    if N and M:
-        # every voxel's row, 1..N / 1..M and 0 for the rest; int32 indices and results: no 8-byte-per-voxel temporary
-        rg, rp = _Rows(g, (g, grows)).row_volume(), _Rows(p, (p, prows)).row_volume()
-        iou = mask_iou(rg, rp)                                          # rows ascend with the ids: the same matrix
+    if sparse:
+        pairs, values = overlap_ious(instance_overlaps(g, p, True, (g, grows), (p, prows))[2], N, M)
+        match = match_instances_sparse(pairs, values, N, M, iou_threshold)
     else:
-        iou = torch.zeros((N, M), dtype=torch.float32, device=dev)
-    match = match_instances(iou, iou_threshold)
+        if N and M:
+            # every voxel's row, 1..N / 1..M and 0 for the rest; int32 indices and results: no 8-byte-per-voxel temporary
+            rg, rp = _Rows(g, (g, grows)).row_volume(), _Rows(p, (p, prows)).row_volume()
+            iou = mask_iou(rg, rp)                                      # rows ascend with the ids: the same matrix
+        else:
+            iou = torch.zeros((N, M), dtype=torch.float32, device=dev)
+        match = match_instances(iou, iou_threshold)
     matched = match >= 0
     col = match.clamp(min=0)
     rows_m = torch.nonzero(matched)[:, 0]
@@ -866,7 +892,13 @@ def compare(ground_truth: Tensor, predictions: Tensor, anisotropy=(1.0, 1.0, 1.0
     K = int(rows_m.numel())
     zeros = torch.zeros(N, dtype=torch.int64, device=dev)
     inter = zeros.clone()
-    if K:
+    if K and sparse:                                         # the table is sorted by (ra, rb): one search per matched row
+        keys = pairs[:, 0] * (M + 1) + pairs[:, 1]
+        want = (rows_m + 1) * (M + 1) + cols_m + 1
+        at = torch.searchsorted(keys, want).clamp(max=max(int(keys.numel()) - 1, 0))
+        if keys.numel():                                     # a match at IoU 0 (a negative threshold) shares nothing
+            inter[rows_m] = torch.where(keys[at] == want, pairs[at, 2], inter.new_zeros(1))
+    elif K:
         chose = torch.cat((match.new_zeros(1), match + 1)).to(torch.int32)     # row of gt -> the row of pred it chose, or 0
         want = chose[rg]
         inter = torch.bincount(rg[(want > 0) & (rp == want)].long(), minlength=N + 1)[1:]
@@ -898,7 +930,11 @@ def compare(ground_truth: Tensor, predictions: Tensor, anisotropy=(1.0, 1.0, 1.0
             out[k][rows_m] = s[k].to(dev)
     un = torch.nonzero(chosen == 0)[:, 0]
     out["unmatched_pred_id"] = ids_p[un]
-    out["unmatched_pred_best_iou"] = (iou.max(dim=0)[0][un] if N else iou.new_zeros(int(un.numel()))).double()
+    if sparse:                                               # a column's largest value; 0 where it shares nothing
+        best = torch.zeros(M, dtype=torch.float32, device=dev).scatter_reduce_(0, pairs[:, 1] - 1, values, "amax")
+        out["unmatched_pred_best_iou"] = best[un].double()
+    else:
+        out["unmatched_pred_best_iou"] = (iou.max(dim=0)[0][un] if N else iou.new_zeros(int(un.numel()))).double()
     out["unmatched_pred_voxels"] = sums_p[un, 0]
     out["unmatched_pred_surface_voxels"] = ns_p[un]
     return out
@@ -940,7 +976,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                skeleton_graph: Optional[Tensor] = None, max_dist2: Optional[Tensor] = None,
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
                mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None,
-               contact_table=None, intensity=None, ring=None, branch_tables=None, core_table=None) -> str:
+               contact_table=None, intensity=None, ring=None, branch_tables=None, core_table=None,
+               parent_table=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -964,7 +1001,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     ``(nodes, branches)`` of ``instance_skeleton_branches``) the columns of ``branch_columns`` come last of all:
     ``graph_components,graph_endpoints,graph_junctions,graph_branches,graph_rings,graph_corner_loops,graph_cycles,
     graph_length,branch_length_mean,longest_branch``.  With ``core_table`` (the (P, 6) table of
-    ``utils.split.core_pieces``) ``cores`` comes behind even those; without it the text is byte for byte what it was."""
+    ``utils.split.core_pieces``) ``cores`` comes behind even those; without it the text is byte for byte what it was.
+    With ``parent_table`` (the ``(parent_id, inside_fraction)`` of ``utils.relate.relate``, N values each)
+    ``parent,inside_fraction`` are the last columns, under the same rule."""
     if ring is not None and intensity is None:
         raise ValueError("ring comes with intensity: the contrast needs both")
     spacing = _spacing(spacing)
@@ -996,6 +1035,12 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         d.update(branch_columns(*branch_tables, len(ids), spacing))
     if core_table is not None:
         d.update(cores_columns(core_table, ids))
+    if parent_table is not None:
+        d.update(parent=torch.as_tensor(parent_table[0]).to(torch.int64).reshape(-1),
+                 inside_fraction=torch.as_tensor(parent_table[1]).to(torch.float64).reshape(-1))
+        if d["parent"].numel() != len(ids) or d["inside_fraction"].numel() != len(ids):
+            raise ValueError(f"parent_table has {d['parent'].numel()} and {d['inside_fraction'].numel()} values for "
+                             f"{len(ids)} ids")
     d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
@@ -1008,7 +1053,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + INTENSITY_COLUMNS if intensity is not None else "") +
              ("," + RING_COLUMNS if ring is not None else "") +
              ("," + BRANCH_COLUMNS if branch_tables is not None else "") +
-             ("," + CORES_COLUMNS if core_table is not None else "") + "\n"]
+             ("," + CORES_COLUMNS if core_table is not None else "") +
+             ("," + PARENT_COLUMNS if parent_table is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -1042,6 +1088,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
             cells += [d[k][i] for k in names[:7]] + [repr(d[k][i]) for k in names[7:]]
         if core_table is not None:
             cells += [d["cores"][i]]
+        if parent_table is not None:
+            cells += [d["parent"][i], repr(d["inside_fraction"][i])]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -1134,6 +1182,17 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--tolerance", type=float, default=None, metavar="TAU",
                         help="With --ground-truth: nsd counts the surface voxels within TAU of the other surface "
                              "(default: the largest spacing component)")
+    parser.add_argument("--sparse-matching", action="store_true",
+                        help="With --ground-truth: match on the sparse table of overlapping pairs instead of the dense "
+                             "N x M IoU matrix: the same file, byte for byte, in memory that does not grow with N x M")
+    parser.add_argument("--parents", type=str, default=None, metavar="P",
+                        help="Append " + PARENT_COLUMNS + ": P (.tif or .npy of the same shape) is a mask of other, larger "
+                             "objects, such as the cells around mitochondria; the id of P that holds most of the "
+                             "instance's voxels (0: none) and the share of the instance inside it, as python -m "
+                             "skoots_amd.utils.relate decides")
+    parser.add_argument("--parent-min-fraction", type=float, default=None, metavar="F",
+                        help="With --parents: an instance with less than this share of its voxels inside its parent gets "
+                             "parent 0 (default 0)")
     parser.add_argument("--out", type=str, default=None, help="Output file (default: <mask>_instance_stats.csv)")
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
@@ -1151,6 +1210,14 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         parser.error("--mesh-ids selects the instances of --save-meshes")
     if args.ground_truth is None and (args.iou_threshold is not None or args.tolerance is not None):
         parser.error("--iou-threshold and --tolerance belong to --ground-truth")
+    if args.ground_truth is None and args.sparse_matching:
+        parser.error("--sparse-matching belongs to --ground-truth")
+    if args.parents is None and args.parent_min_fraction is not None:
+        parser.error("--parent-min-fraction belongs to --parents")
+    if args.parent_min_fraction is None:
+        args.parent_min_fraction = 0.0
+    if not 0.0 <= args.parent_min_fraction <= 1.0:
+        parser.error("--parent-min-fraction takes a share in [0, 1]")
     if args.iou_threshold is None:
         args.iou_threshold = 0.1
     if args.image is None and (args.intensity_ring is not None or args.save_histograms):
@@ -1246,9 +1313,20 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
     if args.cores is not None:
         from ..utils.split import core_pieces
         core_table = core_pieces(rows[0], args.cores, spacing, args.thickness == "closed", rows)[1]
+    parent_table = None
+    if args.parents is not None:
+        if not os.path.exists(args.parents):
+            raise RuntimeError(f"{args.parents} does not exist")
+        from ..utils.relate import relate
+        parent_mask = load_mask(args.parents)
+        if tuple(parent_mask.shape) != tuple(mask.shape):
+            raise ValueError(f"{args.parents} has the shape {tuple(parent_mask.shape)} and {args.mask} "
+                             f"{tuple(mask.shape)}: the parents of a mask have its shape")
+        child_table = relate(rows[0], parent_mask.to("cuda"), args.parent_min_fraction, spacing, rows_children=rows)[0]
+        parent_table = (child_table["parent_id"], child_table["inside_fraction"])
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
                       max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table,
-                      contact_table, intensity, ring, branch_tables, core_table)
+                      contact_table, intensity, ring, branch_tables, core_table, parent_table)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)
@@ -1314,7 +1392,8 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
         if tuple(truth.shape) != tuple(mask.shape):
             raise ValueError(f"{args.ground_truth} has the shape {tuple(truth.shape)} and {args.mask} "
                              f"{tuple(mask.shape)}: a comparison needs one shape")
-        result = compare(truth.to("cuda"), dev_mask, spacing, args.iou_threshold, args.tolerance)
+        result = compare(truth.to("cuda"), dev_mask, spacing, args.iou_threshold, args.tolerance,
+                         sparse=args.sparse_matching)
         compare_path = f"{os.path.splitext(args.mask)[0]}_compare.csv"
         with open(compare_path, "w") as file:
             file.write(format_compare_csv(args.mask, args.ground_truth, result, spacing, args.iou_threshold,

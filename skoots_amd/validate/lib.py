@@ -18,6 +18,9 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 (DESIGN.md §28).
 ``instance_contacts`` says which instances touch and across how many shared faces, edges and corners, one row per pair
 (DESIGN.md §29).
+``instance_overlaps`` says which instance of one mask shares voxels with which instance of another, one row per pair;
+``sparse_mask_iou`` is ``mask_iou`` on those pairs alone, the function the reference declares and leaves unwritten, and
+``match_instances_sparse`` is ``match_instances`` on them.
 ``instance_intensity`` reads the image under every instance -- count, sums, extrema and a 256-bin histogram -- and
 ``intensity_ring`` the image over the background around it.
 ``instance_surfaces``, ``surface_distances``, ``match_instances`` and ``pair_summaries`` are the parts of
@@ -357,6 +360,118 @@ def instance_contacts(x: Tensor, connectivity: int = 6, background: bool = False
     table = out[:stored]
     order = torch.argsort(table[:, 0] * (N + 1) + table[:, 1])     # lo, hi <= N: one int64 key
     return m.ids, table[order].contiguous()
+
+
+# ---- the instances of two masks against each other ----
+
+N_OVERLAP = 3                  # int64 values per row of sk_instance_overlaps: ra, rb, voxels
+MAX_OVERLAP_CAPACITY = 1 << 30
+
+
+def instance_overlaps(a: Tensor, b: Tensor, background: bool = False, rows_a=None, rows_b=None,
+                      capacity=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(ids_a (N) int64 ascending, ids_b (M) int64 ascending, table (P, 3) int64) of two integer device tensors of one
+    shape, (X, Y, Z) or (1, X, Y, Z): which instance of ``a`` shares voxels with which instance of ``b``, from
+    ``sk_instance_overlaps`` (include/skoots_hip.h has the definition).  A row of ``table`` is
+    ``ra, rb, voxels``: a ROW of ``ids_a`` (1 .. N), a row of ``ids_b`` (1 .. M) and the voxels that carry both.  With
+    ``background=True`` the rows with exactly one side 0, the background, are there too, so that the rows of one
+    instance sum to its voxel count; (0, 0) never is.  These are the nonzero entries of the (N + 1) x (M + 1)
+    contingency table that ``mask_iou`` keeps densely.  The table is sorted by ``(ra, rb)`` with torch, so two runs give
+    equal tensors.  ``rows_a`` / ``rows_b`` are ``id_rows(a)`` / ``id_rows(b)`` when the caller already has them.
+
+    The kernel collects the pairs in a hash table of ``capacity`` slots, a power of two; ``None`` starts at the next
+    power of two >= ``max(1024, 8 max(N, M))``, a given value is where the search STARTS.  After the launch the function
+    reads the two counters back; if insertions were refused it runs again at the next power of two >=
+    ``2 * (stored + refused)`` -- at least twice the distinct pairs, and never more than twice the
+    ``min((N + 1)(M + 1) - 1, X Y Z)`` pairs two masks can hold -- and raises ``RuntimeError`` rather than go past 2^30
+    slots.  Two masks of different shape or device raise ``ValueError``."""
+    assert _ffi.lib.sk_instance_overlaps_row_values() == N_OVERLAP
+    ma = _Rows(a, rows_a, check_voxels, name="a")
+    mb = _Rows(b, rows_b, check_voxels, name="b")
+    if ma.shape != mb.shape or ma.dev != mb.dev:
+        raise ValueError(f"a {ma.shape} on {ma.dev} and b {mb.shape} on {mb.dev} must have one shape and one device")
+    dev, N, M, (X, Y, Z) = ma.dev, ma.N, mb.N, ma.shape
+    n = X * Y * Z
+    if n == 0 or (N == 0 and M == 0) or (not background and (N == 0 or M == 0)):
+        return ma.ids, mb.ids, torch.empty((0, N_OVERLAP), dtype=torch.int64, device=dev)
+    if capacity is None:
+        capacity = _pow2_at_least(max(1024, 8 * max(N, M)))
+    capacity = int(capacity)
+    if capacity < 1 or capacity & (capacity - 1):
+        raise ValueError(f"capacity must be a power of two >= 1, got {capacity}")
+    most = min((N + 1) * (M + 1) - 1, n)                     # distinct pairs two masks can hold, background included
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    while True:
+        if capacity > MAX_OVERLAP_CAPACITY:
+            raise RuntimeError(f"instance_overlaps: the pair table would need {capacity} slots, more than "
+                               f"{MAX_OVERLAP_CAPACITY}")
+        ws_bytes = int(_ffi.lib.sk_instance_overlaps_workspace_bytes(capacity))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((capacity, N_OVERLAP), dtype=torch.int64, device=dev)
+        # a side without instances has no volume and no table here: the library reads it as background
+        ma.call(_ffi.lib.sk_instance_overlaps, _ffi.ptr(mb.a), _ffi.ptr(mb.lut), mb.max_id, M, int(bool(background)),
+                _ffi.ptr(out), capacity, _ffi.ptr(counts), _ffi.ptr(ws), ws_bytes)
+        stored, refused = (int(v) for v in counts.tolist())
+        if refused == 0:
+            break
+        del ws, out
+        capacity = max(2 * capacity, _pow2_at_least(2 * min(stored + refused, most)))
+    table = out[:stored]
+    order = torch.argsort(table[:, 0] * (M + 1) + table[:, 1])     # ra <= N, rb <= M: one int64 key
+    return ma.ids, mb.ids, table[order].contiguous()
+
+
+def overlap_ious(table: Tensor, N: int, M: int) -> Tuple[Tensor, Tensor]:
+    """(pairs (Q, 3) int64, values (Q) fp32) from the (P, 3) table of ``instance_overlaps(a, b, background=True)``: its
+    rows between two instances, in the table's order, and the IoU of each -- ``(float)inter / (float)union`` in fp32, the
+    expression of ``sk_mask_iou``'s kernel, with ``union = |a| + |b| - inter`` and the voxel counts ``|a|``, ``|b|`` the
+    table's own row and column sums (that is why it needs the background rows).  The quotient is formed on the host:
+    one correctly rounded fp32 division per pair, the same bits as the kernel's.  Host tensors in, host tensors out;
+    device tensors in, device tensors out."""
+    t = torch.as_tensor(table).to(torch.int64).reshape(-1, N_OVERLAP)
+    size_a = torch.zeros(int(N) + 1, dtype=torch.int64, device=t.device).index_add_(0, t[:, 0], t[:, 2])
+    size_b = torch.zeros(int(M) + 1, dtype=torch.int64, device=t.device).index_add_(0, t[:, 1], t[:, 2])
+    pairs = t[(t[:, 0] > 0) & (t[:, 1] > 0)]
+    inter = pairs[:, 2].cpu()
+    union = (size_a[pairs[:, 0]] + size_b[pairs[:, 1]]).cpu() - inter
+    values = inter.to(torch.float32) / union.to(torch.float32)
+    return pairs, values.to(t.device)
+
+
+def sparse_mask_iou(a: Tensor, b: Tensor) -> Tensor:
+    """``mask_iou(a, b)`` as a coalesced ``torch.sparse_coo_tensor`` of shape (N, M), fp32: one stored value per pair of
+    instances that share a voxel, and ``.to_dense()`` equal to ``mask_iou(a, b)`` bit for bit -- the function the
+    reference declares under this name and leaves unwritten (skoots/validate/lib.py:317).  One ``instance_overlaps``
+    pass with the background rows gives intersections and, as row and column sums, the voxel counts; nothing of size
+    N x M is allocated."""
+    ids_a, ids_b, table = instance_overlaps(a, b, background=True)
+    N, M = int(ids_a.numel()), int(ids_b.numel())
+    pairs, values = overlap_ious(table, N, M)
+    # sorted by (ra, rb) and distinct: coalesce() finds nothing to add up
+    return torch.sparse_coo_tensor((pairs[:, :2] - 1).t().contiguous(), values, (N, M)).coalesce()
+
+
+def match_instances_sparse(table: Tensor, iou_values: Tensor, N: int, M: int, iou_threshold: float = 0.1) -> Tensor:
+    """``match_instances`` on the pairs that exist: ``table`` (Q, >= 2) int64 holds a row 1 .. N and a row 1 .. M per
+    pair (rows with a 0, the background, are ignored; a pair appears once) and ``iou_values`` (Q) its fp32 IoU, which is
+    positive -- ``overlap_ious`` gives both.  Returns the (N) int64 result of ``match_instances(dense, iou_threshold)``
+    for the (N, M) matrix that holds these values and 0 elsewhere: per row the column (0-based) of the largest value
+    when that is > ``iou_threshold``, the lowest column on a tie, -1 otherwise.  A pure function of its tensors, on
+    their device, host tensors included; N or M may be 0."""
+    t = torch.as_tensor(table).to(torch.int64)
+    t = t.reshape(-1, t.shape[-1] if t.ndim == 2 else N_OVERLAP)
+    v = torch.as_tensor(iou_values).to(device=t.device, dtype=torch.float32).reshape(-1)
+    N, M = int(N), int(M)
+    if N == 0 or M == 0:
+        return torch.full((N,), -1, dtype=torch.int64, device=t.device)
+    keep = (t[:, 0] > 0) & (t[:, 1] > 0)
+    r, c, v = t[keep, 0] - 1, t[keep, 1] - 1, v[keep]
+    # a row without a pair is a row of zeros: its largest value is 0, first met in column 0
+    best = torch.zeros(N, dtype=torch.float32, device=t.device).scatter_reduce_(0, r, v, "amax", include_self=True)
+    first = torch.full((N,), M, dtype=torch.int64, device=t.device)
+    first.scatter_reduce_(0, r, torch.where(v == best[r], c, c.new_tensor(M)), "amin", include_self=True)
+    first = torch.where(best > 0, first, first.new_tensor(0))
+    return torch.where(best > iou_threshold, first, first.new_tensor(-1))
 
 
 # ---- the image under every instance (DESIGN.md §30) ----
