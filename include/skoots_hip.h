@@ -1363,6 +1363,62 @@ int sk_instance_overlaps(const int32_t* labels_a, int X, int Y, int Z, const int
                          int64_t capacity, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Instances within a distance of each other (ABI 29; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+/* sk_instance_proximity: which rows of one (X, Y, Z) int32 instance mask lie within a distance of which rows of
+ * another of the same shape, how close they come, and how many voxels lie that close: sk_instance_contacts (one mask,
+ * reach 1) and sk_instance_overlaps (two masks, reach 0) at reach D.  Each mask has its header as sk_instance_overlaps
+ * takes it -- (labels_a, lut_a, max_a, N) and (labels_b, lut_b, max_b, M); ra(p) in 0 .. N and rb(q) in 0 .. M are the
+ * rows, 0 the background.  wx, wy, wz are the spacing squared and limit2 is D^2, doubles as sk_nearest_label takes them.
+ * For a voxel p of a and a voxel q of b
+ *   d2(p, q) = fl(wx dx^2 + fl(wy dy^2 + wz dz^2)),   dx = px - qx, ...
+ * every square an exact integer in double, every product and sum rounded once (no fused multiply-add; w (d d)): the
+ * expression of sk_nearest_label, bit for bit.
+ * A voxel pair (p, q) COUNTS when ra(p) >= 1, rb(q) >= 1 and d2(p, q) <= limit2 (at the limit counts); with
+ * exclude_same = 1 also ra(p) != rb(q) is required -- the one-mask mode, in which labels_b may be labels_a.  Voxels
+ * outside the volume do not exist.  An overlap (p = q) counts with d2 = 0.
+ * rows receives one row of 4 int64 -- ra, rb, near_voxels, gap2_bits -- per key that has a counting pair, in no
+ * particular order, and counts[0] their number:
+ *   key (ra, rb), rb >= 1   near_voxels is the number of voxels p of ra for which SOME q of rb counts (a voxel is counted
+ *                           once per partner, however many q are in reach), gap2_bits the bit pattern of the minimum
+ *                           of d2 over the counting pairs of the key;
+ *   key (ra, 0)             the union row: near_voxels is the number of voxels of ra for which some q of ANY row counts,
+ *                           gap2_bits the minimum over all of them.
+ * One direction per call: the voxels counted are those of a; swap the masks for b's side.  gap2 is symmetric.
+ * Reach: per axis h is the largest k >= 0 with fl(w k^2) <= limit2, found by search.  The kernel stages the rows of b of
+ * a 4 x 16 x 64 tile grown by (hx, hy, hz) on all sides in LDS; a reach whose window does not fit the 160 KiB of a CU is
+ * refused with SK_ERR_ARG before anything is launched -- never truncated.  Every reach with hx, hy, hz <= 5 is taken.
+ * sk_instance_proximity_reach answers without a GPU: out_host holds 8 int32, out[0 .. 2] = hx, hy, hz (each capped at
+ * 2^26), out[3] = 1 when the kernel takes them, out[4] = the LDS bytes of one workgroup at that reach, out[5] = the
+ * workgroups one CU holds at it -- the least of what its 160 KiB of LDS, its 32 wave slots and the registers the kernel
+ * is compiled for allow -- out[6] = the threads of the workgroup launched at that reach (512 where two windows fit a
+ * CU, 1024 where one does), out[7] = 0 (out[4 .. 6] are 0 when refused); it returns SK_ERR_ARG only for weights or a
+ * limit2 that sk_instance_proximity refuses, or a NULL or unaligned out.  sk_instance_proximity_resident (needs the
+ * GPU) writes what the runtime's occupancy query says for the same kernel and dynamic LDS: the two agree (tested).
+ * The pairs are collected in an open-addressing table of `capacity` slots (a power of two) in `workspace`
+ * (sk_instance_proximity_workspace_bytes(capacity) bytes, 0 for a capacity that is not in [1, 2^40]); rows holds
+ * capacity rows.  A key that finds no slot within a bounded number of probes is refused for the whole launch: nothing
+ * is written for it, and every refused insertion adds 1 to counts[1].  counts[1] == 0 says that rows is complete and
+ * exact, and then the set of rows is the same on every run; otherwise the caller repeats the call with a larger table
+ * (validate/lib.py: instance_proximity).  A refusal is never a fault.  Integer adds, and an integer minimum on the bit
+ * pattern (non-negative doubles order as their bits, as in sk_local_thickness_paint); no workgroup waits for another.
+ * Checked before anything is launched or written (SK_ERR_ARG): extents, N, M, max_a and max_b not negative,
+ * X Y Z < 2^62, the weights finite and > 0, limit2 not NaN, >= 0 and finite, exclude_same in {0, 1}, the reach,
+ * capacity a power of two in [1, 2^40], workspace_bytes at least the query's, rows, counts and workspace not NULL and
+ * aligned to 8 bytes; then, unless the call is empty, labels and lut of both sides not NULL and aligned to 4 bytes.  An
+ * empty call -- X Y Z == 0, N == 0 or M == 0 -- writes counts = {0, 0} and returns SK_OK; no mask pointer is looked at.
+ * sk_instance_proximity_row_values() = 4. */
+int sk_instance_proximity_row_values(void);
+size_t sk_instance_proximity_workspace_bytes(int64_t capacity);
+int sk_instance_proximity_reach(double wx, double wy, double wz, double limit2, int32_t* out_host);
+int sk_instance_proximity_resident(double wx, double wy, double wz, double limit2, int32_t* workgroups_host);
+int sk_instance_proximity(const int32_t* labels_a, int X, int Y, int Z, const int32_t* lut_a, int max_a, int N,
+                          const int32_t* labels_b, const int32_t* lut_b, int max_b, int M, double wx, double wy, double wz,
+                          double limit2, int exclude_same, int64_t* rows, int64_t capacity, int64_t* counts,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * The image under every instance (ABI 25; no reference counterpart)
  * ------------------------------------------------------------------------ */
 

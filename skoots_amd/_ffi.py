@@ -245,6 +245,12 @@ _SIGS = {
     "sk_instance_overlaps_row_values": (i32, []),
     "sk_instance_overlaps_workspace_bytes": (sz, [i64]),
     "sk_instance_overlaps": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp, i64, vp, vp, sz, vp]),
+    "sk_instance_proximity_row_values": (i32, []),
+    "sk_instance_proximity_workspace_bytes": (sz, [i64]),
+    "sk_instance_proximity_reach": (i32, [C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "sk_instance_proximity_resident": (i32, [C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "sk_instance_proximity": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, i32, vp, i64, vp, vp, sz, vp]),
     "sk_instance_intensity_row_values": (i32, [i32]),
     "sk_instance_intensity": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
 }

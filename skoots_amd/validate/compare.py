@@ -56,6 +56,10 @@ of the dense N x M matrix and returns the same.
 
 ``parents=P`` / ``--parents P`` adds, for a second mask of other and larger objects, the object of P every instance
 lies in and the share of it inside: ``parent,inside_fraction``, as ``utils.relate`` decides them.
+
+``near=B | "self"`` with ``near_distance=D`` / ``--near B|self --near-distance D`` adds which instances of B -- or of the
+mask itself -- lie within D of every instance: ``near_partners,nearest_id,nearest_gap,near_voxels,near_fraction``, as
+``utils.proximity`` derives them.
 """
 from __future__ import annotations
 
@@ -101,6 +105,7 @@ RING_COLUMNS = "ring_voxels,ring_mean,ring_std,contrast"                        
 BRANCH_COLUMNS = ("graph_components,graph_endpoints,graph_junctions,graph_branches,graph_rings,graph_corner_loops,"
                   "graph_cycles,graph_length,branch_length_mean,longest_branch")             # appended with --branches
 PARENT_COLUMNS = "parent,inside_fraction"                                                   # appended with --parents
+NEAR_COLUMNS = "near_partners,nearest_id,nearest_gap,near_voxels,near_fraction"             # appended with --near
 BRANCH_CSV_COLUMNS = "id,branch,kind,node_a,node_b,voxels,length,chord,tortuosity,ax,ay,az,bx,by,bz"
 BRANCH_RADIUS_COLUMNS = "radius_mean,radius_min,radius_max"                               # --branches with --thickness
 NODE_CSV_COLUMNS = "id,node,type,voxels,internal_links,x,y,z,branch_ends"
@@ -668,7 +673,7 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
                        local_thickness: Optional[str] = None, contacts: Optional[int] = None,
                        image: Optional[Tensor] = None, intensity_ring=None, branches: bool = False,
                        skeleton_volume: Optional[Tensor] = None, cores=None, parents: Optional[Tensor] = None,
-                       parent_min_fraction: float = 0.0) -> Dict[str, Tensor]:
+                       parent_min_fraction: float = 0.0, near=None, near_distance=None) -> Dict[str, Tensor]:
     """Measures every instance of ``x``, a device tensor (X, Y, Z) or (1, X, Y, Z) of any integer dtype, in one kernel
     pass; ``anisotropy`` is the voxel spacing along x, y and z of that tensor.
 
@@ -741,7 +746,18 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
     ``parents=P`` (an integer device volume of the mask's shape: a mask of other, larger objects) adds ``parent`` int64,
     the id of P that holds most of the instance's voxels, 0 for none, and ``inside_fraction`` float64, the share of the
     instance inside it: ``parent_id`` and ``inside_fraction`` of ``utils.relate.relate(x, P, parent_min_fraction)``
-    (DESIGN.md §34)."""
+    (DESIGN.md §34).
+
+    ``near=B`` (an integer device volume of the mask's shape) or ``near="self"`` with ``near_distance=D`` (in the units
+    of ``anisotropy``) adds the columns of ``utils.proximity.proximity``'s per-instance table:
+    ``near_partners`` int64, the instances of B -- or the other instances of the mask -- within D; ``nearest_id`` int64
+    (0: none) and ``nearest_gap`` float64 (``inf``: none), the closest of them and the gap to it; ``near_voxels`` int64,
+    the instance's voxels within D of any of them, and ``near_fraction`` float64, their share.  One without the other
+    raises ``ValueError``."""
+    if (near is None) != (near_distance is None):
+        raise ValueError("near names what to measure the distance to and near_distance the distance: they come together")
+    if isinstance(near, str) and near != "self":
+        raise ValueError(f'near must be a mask or "self", got {near!r}')
     cores = _cores_radius(cores)
     if skeleton_volume is not None and not branches:
         raise ValueError("skeleton_volume is what branches=True traces: it needs branches")
@@ -822,6 +838,12 @@ def stats_per_instance(x: Tensor, anisotropy=(1.0, 1.0, 1.0), surface: Optional[
         from ..utils.relate import relate
         child_table = relate(rows[0], parents, parent_min_fraction, spacing, rows_children=rows)[0]
         out.update(parent=child_table["parent_id"], inside_fraction=child_table["inside_fraction"])
+    if near is not None:
+        from ..utils.proximity import proximity
+        table = proximity(rows[0], None if isinstance(near, str) else near, near_distance, spacing, rows_a=rows,
+                          voxels_a=sums[:, 0])[1]
+        out.update(near_partners=table["partners"], nearest_id=table["nearest_id"], nearest_gap=table["nearest_gap"],
+                   near_voxels=table["near_voxels"], near_fraction=table["near_fraction"])
     return out
 
 
@@ -977,7 +999,7 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
                skeleton_radius: Optional[Tensor] = None, mesh_counts: Optional[Tensor] = None,
                mesh_closed: bool = False, piece_table: Optional[Tensor] = None, thickness_table=None,
                contact_table=None, intensity=None, ring=None, branch_tables=None, core_table=None,
-               parent_table=None) -> str:
+               parent_table=None, near_table=None) -> str:
     """The text of ``_instance_stats.csv``: two header lines (file, spacing), the column names, and one row per
     instance with at least ``min_voxels`` voxels; floats are printed with ``repr``.  With ``mesh_cells`` (the (N, 30)
     counts of ``instance_mesh_cells``) the columns ``surface_area,surface_to_volume`` follow; without, the text is what
@@ -1003,7 +1025,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
     graph_length,branch_length_mean,longest_branch``.  With ``core_table`` (the (P, 6) table of
     ``utils.split.core_pieces``) ``cores`` comes behind even those; without it the text is byte for byte what it was.
     With ``parent_table`` (the ``(parent_id, inside_fraction)`` of ``utils.relate.relate``, N values each)
-    ``parent,inside_fraction`` are the last columns, under the same rule."""
+    ``parent,inside_fraction`` are the last columns, under the same rule.  With ``near_table`` (the per-instance table of
+    ``utils.proximity.proximity``) ``near_partners,nearest_id,nearest_gap,near_voxels,near_fraction`` follow them."""
     if ring is not None and intensity is None:
         raise ValueError("ring comes with intensity: the contrast needs both")
     spacing = _spacing(spacing)
@@ -1041,6 +1064,11 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
         if d["parent"].numel() != len(ids) or d["inside_fraction"].numel() != len(ids):
             raise ValueError(f"parent_table has {d['parent'].numel()} and {d['inside_fraction'].numel()} values for "
                              f"{len(ids)} ids")
+    if near_table is not None:
+        near_keys = ("partners", "nearest_id", "nearest_gap", "near_voxels", "near_fraction")
+        d.update({n: torch.as_tensor(near_table[k]).reshape(-1) for n, k in zip(NEAR_COLUMNS.split(","), near_keys)})
+        if any(d[n].numel() != len(ids) for n in NEAR_COLUMNS.split(",")):
+            raise ValueError(f"near_table does not have one row for each of the {len(ids)} ids")
     d = {k: v.cpu().tolist() for k, v in d.items()}
     lines = [f"Mask File: {mask_path}\n", "Spacing: {} {} {}\n".format(*(repr(v) for v in spacing)),
              CSV_COLUMNS + ("," + SURFACE_COLUMNS if mesh_cells is not None else "") +
@@ -1054,7 +1082,8 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
              ("," + RING_COLUMNS if ring is not None else "") +
              ("," + BRANCH_COLUMNS if branch_tables is not None else "") +
              ("," + CORES_COLUMNS if core_table is not None else "") +
-             ("," + PARENT_COLUMNS if parent_table is not None else "") + "\n"]
+             ("," + PARENT_COLUMNS if parent_table is not None else "") +
+             ("," + NEAR_COLUMNS if near_table is not None else "") + "\n"]
     for i, u in enumerate(ids):
         if d["voxels"][i] < min_voxels:
             continue
@@ -1090,6 +1119,9 @@ def format_csv(mask_path: str, ids, sums: Tensor, boxes: Tensor, shape, spacing=
             cells += [d["cores"][i]]
         if parent_table is not None:
             cells += [d["parent"][i], repr(d["inside_fraction"][i])]
+        if near_table is not None:
+            cells += [d["near_partners"][i], d["nearest_id"][i], repr(d["nearest_gap"][i]), d["near_voxels"][i],
+                      repr(d["near_fraction"][i])]
         lines.append(",".join(str(c) for c in cells) + "\n")
     return "".join(lines)
 
@@ -1193,6 +1225,13 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     parser.add_argument("--parent-min-fraction", type=float, default=None, metavar="F",
                         help="With --parents: an instance with less than this share of its voxels inside its parent gets "
                              "parent 0 (default 0)")
+    parser.add_argument("--near", type=str, default=None, metavar="B|self",
+                        help="Append " + NEAR_COLUMNS + ": B (.tif or .npy of the same shape) is a second mask, 'self' "
+                             "the mask itself; the instances of it within --near-distance of every instance, the "
+                             "closest of them and the gap to it, and the instance's voxels that lie that close, as "
+                             "python -m skoots_amd.utils.proximity derives them")
+    parser.add_argument("--near-distance", type=float, default=None, metavar="D",
+                        help="With --near: the distance, in the units of --spacing")
     parser.add_argument("--out", type=str, default=None, help="Output file (default: <mask>_instance_stats.csv)")
     parser.add_argument("--log", type=int, default=3, choices=range(5),
                         help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
@@ -1218,6 +1257,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         args.parent_min_fraction = 0.0
     if not 0.0 <= args.parent_min_fraction <= 1.0:
         parser.error("--parent-min-fraction takes a share in [0, 1]")
+    if (args.near is None) != (args.near_distance is None):
+        parser.error("--near and --near-distance come together")
+    if args.near_distance is not None and not (0.0 <= args.near_distance < float("inf")):
+        parser.error("--near-distance takes a non-negative finite distance")
     if args.iou_threshold is None:
         args.iou_threshold = 0.1
     if args.image is None and (args.intensity_ring is not None or args.save_histograms):
@@ -1324,9 +1367,22 @@ def main(argv: Optional[Sequence[str]] = None) -> str:
                              f"{tuple(mask.shape)}: the parents of a mask have its shape")
         child_table = relate(rows[0], parent_mask.to("cuda"), args.parent_min_fraction, spacing, rows_children=rows)[0]
         parent_table = (child_table["parent_id"], child_table["inside_fraction"])
+    near_table = None
+    if args.near is not None:
+        from ..utils.proximity import proximity
+        near_mask = None
+        if args.near != "self":
+            if not os.path.exists(args.near):
+                raise RuntimeError(f"{args.near} does not exist")
+            near_mask = load_mask(args.near)
+            if tuple(near_mask.shape) != tuple(mask.shape):
+                raise ValueError(f"{args.near} has the shape {tuple(near_mask.shape)} and {args.mask} "
+                                 f"{tuple(mask.shape)}: the mask of --near has the mask's shape")
+            near_mask = near_mask.to("cuda")
+        near_table = proximity(rows[0], near_mask, args.near_distance, spacing, rows_a=rows, voxels_a=sums[:, 0])[1]
     text = format_csv(args.mask, ids, sums, boxes, tuple(mask.shape[-3:]), spacing, args.min_voxels, cells, graph,
                       max_d2, skel_radius, mesh_counts, args.mesh == "closed", piece_table, thickness_table,
-                      contact_table, intensity, ring, branch_tables, core_table, parent_table)
+                      contact_table, intensity, ring, branch_tables, core_table, parent_table, near_table)
     out_path = args.out or f"{os.path.splitext(args.mask)[0]}_instance_stats.csv"
     with open(out_path, "w") as file:
         file.write(text)

@@ -21,6 +21,9 @@ reference's function of that name on top of it, and ``validate/compare.py`` deri
 ``instance_overlaps`` says which instance of one mask shares voxels with which instance of another, one row per pair;
 ``sparse_mask_iou`` is ``mask_iou`` on those pairs alone, the function the reference declares and leaves unwritten, and
 ``match_instances_sparse`` is ``match_instances`` on them.
+``instance_proximity`` says which instances lie within a distance of each other, how close they come and how many voxels
+of each lie that close, one row per pair; ``proximity_reach`` is the reach of a distance in voxels and ``plan_proximity``
+the per-instance summary of the table.
 ``instance_intensity`` reads the image under every instance -- count, sums, extrema and a 256-bin histogram -- and
 ``intensity_ring`` the image over the background around it.
 ``instance_surfaces``, ``surface_distances``, ``match_instances`` and ``pair_summaries`` are the parts of
@@ -472,6 +475,130 @@ def match_instances_sparse(table: Tensor, iou_values: Tensor, N: int, M: int, io
     first.scatter_reduce_(0, r, torch.where(v == best[r], c, c.new_tensor(M)), "amin", include_self=True)
     first = torch.where(best > 0, first, first.new_tensor(0))
     return torch.where(best > iou_threshold, first, first.new_tensor(-1))
+
+
+# ---- instances within a distance of each other ----
+
+N_PROXIMITY = 4                # int64 values per row of sk_instance_proximity: ra, rb, near_voxels, gap2_bits
+MAX_PROXIMITY_CAPACITY = 1 << 30
+
+
+def _proximity_metric(distance, spacing) -> Tuple[Tuple[float, float, float], float]:
+    """((wx, wy, wz), limit2) of a distance and a spacing, as ``nearest_label`` forms them: the spacing squared and
+    ``fl(d d)``; the distance must be a non-negative finite number whose square is finite."""
+    from ..lib.morphology import max_distance_squared, squared_spacing
+    w = squared_spacing(spacing)
+    if distance is None:
+        raise ValueError("distance must be a non-negative finite number, got None")
+    try:
+        limit2 = max_distance_squared(distance)
+    except ValueError:
+        raise ValueError(f"distance must be a non-negative finite number, got {distance!r}") from None
+    if not limit2 < float("inf"):
+        raise ValueError(f"distance must be a non-negative finite number with a finite square, got {distance!r}")
+    return w, limit2
+
+
+def _reach_query(w, limit2):
+    out = np.zeros(8, dtype=np.int32)
+    _ffi.check(_ffi.lib.sk_instance_proximity_reach(w[0], w[1], w[2], limit2, out.ctypes.data))
+    return tuple(int(v) for v in out)
+
+
+def proximity_reach(distance, spacing=(1.0, 1.0, 1.0)) -> Tuple[int, int, int]:
+    """(hx, hy, hz): how many voxels ``distance`` reaches along every axis at ``spacing`` -- per axis the largest k with
+    ``fl(w k^2) <= fl(d d)``, the library's own search (``sk_instance_proximity_reach``; a host function, no GPU).
+    Raises ``ValueError`` when the kernel does not stage a window that large; the message names the distance below
+    which it does at that spacing.  A reach is never truncated."""
+    w, limit2 = _proximity_metric(distance, spacing)
+    hx, hy, hz, taken = _reach_query(w, limit2)[:4]
+    if taken:
+        return hx, hy, hz
+    # the reach grows where d passes a multiple of a spacing: the first such distance that is refused
+    steps = sorted({wk * float(k * k) for wk in w for k in range(1, 257)})
+    first = next((t for t in steps if t <= limit2 and not _reach_query(w, t)[3]), limit2)
+    raise ValueError(f"distance {distance!r} reaches ({hx}, {hy}, {hz}) voxels at spacing {tuple(spacing)}, beyond the "
+                     f"window the proximity kernel stages; at this spacing it takes every distance below "
+                     f"{float(np.sqrt(first))!r}")
+
+
+def instance_proximity(a: Tensor, b=None, distance=None, spacing=(1.0, 1.0, 1.0), rows_a=None, rows_b=None,
+                       capacity=None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(ids_a (N) int64 ascending, ids_b (M) int64 ascending, pairs (P, 3) int64, gap2 (P) float64) of two integer
+    device tensors of one shape, (X, Y, Z) or (1, X, Y, Z): which instance of ``a`` lies within ``distance`` of which
+    instance of ``b``, from ``sk_instance_proximity`` (include/skoots_hip.h has the definition).  A row
+    of ``pairs`` is ``ra, rb, near_voxels``: a ROW of ``ids_a`` (1 .. N), a row of ``ids_b`` (1 .. M) and the voxels of
+    ``ra`` that have a voxel of ``rb`` within the distance (``<=``; centre to centre at ``spacing``); ``gap2`` is the
+    smallest squared distance between the two, 0 where they overlap.  The rows with ``rb = 0`` are the union rows: the
+    voxels of ``ra`` within the distance of ANY instance of ``b``, and the smallest squared distance to one.  Only the
+    voxels of ``a`` are counted; swap the masks for the other side -- ``gap2`` is the same from both.  ``b=None`` is
+    the one-mask mode: ``a`` against itself, an instance never its own partner.  Sorted by ``(ra, rb)`` with torch, so
+    two runs give equal tensors.  ``rows_a`` / ``rows_b`` are ``id_rows(a)`` / ``id_rows(b)`` when the caller has them.
+
+    ``distance`` must be within ``proximity_reach``; the capacity and its retry are ``instance_overlaps``'.  Two masks
+    of different shape or device raise ``ValueError``."""
+    assert _ffi.lib.sk_instance_proximity_row_values() == N_PROXIMITY
+    ma = _Rows(a, rows_a, check_voxels, name="a")
+    same = b is None
+    mb = ma if same else _Rows(b, rows_b, check_voxels, name="b")
+    if ma.shape != mb.shape or ma.dev != mb.dev:
+        raise ValueError(f"a {ma.shape} on {ma.dev} and b {mb.shape} on {mb.dev} must have one shape and one device")
+    w, limit2 = _proximity_metric(distance, spacing)
+    proximity_reach(distance, spacing)
+    dev, N, M, (X, Y, Z) = ma.dev, ma.N, mb.N, ma.shape
+    n = X * Y * Z
+    if n == 0 or N == 0 or M == 0:
+        return (ma.ids, mb.ids, torch.empty((0, 3), dtype=torch.int64, device=dev),
+                torch.empty((0,), dtype=torch.float64, device=dev))
+    if capacity is None:
+        capacity = _pow2_at_least(max(1024, 8 * max(N, M)))
+    capacity = int(capacity)
+    if capacity < 1 or capacity & (capacity - 1):
+        raise ValueError(f"capacity must be a power of two >= 1, got {capacity}")
+    most = min(N * (M + 1), n * (M + 1))                     # distinct keys, the union rows included
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    while True:
+        if capacity > MAX_PROXIMITY_CAPACITY:
+            raise RuntimeError(f"instance_proximity: the pair table would need {capacity} slots, more than "
+                               f"{MAX_PROXIMITY_CAPACITY}")
+        ws_bytes = int(_ffi.lib.sk_instance_proximity_workspace_bytes(capacity))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((capacity, N_PROXIMITY), dtype=torch.int64, device=dev)
+        ma.call(_ffi.lib.sk_instance_proximity, _ffi.ptr(mb.a), _ffi.ptr(mb.lut), mb.max_id, M, *w, limit2, int(same),
+                _ffi.ptr(out), capacity, _ffi.ptr(counts), _ffi.ptr(ws), ws_bytes)
+        stored, refused = (int(v) for v in counts.tolist())
+        if refused == 0:
+            break
+        del ws, out
+        capacity = max(2 * capacity, _pow2_at_least(2 * min(stored + refused, most)))
+    table = out[:stored]
+    table = table[torch.argsort(table[:, 0] * (M + 1) + table[:, 1])]     # ra <= N, rb <= M: one int64 key
+    return ma.ids, mb.ids, table[:, :3].contiguous(), table[:, 3].contiguous().view(torch.float64)
+
+
+def plan_proximity(pairs, gap2, N: int, M: int) -> Dict[str, np.ndarray]:
+    """What the table of ``instance_proximity`` says about every row 1 .. N of ``a``, numpy in and numpy out:
+    ``partners`` (N) int64, the instances of ``b`` within the distance; ``nearest_row`` (N) int64, the one with the
+    smallest ``gap2`` and on a tie the lowest row, 0 without a partner; ``nearest_gap2`` (N) float64, that gap, ``inf``
+    without a partner; ``near_voxels`` (N) int64, the union row's count.  ``pairs`` is (P, 3), ``gap2`` (P)."""
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)
+    g = np.asarray(gap2, dtype=np.float64).reshape(-1)
+    N, M = int(N), int(M)
+    if p.shape[0] != g.shape[0]:
+        raise ValueError(f"pairs has {p.shape[0]} rows and gap2 {g.shape[0]} values")
+    if p.shape[0] and (p[:, 0].min() < 1 or p[:, 0].max() > N or p[:, 1].min() < 0 or p[:, 1].max() > M):
+        raise ValueError(f"pairs holds rows outside 1 .. {N} of a or 0 .. {M} of b")
+    partners, near_voxels = np.zeros(N + 1, np.int64), np.zeros(N + 1, np.int64)
+    nearest_row, nearest_gap2 = np.zeros(N + 1, np.int64), np.full(N + 1, np.inf)
+    union = p[:, 1] == 0
+    near_voxels[p[union, 0]] = p[union, 2]
+    q, qg = p[~union], g[~union]
+    np.add.at(partners, q[:, 0], 1)
+    order = np.lexsort((q[:, 1], qg, q[:, 0]))[::-1]         # the last write wins: smallest gap, then lowest row
+    nearest_row[q[order, 0]] = q[order, 1]
+    nearest_gap2[q[order, 0]] = qg[order]
+    return {"partners": partners[1:], "nearest_row": nearest_row[1:], "nearest_gap2": nearest_gap2[1:],
+            "near_voxels": near_voxels[1:]}
 
 
 # ---- the image under every instance (DESIGN.md §30) ----
