@@ -855,6 +855,36 @@ size_t sk_deflate_workspace_bytes(int n_streams, int64_t stream_bytes);
 int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes, uint8_t* dst,
                        int64_t* dst_offsets, uint8_t* all_zero, void* workspace, size_t workspace_bytes, void* stream);
 
+/* sk_deflate_streams with a choice of code.  huffman = 0: the fixed code of RFC 1951 3.2.6, byte for byte what
+ * sk_deflate_streams writes.  huffman = 1: the same parse, and every 16 KiB piece is written in the form with the
+ * fewest bytes among stored (5 + n), the fixed code and a dynamic code built for the piece (3.2.7, header included);
+ * on equal bytes the order is stored, fixed, dynamic.  So a stream is never longer than with huffman = 0, and
+ * sk_deflate_bound and sk_deflate_workspace_bytes hold for both.  The dynamic code: optimal code lengths under the
+ * limit 15 (ties in the order (count, symbol); see sk_deflate_code_host), HDIST = 1 with one length of zero when the
+ * piece has no match, one length of 1 when it has one distance symbol, complete codes otherwise; the length sequence
+ * uses 16, 17 and 18.  The same argument checks run before any launch; any other huffman is refused
+ * (SK_ERR_ARG, "sk_deflate_streams_coded: huffman = ...").  The bytes depend on the input alone. */
+int sk_deflate_streams_coded(const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes, int huffman,
+                             uint8_t* dst, int64_t* dst_offsets, uint8_t* all_zero, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* Host function, no device touched: the code builder the piece kernel runs (the same text, compiled for the host).
+ * freq[n_symbols] (1 <= n_symbols <= 286, sum below 2^32) -> lengths[n_symbols] (0 for an unused symbol, else
+ * 1..limit, 1 <= limit <= 15) and the canonical codes of RFC 1951 3.2.2 (most significant bit first, 0 for an unused
+ * symbol).  The result is a function of freq alone: the used symbols are ordered by (count, symbol), merged with the
+ * two-queue method (leaf before internal node on equal weights), depths beyond the limit are repaired on the
+ * per-depth counts, and lengths are dealt out along the order, longest to the rarest.  Sum freq * length is the
+ * Huffman optimum whenever an optimal code fits the limit; the Kraft sum is exactly 1 with two or more used symbols.
+ * One used symbol gets length 1, none gets no length.  More used symbols than 2^limit is refused. */
+int sk_deflate_code_host(const uint32_t* freq, int n_symbols, int limit, uint8_t* lengths, uint16_t* codes);
+
+/* Host function, no device touched: the header of a dynamic block for lit_lengths[286] and dist_lengths[30] (each
+ * 0..15), as the piece kernel writes it: BFINAL = bfinal, BTYPE = 10, HLIT, HDIST, HCLEN, the code-length code's
+ * lengths (limit 7), the run-length coded length sequence.  out (at least 576 bytes) receives the bits, least
+ * significant bit of out[0] first, the rest zero; *n_bits their number. */
+int sk_deflate_header_host(const uint8_t* lit_lengths, const uint8_t* dist_lengths, int bfinal, uint8_t* out,
+                           size_t out_bytes, int64_t* n_bits);
+
 /* ------------------------------------------------------------------------ *
  * Reading eval()'s files back: inflate decoder for zarr chunks and TIFF strips
  * ------------------------------------------------------------------------ */

@@ -20,6 +20,9 @@ def build_parser() -> argparse.ArgumentParser:
                            help="skips model evaluation and loads previously evaluated arrays")
     eval_args.add_argument("--log", type=int, default=3,
                            help="Log Level: 0-Debug, 1-Info, 2-Warning, 3-Error, 4-Critical")
+    eval_args.add_argument("--output-huffman", choices=("fixed", "dynamic"), default=None,
+                           help="Huffman code of the device deflate encoder that writes the zarr chunks and TIFF pages "
+                                "(eval and --convert); default: skoots_amd.lib.eval.OUTPUT_HUFFMAN")
     accessory_args = parser.add_argument_group("scripting arguments")
     accessory_args.add_argument("--skeletonize-train-data",
                                 help="calculate skeletons of training data (a label TIFF or a directory of them)")
@@ -50,7 +53,7 @@ def main(argv=None):
         create_gt_skeletons(args.skeletonize_train_data, args.mask_filter, scale)
     if args.convert is not None:
         from skoots_amd.utils.convert_trch_to_tif import convert
-        convert(args.convert)
+        convert(args.convert, huffman=args.output_huffman)
     if args.skeletonize_train_data is not None or args.convert is not None:   # no eval (skoots/__main__.py:84)
         return
     assert args.pretrained_checkpoint is not None, (
@@ -58,7 +61,7 @@ def main(argv=None):
     from skoots_amd.lib.eval import eval as sk_eval
     files = sorted(glob.glob(args.image + "/*.tif")) if os.path.isdir(args.image) else [args.image]
     for f in files:
-        sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached)
+        sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached, output_huffman=args.output_huffman)
 
 
 if __name__ == "__main__":

@@ -201,6 +201,9 @@ _SIGS = {
     "sk_deflate_bound": (sz, [i64]),
     "sk_deflate_workspace_bytes": (sz, [i32, i64]),
     "sk_deflate_streams": (i32, [vp, i32, i64, i32, vp, vp, vp, vp, sz, vp]),
+    "sk_deflate_streams_coded": (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "sk_deflate_code_host": (i32, [vp, i32, i32, vp, vp]),
+    "sk_deflate_header_host": (i32, [vp, vp, i32, vp, sz, vp]),
     "sk_inflate_streams": (i32, [vp, vp, i32, vp, vp, i32, vp, vp]),
     "sk_tiff_undo_predictor": (i32, [vp, i64, i32, i32, i32, vp]),
     "sk_lz4_streams": (i32, [vp, i64, vp, i32, vp, i64, vp, vp]),

@@ -7,7 +7,7 @@
 // encoded independently, every piece but the last ends with an empty stored block (00 00 FF FF after padding to a
 // byte), so that pieces are byte-aligned and a stream is the concatenation of its pieces; Adler-32 is computed per
 // piece and combined.  Four launches, all stream-ordered:
-//   deflate_piece_kernel    one workgroup per piece: match search, parse, fixed-Huffman bits -> the piece's slot
+//   deflate_piece_kernel    one workgroup per piece: match search, parse, Huffman bits -> the piece's slot
 //   deflate_stream_kernel   one workgroup per stream: prefix sum of its pieces' sizes, Adler-32 combine, all-zero flag
 //   deflate_offsets_kernel  one workgroup: prefix sum of the stream sizes -> dst_offsets
 //   deflate_compact_kernel  one workgroup per piece: slot -> its place in dst, stream header and trailer
@@ -24,9 +24,23 @@
 //   (c) bits per token -> block scan -> every token ORs its bits into the LDS image of the output (atomicOr: the
 //       result does not depend on the order).  Huffman codes most-significant bit first, extra bits least first.
 //   (d) end of block, the aligning stored block; a piece whose encoding would be longer than storing it is stored.
-// Nothing depends on the order in which atomics land (OR into words, monotone marks), so the bytes are the same on
-// every run and for every batching.
+// Nothing depends on the order in which atomics land (OR into words, monotone marks, integer counters), so the bytes
+// are the same on every run and for every batching.
+//
+// Dynamic codes (deflate_piece_kernel<true>, sk_deflate_streams_coded with huffman = 1).  Parse, (a), (b), the Adler sums
+// and the all-zero flag are the same text.  After (b): (i) the tokens are counted into 286 + 30 LDS counters; (ii) the
+// used symbols are ranked by (count, symbol) by counting, and one lane runs the serial text of deflate_code.inc on the
+// tables in LDS: two-queue merge, limit 15 with its repair, canonical codes, the run-length coded length sequence, the
+// code-length code; (iii) one walk gives every token's bits under both codes; (iv) the piece is written in the form
+// with the fewest bytes -- stored, fixed, dynamic in that order on equal bytes -- by the same phase (c), the codes
+// read from an LDS table.  A minimum over forms that include "stored" keeps sk_deflate_bound as it is.
 #include "common.h"
+
+#define SK_DFC_NS sk_dfc
+#define SK_DFC_FN __host__ __device__
+#include "deflate_code.inc"
+#undef SK_DFC_NS
+#undef SK_DFC_FN
 
 namespace sk {
 
@@ -42,15 +56,31 @@ constexpr int kDfSlot = kDfPiece + 32;          // workspace bytes per piece
 constexpr int kDfStoredOff = 11;                // a stored piece's 5 header bytes end where its 16-byte aligned data begin
 constexpr int kDfMeta = 8;                      // uint32 per piece: bytes, offset in slot, sum, weighted sum, nonzero
 constexpr unsigned kAdlerMod = 65521u;
+constexpr int kDfSyms = sk_dfc::kDfcSeq;         // 286 literal / length symbols, then the 30 distance symbols
 static_assert(kDfPer == 64, "one mask word per thread");
 
 static inline int64_t df_pieces(int64_t stream_bytes) {
     return stream_bytes <= 0 ? 1 : (stream_bytes + kDfPiece - 1) / kDfPiece;
 }
 
+// tables of a piece's dynamic code; they live where eq[] was, which is dead after the match search
+struct DfDyn {
+    unsigned freq[kDfSyms];                                  // token histogram
+    unsigned tab[kDfSyms];                                   // bit-reversed code | length << 16
+    unsigned short code[kDfSyms];
+    uint8_t len[kDfSyms];
+    unsigned short dorder[sk_dfc::kDfcDist];                 // used distance symbols by (count, symbol)
+    int used[2];
+    sk_dfc::DfcWork work;
+    sk_dfc::DfcHdr hdr;
+};
+
 struct DfLds {
     unsigned data[kDfWords + kDfWords / 16];                 // word w at w + (w >> 4): a thread's 16 words, stride 17
-    unsigned long long eq[kDfGroup][kDfBlock + 8];           // words past the piece stay zero
+    union {
+        unsigned long long eq[kDfGroup][kDfBlock + 8];       // words past the piece stay zero
+        DfDyn dyn;
+    };
     unsigned long long marks[kDfBlock];
     unsigned red[32];
     union {
@@ -71,10 +101,11 @@ __device__ inline void df_sym(int sym, unsigned& code, int& nb) {
     else { code = 0xC0u + (sym - 280); nb = 8; }
     code = df_rev(code, nb);
 }
-__device__ inline void df_len_bits(int len, unsigned& bits, int& nb) {
+// length 3..258 -> symbol 257..285, its extra bits and their value
+__device__ inline void df_len_sym(int len, int& sym, int& eb, unsigned& extra) {
     const int l = len - 3;
-    int sym, eb = 0;
-    unsigned extra = 0;
+    eb = 0;
+    extra = 0;
     if (len == kDfMaxLen) sym = 285;
     else if (l < 8) sym = 257 + l;
     else {
@@ -82,20 +113,32 @@ __device__ inline void df_len_bits(int len, unsigned& bits, int& nb) {
         sym = 261 + 4 * eb + ((l >> eb) & 3);
         extra = l & ((1u << eb) - 1);
     }
+}
+// distance 1..32768 -> symbol 0..29, its extra bits and their value
+__device__ inline void df_dist_sym(int d, int& code, int& eb, unsigned& extra) {
+    const int dd = d - 1;
+    code = dd;
+    eb = 0;
+    extra = 0;
+    if (dd >= 4) {
+        eb = (31 - __clz(dd)) - 1;
+        code = 2 * eb + 2 + ((dd >> eb) & 1);
+        extra = dd & ((1u << eb) - 1);
+    }
+}
+__device__ inline void df_len_bits(int len, unsigned& bits, int& nb) {
+    int sym, eb;
+    unsigned extra;
+    df_len_sym(len, sym, eb, extra);
     unsigned code;
     df_sym(sym, code, nb);
     bits = code | (extra << nb);
     nb += eb;
 }
 __device__ inline void df_dist_bits(int d, unsigned& bits, int& nb) {
-    const int dd = d - 1;
-    int code = dd, eb = 0;
-    unsigned extra = 0;
-    if (dd >= 4) {
-        eb = (31 - __clz(dd)) - 1;
-        code = 2 * eb + 2 + ((dd >> eb) & 1);
-        extra = dd & ((1u << eb) - 1);
-    }
+    int code, eb;
+    unsigned extra;
+    df_dist_sym(d, code, eb, extra);
     bits = df_rev(code, 5) | (extra << 5);
     nb = 5 + eb;
 }
@@ -122,7 +165,35 @@ __device__ inline void df_token(unsigned best, unsigned byte, int e, unsigned& b
         n1 = 0;
     }
 }
+// the same token under the piece's own code: codes and lengths come from tab[]
+__device__ inline void df_token_dyn(unsigned best, unsigned byte, int e, const unsigned* tab, unsigned& b0, int& n0,
+                                    unsigned& b1, int& n1) {
+    const int len = (int)(best >> 7);
+    if (len >= 3) {
+        int sym, eb;
+        unsigned extra;
+        df_len_sym(len, sym, eb, extra);
+        unsigned ent = tab[sym];
+        int nl = (int)(ent >> 16);
+        b0 = (ent & 0xffffu) | (extra << nl);
+        n0 = nl + eb;
+        df_dist_sym(df_dist(127 - (int)(best & 127u), e), sym, eb, extra);
+        ent = tab[sk_dfc::kDfcLit + sym];
+        nl = (int)(ent >> 16);
+        b1 = (ent & 0xffffu) | (extra << nl);
+        n1 = nl + eb;
+    } else {
+        const unsigned ent = tab[byte];
+        b0 = ent & 0xffffu;
+        n0 = (int)(ent >> 16);
+        b1 = 0;
+        n1 = 0;
+    }
+}
 
+// kDyn = false: every piece is coded with the fixed code or stored.  kDyn = true: the piece's own code is built as
+// well and the smallest of stored, fixed and dynamic is written.
+template <bool kDyn>
 __global__ __launch_bounds__(kDfBlock, 2) void deflate_piece_kernel(const uint8_t* __restrict__ src, const int64_t L,
                                                                     const int64_t pps, const int e,
                                                                     uint8_t* __restrict__ slots,
@@ -253,6 +324,10 @@ __global__ __launch_bounds__(kDfBlock, 2) void deflate_piece_kernel(const uint8_
         s.jump[k * kDfBlock + t] = (unsigned short)nx;
     }
     s.marks[t] = (t == 0 && n > 0) ? 1ull : 0ull;
+    if constexpr (kDyn) {   // eq[] is behind the last barrier of (a)
+        for (int i = t; i < kDfSyms; i += kDfBlock) s.dyn.freq[i] = i == 256 ? 1u : 0u;   // end of block counts once
+        if (t < 2) s.dyn.used[t] = 0;
+    }
     __syncthreads();
     while ((int)s.jump[0] < n) {   // level k: everything within 2^k - 1 hops of 0 is marked, jump = next^(2^k)
         const unsigned long long m = s.marks[t];
@@ -275,7 +350,73 @@ __global__ __launch_bounds__(kDfBlock, 2) void deflate_piece_kernel(const uint8_
 
     // ---- (c) bits per token, block scan
     const unsigned long long marked = s.marks[t];
-    unsigned tb = 0;
+    if constexpr (kDyn) {
+        DfDyn& y = s.dyn;
+        // (i) histogram of the tokens.  A thread keeps the two symbols it saw last in registers, so that a piece made of
+        // two literals costs two adds per thread; integer adds, so the counts do not depend on the order.
+        int ca = -1, cb = -1;
+        unsigned na = 0, nb = 0;
+#pragma unroll
+        for (int k = 0; k < kDfPer; ++k) {
+            if ((marked >> k) & 1ull) {
+                const int len = (int)(best[k] >> 7);
+                int sym = (int)((own[k >> 2] >> (8 * (k & 3))) & 255u);
+                if (len >= 3) {
+                    int dsym, eb;
+                    unsigned extra;
+                    df_len_sym(len, sym, eb, extra);
+                    df_dist_sym(df_dist(127 - (int)(best[k] & 127u), e), dsym, eb, extra);
+                    atomicAdd(&y.freq[sk_dfc::kDfcLit + dsym], 1u);
+                }
+                if (sym == cb) ++nb;
+                else if (sym == ca) ++na;
+                else {
+                    if (na) atomicAdd(&y.freq[ca], na);
+                    ca = cb;
+                    na = nb;
+                    cb = sym;
+                    nb = 1;
+                }
+            }
+        }
+        if (na) atomicAdd(&y.freq[ca], na);
+        if (nb) atomicAdd(&y.freq[cb], nb);
+        __syncthreads();
+        // (ii) the used symbols of either alphabet in the order (count, symbol): rank by counting
+        for (int i = t; i < kDfSyms; i += kDfBlock) {
+            const unsigned f = y.freq[i];
+            if (f) {
+                const bool dist = i >= sk_dfc::kDfcLit;
+                const int lo = dist ? sk_dfc::kDfcLit : 0, hi = dist ? kDfSyms : sk_dfc::kDfcLit;
+                int r = 0;
+                for (int j = lo; j < hi; ++j) {
+                    const unsigned g = y.freq[j];
+                    r += (g != 0 && (g < f || (g == f && j < i))) ? 1 : 0;
+                }
+                if (dist) y.dorder[r] = (unsigned short)(i - sk_dfc::kDfcLit);
+                else y.work.order[r] = (unsigned short)i;
+                atomicAdd(&y.used[dist ? 1 : 0], 1);
+            }
+        }
+        __syncthreads();
+        if (t == 0) {   // the serial parts: deflate_code.inc
+            sk_dfc::dfc_lengths(y.freq, sk_dfc::kDfcLit, y.used[0], 15, y.work, y.len);
+            sk_dfc::dfc_codes(y.len, sk_dfc::kDfcLit, y.work, y.code);
+            const int md = y.used[1];
+            for (int i = 0; i < md; ++i) y.work.order[i] = y.dorder[i];
+            sk_dfc::dfc_lengths(y.freq + sk_dfc::kDfcLit, sk_dfc::kDfcDist, md, 15, y.work, y.len + sk_dfc::kDfcLit);
+            sk_dfc::dfc_codes(y.len + sk_dfc::kDfcLit, sk_dfc::kDfcDist, y.work, y.code + sk_dfc::kDfcLit);
+            sk_dfc::dfc_header_plan(y.len, y.len + sk_dfc::kDfcLit, y.work, y.hdr);
+        }
+        __syncthreads();
+        for (int i = t; i < kDfSyms; i += kDfBlock) {
+            const int nl = y.len[i];
+            y.tab[i] = (nl ? df_rev(y.code[i], nl) : 0u) | ((unsigned)nl << 16);
+        }
+        __syncthreads();
+    }
+    // bits per token under both codes in one walk
+    unsigned tb = 0, tbd = 0;
 #pragma unroll
     for (int k = 0; k < kDfPer; ++k) {
         if ((marked >> k) & 1ull) {
@@ -283,27 +424,65 @@ __global__ __launch_bounds__(kDfBlock, 2) void deflate_piece_kernel(const uint8_
             int n0, n1;
             df_token(best[k], (own[k >> 2] >> (8 * (k & 3))) & 255u, e, b0, n0, b1, n1);
             tb += (unsigned)(n0 + n1);
+            if constexpr (kDyn) {
+                df_token_dyn(best[k], (own[k >> 2] >> (8 * (k & 3))) & 255u, e, s.dyn.tab, b0, n0, b1, n1);
+                tbd += (unsigned)(n0 + n1);
+            }
         }
     }
-    unsigned inc = tb;
+    unsigned inc = tb, incd = tbd;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const unsigned v = __shfl_up(inc, o);
         if (lane >= o) inc += v;
+        if constexpr (kDyn) {
+            const unsigned vd = __shfl_up(incd, o);
+            if (lane >= o) incd += vd;
+        }
     }
-    if (lane == 63) s.red[16 + wave] = inc;
+    if (lane == 63) {
+        s.red[16 + wave] = inc;
+        if constexpr (kDyn) s.red[20 + wave] = incd;
+    }
     __syncthreads();   // also: every read of jump[] is behind us, out[] may take its place
-    unsigned woff = 0, total = 0;
+    unsigned woff = 0, total = 0, woffd = 0, totald = 0;
 #pragma unroll
     for (int w = 0; w < kDfBlock / 64; ++w) {
         const unsigned v = s.red[16 + w];
         if (w < wave) woff += v;
         total += v;
+        if constexpr (kDyn) {
+            const unsigned vd = s.red[20 + w];
+            if (w < wave) woffd += vd;
+            totald += vd;
+        }
     }
-    const unsigned T = 3u + total + 7u;                       // block header, tokens, end of block
-    const unsigned sync_at = (T + 3u + 7u) / 8u;              // first byte after the empty stored block's header
-    const unsigned cbytes = last ? (T + 7u) / 8u : sync_at + 4u;
-    const bool stored = cbytes > 5u + (unsigned)n;
+    unsigned T = 3u + total + 7u;                             // block header, tokens, end of block
+    unsigned sync_at = (T + 3u + 7u) / 8u;                    // first byte after the empty stored block's header
+    unsigned cbytes = last ? (T + 7u) / 8u : sync_at + 4u;
+    bool stored = cbytes > 5u + (unsigned)n;
+    bool dyn = false;
+    unsigned hbits = 3u;                                      // bits in front of the first token
+    if constexpr (kDyn) {
+        // the smallest of the three wins; on equal bytes stored, then fixed, then dynamic
+        stored = cbytes >= 5u + (unsigned)n;
+        hbits = s.dyn.hdr.bits;
+        const unsigned Td = hbits + totald + (s.dyn.tab[256] >> 16);
+        const unsigned sync_d = (Td + 3u + 7u) / 8u;
+        const unsigned cbytes_d = last ? (Td + 7u) / 8u : sync_d + 4u;
+        if (cbytes_d < (stored ? 5u + (unsigned)n : cbytes)) {
+            dyn = true;
+            stored = false;
+            T = Td;
+            sync_at = sync_d;
+            cbytes = cbytes_d;
+            woff = woffd;
+            inc = incd;
+            tb = tbd;
+        } else {
+            hbits = 3u;
+        }
+    }
     uint8_t* slot = slots + piece * kDfSlot;
 
     if (!stored) {
@@ -311,19 +490,32 @@ __global__ __launch_bounds__(kDfBlock, 2) void deflate_piece_kernel(const uint8_
         for (unsigned i = t; i < nwords; i += kDfBlock) s.out[i] = 0;
         __syncthreads();
         if (t == 0) {
-            atomicOr(&s.out[0], (last ? 1u : 0u) | 2u);       // BFINAL, BTYPE = 01
+            if (!dyn) atomicOr(&s.out[0], (last ? 1u : 0u) | 2u);   // BFINAL, BTYPE = 01; its end of block is 7 zero bits
             if (!last) {                                      // 00 00 FF FF
                 atomicOr(&s.out[(sync_at + 2) >> 2], 0xFFu << (8 * ((sync_at + 2) & 3)));
                 atomicOr(&s.out[(sync_at + 3) >> 2], 0xFFu << (8 * ((sync_at + 3) & 3)));
             }
         }
-        unsigned off = 3u + woff + inc - tb;
+        if constexpr (kDyn) {
+            if (dyn && t == 0) {                              // BFINAL, BTYPE = 10, the code lengths; end of block
+                unsigned at = 0;
+                unsigned* out = s.out;
+                sk_dfc::dfc_header_emit(s.dyn.hdr, last ? 1 : 0, [&](unsigned val, int nb) {
+                    df_put(out, at, val, nb);
+                    at += (unsigned)nb;
+                });
+                const unsigned eob = s.dyn.tab[256];
+                df_put(out, hbits + totald, eob & 0xffffu, (int)(eob >> 16));
+            }
+        }
+        unsigned off = hbits + woff + inc - tb;
 #pragma unroll
         for (int k = 0; k < kDfPer; ++k) {
             if ((marked >> k) & 1ull) {
                 unsigned b0, b1;
                 int n0, n1;
-                df_token(best[k], (own[k >> 2] >> (8 * (k & 3))) & 255u, e, b0, n0, b1, n1);
+                if (kDyn && dyn) df_token_dyn(best[k], (own[k >> 2] >> (8 * (k & 3))) & 255u, e, s.dyn.tab, b0, n0, b1, n1);
+                else df_token(best[k], (own[k >> 2] >> (8 * (k & 3))) & 255u, e, b0, n0, b1, n1);
                 df_put(s.out, off, b0, n0);
                 off += n0;
                 if (n1) df_put(s.out, off, b1, n1);
@@ -474,6 +666,7 @@ __global__ __launch_bounds__(kDfBlock) void deflate_compact_kernel(const uint8_t
     }
 }
 
+static_assert(sizeof(DfDyn) <= sizeof(unsigned long long) * kDfGroup * (kDfBlock + 8), "the dynamic tables take eq[]'s place");
 static inline size_t df_align(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace sk
@@ -491,26 +684,29 @@ extern "C" size_t sk_deflate_workspace_bytes(int n_streams, int64_t stream_bytes
            sk::df_align((size_t)n_streams * 8) + 2 * sk::df_align((size_t)n_streams * 4) + 16;
 }
 
-extern "C" int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes, uint8_t* dst,
-                                  int64_t* dst_offsets, uint8_t* all_zero, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
-    SK_CHECK_ARG(n_streams >= 0, "sk_deflate_streams: n_streams = %d is negative", n_streams);
-    SK_CHECK_ARG(stream_bytes >= 0 && stream_bytes <= ((int64_t)1 << 40),
-                 "sk_deflate_streams: stream_bytes = %lld outside [0, 2^40]", (long long)stream_bytes);
-    SK_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4,
-                 "sk_deflate_streams: elem_bytes = %d, must be 1, 2 or 4", elem_bytes);
+// both entry points: fn is the name the refusals carry
+static int df_streams(const char* fn, const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes, int huffman,
+                      uint8_t* dst, int64_t* dst_offsets, uint8_t* all_zero, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    SK_CHECK_ARG(n_streams >= 0, "%s: n_streams = %d is negative", fn, n_streams);
+    SK_CHECK_ARG(stream_bytes >= 0 && stream_bytes <= ((int64_t)1 << 40), "%s: stream_bytes = %lld outside [0, 2^40]", fn,
+                 (long long)stream_bytes);
+    SK_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, "%s: elem_bytes = %d, must be 1, 2 or 4", fn,
+                 elem_bytes);
+    SK_CHECK_ARG(huffman == 0 || huffman == 1, "%s: huffman = %d, must be 0 (fixed code) or 1 (best of fixed and dynamic)",
+                 fn, huffman);
     SK_CHECK_ARG(dst_offsets != nullptr && ((uintptr_t)dst_offsets & 7) == 0,
-                 "sk_deflate_streams: dst_offsets is NULL or not 8-byte aligned");
+                 "%s: dst_offsets is NULL or not 8-byte aligned", fn);
     const int64_t pps = sk::df_pieces(stream_bytes);
     const int64_t pieces = (int64_t)n_streams * pps;
-    SK_CHECK_ARG(pieces <= 0x7fffffffLL, "sk_deflate_streams: %lld pieces of 16 KiB in one call, at most 2^31 - 1",
+    SK_CHECK_ARG(pieces <= 0x7fffffffLL, "%s: %lld pieces of 16 KiB in one call, at most 2^31 - 1", fn,
                  (long long)pieces);
-    SK_CHECK_ARG(n_streams == 0 || stream_bytes == 0 || src != nullptr, "sk_deflate_streams: src is NULL");
-    SK_CHECK_ARG(n_streams == 0 || dst != nullptr, "sk_deflate_streams: dst is NULL");
+    SK_CHECK_ARG(n_streams == 0 || stream_bytes == 0 || src != nullptr, "%s: src is NULL", fn);
+    SK_CHECK_ARG(n_streams == 0 || dst != nullptr, "%s: dst is NULL", fn);
     const size_t need = sk_deflate_workspace_bytes(n_streams, stream_bytes);
     SK_CHECK_ARG(workspace != nullptr && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= need,
-                 "sk_deflate_streams: workspace of %zu bytes (16-byte aligned) needed, got %zu at %p", need,
-                 workspace_bytes, workspace);
+                 "%s: workspace of %zu bytes (16-byte aligned) needed, got %zu at %p", fn, need, workspace_bytes,
+                 workspace);
     uint8_t* w = (uint8_t*)workspace;
     uint8_t* slots = w;
     w += sk::df_align((size_t)pieces * sk::kDfSlot);
@@ -525,8 +721,12 @@ extern "C" int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t str
     unsigned* stream_zero = (unsigned*)w;
     hipStream_t st = (hipStream_t)stream;
     if (n_streams > 0) {
-        hipLaunchKernelGGL(sk::deflate_piece_kernel, dim3((unsigned)pieces), dim3(sk::kDfBlock), 0, st, src, stream_bytes,
-                           pps, elem_bytes, slots, meta);
+        if (huffman)
+            hipLaunchKernelGGL(sk::deflate_piece_kernel<true>, dim3((unsigned)pieces), dim3(sk::kDfBlock), 0, st, src,
+                               stream_bytes, pps, elem_bytes, slots, meta);
+        else
+            hipLaunchKernelGGL(sk::deflate_piece_kernel<false>, dim3((unsigned)pieces), dim3(sk::kDfBlock), 0, st, src,
+                               stream_bytes, pps, elem_bytes, slots, meta);
         SK_CHECK_LAUNCH();
         hipLaunchKernelGGL(sk::deflate_stream_kernel, dim3((unsigned)n_streams), dim3(sk::kDfBlock), 0, st, meta,
                            stream_bytes, pps, all_zero != nullptr ? 1 : 0, prefix, stream_size, stream_adler, stream_zero);
@@ -540,5 +740,63 @@ extern "C" int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t str
                            prefix, stream_size, stream_adler, dst_offsets, dst);
         SK_CHECK_LAUNCH();
     }
+    return SK_OK;
+}
+
+extern "C" int sk_deflate_streams(const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes, uint8_t* dst,
+                                  int64_t* dst_offsets, uint8_t* all_zero, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    return df_streams("sk_deflate_streams", src, n_streams, stream_bytes, elem_bytes, 0, dst, dst_offsets, all_zero,
+                      workspace, workspace_bytes, stream);
+}
+
+extern "C" int sk_deflate_streams_coded(const uint8_t* src, int n_streams, int64_t stream_bytes, int elem_bytes,
+                                        int huffman, uint8_t* dst, int64_t* dst_offsets, uint8_t* all_zero,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    return df_streams("sk_deflate_streams_coded", src, n_streams, stream_bytes, elem_bytes, huffman, dst, dst_offsets,
+                      all_zero, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sk_deflate_code_host(const uint32_t* freq, int n_symbols, int limit, uint8_t* lengths, uint16_t* codes) {
+    SK_CHECK_ARG(freq != nullptr && lengths != nullptr && codes != nullptr, "sk_deflate_code_host: NULL argument");
+    SK_CHECK_ARG(n_symbols >= 1 && n_symbols <= sk_dfc::kDfcLit, "sk_deflate_code_host: n_symbols = %d outside [1, 286]",
+                 n_symbols);
+    SK_CHECK_ARG(limit >= 1 && limit <= 15, "sk_deflate_code_host: limit = %d outside [1, 15]", limit);
+    unsigned long long sum = 0;
+    int used = 0;
+    for (int s = 0; s < n_symbols; ++s) {
+        sum += freq[s];
+        used += freq[s] != 0;
+    }
+    SK_CHECK_ARG(sum <= 0xffffffffull, "sk_deflate_code_host: the counts add up to %llu, at most 2^32 - 1", sum);
+    SK_CHECK_ARG(used <= (1 << limit), "sk_deflate_code_host: %d used symbols do not fit a code of at most %d bits", used,
+                 limit);
+    sk_dfc::DfcWork w;
+    const int m = sk_dfc::dfc_sort(freq, n_symbols, w.order);
+    sk_dfc::dfc_lengths(freq, n_symbols, m, limit, w, lengths);
+    sk_dfc::dfc_codes(lengths, n_symbols, w, codes);
+    return SK_OK;
+}
+
+extern "C" int sk_deflate_header_host(const uint8_t* lit_lengths, const uint8_t* dist_lengths, int bfinal, uint8_t* out,
+                                      size_t out_bytes, int64_t* n_bits) {
+    SK_CHECK_ARG(lit_lengths != nullptr && dist_lengths != nullptr && out != nullptr && n_bits != nullptr,
+                 "sk_deflate_header_host: NULL argument");
+    SK_CHECK_ARG(bfinal == 0 || bfinal == 1, "sk_deflate_header_host: bfinal = %d, must be 0 or 1", bfinal);
+    SK_CHECK_ARG(out_bytes >= (size_t)sk_dfc::kDfcHeaderBytes, "sk_deflate_header_host: out of %zu bytes, need %d", out_bytes,
+                 sk_dfc::kDfcHeaderBytes);
+    for (int s = 0; s < sk_dfc::kDfcLit; ++s)
+        SK_CHECK_ARG(lit_lengths[s] <= 15, "sk_deflate_header_host: lit_lengths[%d] = %d above 15", s, lit_lengths[s]);
+    for (int s = 0; s < sk_dfc::kDfcDist; ++s)
+        SK_CHECK_ARG(dist_lengths[s] <= 15, "sk_deflate_header_host: dist_lengths[%d] = %d above 15", s, dist_lengths[s]);
+    sk_dfc::DfcWork w;
+    sk_dfc::DfcHdr h;
+    sk_dfc::dfc_header_plan(lit_lengths, dist_lengths, w, h);
+    for (int i = 0; i < sk_dfc::kDfcHeaderBytes; ++i) out[i] = 0;
+    unsigned at = 0;
+    sk_dfc::dfc_header_emit(h, bfinal, [&](unsigned val, int nb) {
+        for (int b = 0; b < nb; ++b, ++at) out[at >> 3] |= (uint8_t)(((val >> b) & 1u) << (at & 7));
+    });
+    *n_bits = (int64_t)at;
     return SK_OK;
 }

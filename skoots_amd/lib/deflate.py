@@ -4,7 +4,8 @@ A device tensor goes through ``sk_deflate_streams`` (skoots_amd/csrc/deflate.hip
 one read-back of the offsets, one device-to-host copy of exactly the compressed bytes.  A CPU tensor goes through the
 stdlib's ``zlib.compress(row, 1)``, which is what the host writers always did, so that everything above this module
 (chunking, store layout, TIFF directories) runs and is tested without a GPU.  Both give complete RFC 1950 streams; the
-bytes differ (the device encoder uses the fixed Huffman code and its own match search), what they decode to does not.
+bytes differ (the device encoder has its own match search and codes every 16 KiB piece with the fixed Huffman code, or
+with ``huffman="dynamic"`` with the smaller of that and a code built for the piece), what they decode to does not.
 
 ``inflate_streams`` is the way back: streams from any deflate encoder go to the device compressed and are inflated there
 by ``sk_inflate_streams`` (skoots_amd/csrc/inflate.hip), one wave per stream; for ``device="cpu"`` the stdlib's zlib does
@@ -32,14 +33,28 @@ def device_bytes_per_stream(stream_bytes: int) -> int:
     return bound(stream_bytes) + int(_ffi.lib.sk_deflate_workspace_bytes(1, int(stream_bytes)))
 
 
+HUFFMAN_MODES = {"fixed": 0, "dynamic": 1}
+
+
+def huffman_mode(huffman: str) -> int:
+    """``"fixed" | "dynamic"`` -> the ``huffman`` argument of ``sk_deflate_streams_coded``; anything else raises."""
+    if not isinstance(huffman, str) or huffman not in HUFFMAN_MODES:
+        raise ValueError(f"huffman = {huffman!r}, must be 'fixed' or 'dynamic'")
+    return HUFFMAN_MODES[huffman]
+
+
 def deflate_streams(t: torch.Tensor, elem_bytes: int = 1, skip_zero: bool = False,
-                    timings: Optional[Dict[str, float]] = None) -> List[Optional[bytes]]:
+                    timings: Optional[Dict[str, float]] = None, huffman: str = "fixed") -> List[Optional[bytes]]:
     """One zlib stream per row of the ``(n, L)`` uint8 tensor ``t``.
 
     ``elem_bytes`` (1, 2 or 4) tells the device encoder which match distances are worth trying; it never changes the
     format.  With ``skip_zero`` a row of zero bytes gives ``None`` (on the device its stream is neither compacted nor
     copied).  ``timings`` (optional) accumulates ``kernel_s`` (device events), ``d2h_s`` and ``compressed_bytes``.
+    ``huffman``: ``"fixed"`` codes every piece with the fixed code of RFC 1951 (or stores it); ``"dynamic"`` also builds
+    a code for every piece and writes the smallest form, so no stream gets longer.  A CPU tensor is compressed by zlib
+    either way.
     """
+    mode = huffman_mode(huffman)
     if t.ndim != 2 or t.dtype != torch.uint8:
         raise ValueError(f"deflate_streams takes a (n, L) uint8 tensor, got {tuple(t.shape)} {t.dtype}")
     if elem_bytes not in (1, 2, 4):
@@ -65,8 +80,13 @@ def deflate_streams(t: torch.Tensor, elem_bytes: int = 1, skip_zero: bool = Fals
     if timings is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record(torch.cuda.current_stream(dev))
-    _ffi.check(_ffi.lib.sk_deflate_streams(_ffi.ptr(t), n, length, elem_bytes, _ffi.ptr(dst), _ffi.ptr(offsets),
-                                           _ffi.ptr(zero), _ffi.ptr(ws), ws_bytes, _ffi.stream_ptr(dev)))
+    if mode == 0:
+        _ffi.check(_ffi.lib.sk_deflate_streams(_ffi.ptr(t), n, length, elem_bytes, _ffi.ptr(dst), _ffi.ptr(offsets),
+                                               _ffi.ptr(zero), _ffi.ptr(ws), ws_bytes, _ffi.stream_ptr(dev)))
+    else:
+        _ffi.check(_ffi.lib.sk_deflate_streams_coded(_ffi.ptr(t), n, length, elem_bytes, mode, _ffi.ptr(dst),
+                                                     _ffi.ptr(offsets), _ffi.ptr(zero), _ffi.ptr(ws), ws_bytes,
+                                                     _ffi.stream_ptr(dev)))
     if timings is not None:
         ev1.record(torch.cuda.current_stream(dev))
     off = offsets.cpu().tolist()   # the one synchronisation

@@ -247,6 +247,11 @@ def _write_mask_tif(path: str, mask_zxy: np.ndarray) -> None:
 # through the host readers and an upload.  The results are the same; DESIGN.md section 16 has the timings behind the default.
 READ_ON_DEVICE = False
 
+# The Huffman code of the chunks and pages eval() writes: "fixed" (RFC 1951's fixed code) or "dynamic" (per 16 KiB piece
+# the smaller of that and a code built for the piece).  The files inflate to the same arrays; DESIGN.md section 15 has the
+# sizes and timings behind the default.
+OUTPUT_HUFFMAN = "fixed"
+
 
 def _to_f32(t: torch.Tensor) -> torch.Tensor:
     """Integer samples as float32, what ``ndarray.astype(np.float32)`` gives; uint16 goes through its bit pattern."""
@@ -262,7 +267,7 @@ def _cfg_get(cfg, section: str, key: str, default=None):
 
 @torch.inference_mode()
 def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16",
-         read_on_device: Optional[bool] = None) -> None:
+         read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None) -> None:
     """Evaluates SKOOTS on an arbitrary image (drop-in for ``skoots.lib.eval.eval``).
 
     ``precision`` (not in the reference's signature; keyword with the reference's behaviour as default): "fp16" = what the
@@ -281,11 +286,19 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     stores are read by ``tiff.read_stack`` / ``zarr_store.load_device`` (compressed bytes go to the device and are inflated
     there) instead of the host readers + an upload; the results do not depend on it.
 
+    ``output_huffman`` (keyword, not in the reference's signature; ``None`` = the module's ``OUTPUT_HUFFMAN``):
+    ``"fixed"`` or ``"dynamic"``, the code of the device deflate encoder that writes the two stores and the TIFF.  The
+    files differ in size only: they inflate to the same arrays, and the ``.zarray`` text is the same.
+
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
     ``SKOOTS.VECTOR_SCALING`` and ``MODEL.*``), ``model_state_dict`` and optionally
     ``dataset_mean`` / ``dataset_std`` (eval.py:51-55, 87-88, 99, 117-118).
     """
     from .. import unet
+    from . import deflate
+    if output_huffman is None:
+        output_huffman = OUTPUT_HUFFMAN   # looked up now, so that setting the module's switch takes effect
+    deflate.huffman_mode(output_huffman)
     start = time.time()
     logging.info(f"Loading model file: {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -353,8 +366,9 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     torch.cuda.synchronize(device)
     dt = time.time() - benchmark_start
 
-    zarr_store.save_device(skel_path, skeleton.unsqueeze(0))  # deflated on the device: only compressed bytes leave it
-    zarr_store.save_device(vec_path, vectors)
+    # deflated on the device: only compressed bytes leave it
+    zarr_store.save_device(skel_path, skeleton.unsqueeze(0), huffman=output_huffman)
+    zarr_store.save_device(vec_path, vectors, huffman=output_huffman)
     logging.info("writing benchmark information")
     with open(base + "_skoots_benchmark.txt", "w") as f:  # eval.py:286-295
         f.write("SKOOTS Segmentation Benchmark:\n")
@@ -364,6 +378,6 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
                 f"{torch.cuda.max_memory_allocated(device)})\n\n")
     print("DONE")
     logging.info(f"saving to tif file at {base}_instance_mask.tif")
-    tiff.write_label_stack(base + "_instance_mask.tif", inst.permute(2, 0, 1))
+    tiff.write_label_stack(base + "_instance_mask.tif", inst.permute(2, 0, 1), huffman=output_huffman)
     elapsed = time.time() - start
     logging.info(f"DONE: Process took {elapsed} seconds, {elapsed / 60} minutes, {elapsed / (60 ** 2)}, hours")

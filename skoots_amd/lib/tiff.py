@@ -244,13 +244,15 @@ def _page_rows(pages):
 
 
 def _write_pages(path: str, rows, height: int, width: int, bits: int, sample_format: int,
-                 budget_bytes: int = WRITE_STACK_BUDGET, timings=None, samples: int = 1) -> None:
+                 budget_bytes: int = WRITE_STACK_BUDGET, timings=None, samples: int = 1, huffman: str = "fixed") -> None:
     """``rows``: (Z, page_bytes) uint8 tensor on either device, page z = row z in C order, little-endian samples;
-    ``samples`` = 3 / 4: chunky RGB / RGBA pixels of 8-bit samples."""
+    ``samples`` = 3 / 4: chunky RGB / RGBA pixels of 8-bit samples; ``huffman``: see ``deflate.deflate_streams``."""
     import time
 
     from . import deflate
     n_pages, page_bytes = int(rows.shape[0]), int(rows.shape[1])
+    # the keyword goes down only when it is not the default: the call is then the one it always was
+    coded = {"huffman": huffman} if deflate.huffman_mode(huffman) else {}
     if samples not in (1, 3, 4) or (samples > 1 and (bits, sample_format) != (8, 1)):
         raise ValueError(f"{samples} samples of {bits} bits per pixel: pages are grey, or 8-bit RGB / RGBA")
     if n_pages < 1 or height * width * samples * (bits // 8) != page_bytes:
@@ -259,7 +261,7 @@ def _write_pages(path: str, rows, height: int, width: int, bits: int, sample_for
     batch = max(1, int(budget_bytes) // (page_bytes + deflate.device_bytes_per_stream(page_bytes)))
     strips = []
     for lo in range(0, n_pages, batch):
-        strips += deflate.deflate_streams(rows[lo:lo + batch], elem_bytes=bits // 8, timings=timings)
+        strips += deflate.deflate_streams(rows[lo:lo + batch], elem_bytes=bits // 8, timings=timings, **coded)
     # layout: header, the strips (each on an even offset), then one directory per page
     offsets, at = [], 8
     for s in strips:
@@ -302,7 +304,7 @@ def _write_pages(path: str, rows, height: int, width: int, bits: int, sample_for
         timings["file_s"] = timings.get("file_s", 0.0) + time.perf_counter() - t0
 
 
-def write_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timings=None) -> None:
+def write_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timings=None, huffman: str = "fixed") -> None:
     """(Z, H, W) uint8 / uint16 / int32 tensor (either device) or array -> multi-page TIFF with Adobe-deflate strips;
     (Z, H, W, C) uint8 with C = 3 / 4 -> RGB / RGBA pages (PhotometricInterpretation 2, SamplesPerPixel C, chunky, C
     BitsPerSample shorts out of line, ExtraSamples 2 for C = 4), and (Z, H, W, 1) is written as grey.
@@ -310,12 +312,15 @@ def write_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timing
     One directory and one strip per page; tags 256, 257, 258, 259 (= 8), 262 (= 1), 273, 277, 278, 279, 339.  Every
     strip is one zlib stream from :func:`skoots_amd.lib.deflate.deflate_streams`, made on the tensor's device in batches
     of pages that keep page data + encoder buffers under ``budget_bytes``; the compressed strips are held on the host
-    until the layout is known.  A file past 2**32 - 1 bytes raises ``ValueError`` before anything is written."""
+    until the layout is known.  A file past 2**32 - 1 bytes raises ``ValueError`` before anything is written.
+    ``huffman`` (``"fixed" | "dynamic"``) is the code of the strips made on a device, as in ``deflate_streams``."""
     rows, bits, fmt, spp = _page_rows(pages)
-    _write_pages(path, rows, int(pages.shape[1]), int(pages.shape[2]), bits, fmt, budget_bytes, timings, samples=spp)
+    _write_pages(path, rows, int(pages.shape[1]), int(pages.shape[2]), bits, fmt, budget_bytes, timings, samples=spp,
+                 huffman=huffman)
 
 
-def write_float_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timings=None) -> None:
+def write_float_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, timings=None,
+                      huffman: str = "fixed") -> None:
     """(Z, H, W) float32 tensor (either device) or array -> multi-page TIFF of 32-bit IEEE samples (SampleFormat 3),
     laid out like ``write_stack``'s pages: one Adobe-deflate strip and one directory per page.  ``write_stack`` and the
     readers of this module keep to integer samples; ImageJ / Fiji and tifffile open these pages as 32-bit float."""
@@ -325,10 +330,10 @@ def write_float_stack(path: str, pages, budget_bytes: int = WRITE_STACK_BUDGET, 
         raise ValueError(f"write_float_stack takes (Z, H, W) float32, got {tuple(pages.shape)} {pages.dtype}")
     t = torch.from_numpy(np.ascontiguousarray(pages)) if is_np else pages.contiguous()
     rows = t.view(torch.uint8).reshape(t.shape[0], -1) if t.numel() else torch.zeros((t.shape[0], 0), dtype=torch.uint8)
-    _write_pages(path, rows, int(t.shape[1]), int(t.shape[2]), 32, 3, budget_bytes, timings)
+    _write_pages(path, rows, int(t.shape[1]), int(t.shape[2]), 32, 3, budget_bytes, timings, huffman=huffman)
 
 
-def write_label_stack(path: str, labels_zxy, timings=None) -> None:
+def write_label_stack(path: str, labels_zxy, timings=None, huffman: str = "fixed") -> None:
     """(Z, X, Y) int32 label tensor -> TIFF, uint16 pages while every label is below 65536, int32 otherwise (the
     narrowing ``eval._write_mask_tif`` applies on the host), without leaving the tensor's device."""
     import torch
@@ -338,6 +343,6 @@ def write_label_stack(path: str, labels_zxy, timings=None) -> None:
     if t.numel() == 0 or int(t.max()) < 65536:
         # the low two bytes of every label: int16 storage holds the uint16 bit patterns
         rows = t.to(torch.int16).view(torch.uint8).reshape(t.shape[0], -1)
-        _write_pages(path, rows, int(t.shape[1]), int(t.shape[2]), 16, 1, timings=timings)
+        _write_pages(path, rows, int(t.shape[1]), int(t.shape[2]), 16, 1, timings=timings, huffman=huffman)
     else:
-        write_stack(path, t, timings=timings)
+        write_stack(path, t, timings=timings, huffman=huffman)

@@ -68,17 +68,21 @@ SAVE_DEVICE_BUDGET = 256 << 20  # bytes of staging + encoder buffers per batch o
 
 
 def save_device(path: str, tensor, chunks: Optional[Sequence[int]] = None, budget_bytes: int = SAVE_DEVICE_BUDGET,
-                timings=None) -> None:
+                timings=None, huffman: str = "fixed") -> None:
     """The store ``save(path, array, compressor="zlib")`` writes -- same default chunks, same ``.zarray`` text, edge
     chunks zero-padded, fill-value chunks left out -- from a torch tensor on either device (a numpy array is taken as a
     CPU tensor).  Chunks are copied into a ``(n, chunk_bytes)`` staging buffer with torch indexing on the tensor's device
     and deflated there in batches: one batch takes about three times its chunks' bytes (staging, the encoder's worst-case
     output, its workspace), and a batch is sized to keep that under ``budget_bytes`` (256 MiB by default; at least one
     chunk), so the memory this takes does not grow with the array.  On a CPU tensor the files are byte for byte
-    those of ``save``; on a device tensor the chunk files hold other bytes that inflate to the same chunks."""
+    those of ``save``; on a device tensor the chunk files hold other bytes that inflate to the same chunks.
+    ``huffman`` (``"fixed" | "dynamic"``) goes to ``deflate.deflate_streams``: it changes the chunk files' bytes on a
+    device tensor, never the ``.zarray`` text or what the chunks inflate to."""
     import torch
 
     from . import deflate
+    # refused before the store is touched; the keyword goes down only when it is not the default
+    coded = {"huffman": huffman} if deflate.huffman_mode(huffman) else {}
     t = torch.from_numpy(np.ascontiguousarray(tensor)) if isinstance(tensor, np.ndarray) else tensor
     np_dtype = torch.empty(0, dtype=t.dtype).numpy().dtype
     if chunks is None:
@@ -115,7 +119,7 @@ def save_device(path: str, tensor, chunks: Optional[Sequence[int]] = None, budge
                 rows = rows[torch.tensor(keep, device=rows.device)]
         streams = deflate.deflate_streams(rows.contiguous().view(torch.uint8).view(len(part), chunk_bytes),
                                           elem_bytes=item if item in (1, 2, 4) else 1, skip_zero=not by_value,
-                                          timings=timings)
+                                          timings=timings, **coded)
         t0 = time.perf_counter()
         for idx, stream in zip(part, streams):
             if stream is None:

@@ -142,12 +142,19 @@ def _check_pages(f: str, shape, plan: ConversionPlan) -> None:
                          "written (grey pages are uint8 / uint16 / int32, RGB(A) pages uint8)")
 
 
-def convert(base_dir: str, device=None, read_on_device: Optional[bool] = None) -> List[str]:
+def convert(base_dir: str, device=None, read_on_device: Optional[bool] = None,
+            huffman: Optional[str] = None) -> List[str]:
     """Converts every store / tensor ``discover(base_dir)`` finds to ``os.path.splitext(f)[0] + ".tif"``; returns the
     files written.  ``device``: where the work happens (default: the current GPU if there is one, else ``"cpu"``).
     ``read_on_device``: stores are read with ``zarr_store.load_device`` (chunks inflated on the device) instead of
-    ``zarr_store.load`` + upload; ``None`` = ``skoots_amd.lib.eval.READ_ON_DEVICE`` at the time of the call."""
-    from ..lib import tiff, zarr_store
+    ``zarr_store.load`` + upload; ``None`` = ``skoots_amd.lib.eval.READ_ON_DEVICE`` at the time of the call.
+    ``huffman``: the code of the strips ``tiff.write_stack`` makes on a device (``"fixed" | "dynamic"``); ``None`` =
+    ``skoots_amd.lib.eval.OUTPUT_HUFFMAN`` at the time of the call."""
+    from ..lib import deflate, tiff, zarr_store
+    if huffman is None:
+        from ..lib import eval as E
+        huffman = E.OUTPUT_HUFFMAN
+    deflate.huffman_mode(huffman)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     device = torch.device(device)
@@ -188,6 +195,6 @@ def convert(base_dir: str, device=None, read_on_device: Optional[bool] = None) -
         if pages.ndim == 4 and pages.shape[3] == 1:
             # difference 4: (Z, X, Y, 1) is written as grey pages; what tifffile makes of that shape is not pinned
             pages = pages.squeeze(3)
-        tiff.write_stack(new_file, pages)    # difference 3: deflate strips; the reference leaves 4-D outputs uncompressed
+        tiff.write_stack(new_file, pages, huffman=huffman)    # difference 3: deflate strips; the reference leaves 4-D outputs uncompressed
         written.append(new_file)
     return written

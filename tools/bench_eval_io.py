@@ -10,7 +10,12 @@ per output: wall time, and for (B) the encoder's time (device events), the devic
 bytes, the file writes, and the bytes on disk.  Both paths write into --dir; with --verify the stores and the TIFF of
 (B) are read back and compared with the arrays.
 
-    python tools/bench_eval_io.py --dir /tmp/evalio --out profiles/eval_io.json
+--huffman names the codes of the device encoder to measure (fixed, dynamic, or both).  With both, the modes run in one
+call and alternate (fixed, dynamic, fixed, ...), each warmed up once, and the median of --repeats is taken per mode:
+"modes" holds the figures of each, "dynamic_vs_fixed" the bytes saved per output next to the encoder time it costs and
+the copy and write time it saves.  "device_path" stays the first mode named.
+
+    python tools/bench_eval_io.py --dir /tmp/evalio --huffman fixed dynamic --verify --out profiles/eval_io_bench.json
 """
 import argparse
 import json
@@ -77,15 +82,15 @@ def run_host(arrays, d, device):
     return res
 
 
-def run_device(arrays, d, device):
+def run_device(arrays, d, device, huffman="fixed"):
     from skoots_amd.lib import tiff, zarr_store
     vectors, skeleton, inst = arrays
     res = {}
     for name, path, fn in (
-            ("skeleton", os.path.join(d, "b_skeleton.zarr"), lambda p, tm: zarr_store.save_device(p, skeleton, timings=tm)),
-            ("vectors", os.path.join(d, "b_vectors.zarr"), lambda p, tm: zarr_store.save_device(p, vectors, timings=tm)),
+            ("skeleton", os.path.join(d, "b_skeleton.zarr"), lambda p, tm: zarr_store.save_device(p, skeleton, timings=tm, huffman=huffman)),
+            ("vectors", os.path.join(d, "b_vectors.zarr"), lambda p, tm: zarr_store.save_device(p, vectors, timings=tm, huffman=huffman)),
             ("mask", os.path.join(d, "b_mask.tif"),
-             lambda p, tm: tiff.write_label_stack(p, inst.permute(2, 0, 1), timings=tm))):
+             lambda p, tm: tiff.write_label_stack(p, inst.permute(2, 0, 1), timings=tm, huffman=huffman))):
         tm = {}
         sync(device)
         t0 = time.perf_counter()
@@ -116,6 +121,8 @@ def main():
     ap.add_argument("--device", default="cuda:0", help="'cpu' rehearses the plumbing; its times mean nothing")
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--verify", action="store_true")
+    ap.add_argument("--huffman", nargs="+", choices=("fixed", "dynamic"), default=["fixed"],
+                    help="codes of the device encoder to measure; several alternate within one call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     device = torch.device(args.device)
@@ -127,14 +134,33 @@ def main():
               "shape": list(arrays[2].shape), "tiles": list(args.tiles),
               "raw_bytes": {"vectors": arrays[0].numel() * 2, "skeleton": arrays[1].numel(),
                             "mask": arrays[2].numel() * 2}}
-    run_device(arrays, args.dir, device)   # warm-up: code objects, allocator
-    runs = [run_device(arrays, args.dir, device) for _ in range(args.repeats)]
-    report["device_path"] = {
-        name: {k: (statistics.median(r[name].get(k, 0.0) for r in runs)) for k in
-               ("wall_s", "kernel_s", "d2h_s", "file_s", "bytes", "compressed_bytes")} for name in runs[0]}
-    report["device_path_wall_all"] = {name: [r[name]["wall_s"] for r in runs] for name in runs[0]}
+    modes = list(dict.fromkeys(args.huffman))
+    keys = ("wall_s", "kernel_s", "d2h_s", "file_s", "bytes", "compressed_bytes")
+    for m in modes:
+        run_device(arrays, args.dir, device, m)   # warm-up: code objects, allocator
+    runs = {m: [] for m in modes}
+    for _ in range(args.repeats):
+        for m in modes:                           # alternating, so that drift hits the modes alike
+            runs[m].append(run_device(arrays, args.dir, device, m))
+    report["repeats"] = args.repeats
+    report["modes"] = {m: {name: {k: statistics.median(r[name].get(k, 0.0) for r in runs[m]) for k in keys}
+                           for name in runs[m][0]} for m in modes}
+    report["modes_kernel_all"] = {m: {name: [r[name].get("kernel_s", 0.0) for r in runs[m]] for name in runs[m][0]}
+                                  for m in modes}
+    report["device_path"] = report["modes"][modes[0]]
+    report["device_path_wall_all"] = {name: [r[name]["wall_s"] for r in runs[modes[0]]] for name in runs[modes[0]][0]}
+    if "fixed" in modes and "dynamic" in modes:
+        f, d = report["modes"]["fixed"], report["modes"]["dynamic"]
+        report["dynamic_vs_fixed"] = {
+            name: {"bytes_ratio": d[name]["bytes"] / f[name]["bytes"], "bytes_saved": f[name]["bytes"] - d[name]["bytes"],
+                   "kernel_s_added": d[name]["kernel_s"] - f[name]["kernel_s"],
+                   "d2h_s_saved": f[name]["d2h_s"] - d[name]["d2h_s"], "file_s_saved": f[name]["file_s"] - d[name]["file_s"],
+                   "wall_s_saved": f[name]["wall_s"] - d[name]["wall_s"]} for name in f}
     if args.verify:
-        report["verified"] = verify(arrays, args.dir)
+        report["verified"] = {}
+        for m in modes:                           # the files of the mode that ran last are on disk: write each again
+            run_device(arrays, args.dir, device, m)
+            report["verified"][m] = verify(arrays, args.dir)
     if not args.skip_host:
         report["host_path"] = run_host(arrays, args.dir, device)
         report["speedup_wall"] = {n: report["host_path"][n]["wall_s"] / report["device_path"][n]["wall_s"]
