@@ -35,6 +35,7 @@ extern "C" {
 #define SK_I16 2
 #define SK_I32 3
 #define SK_U8 4
+#define SK_U16 5 /* sk_pool_volume only */
 
 const char* sk_last_error(void);
 int sk_abi_version(void);
@@ -995,6 +996,30 @@ int sk_blosc_decode_host(const uint8_t* frame, int64_t frame_bytes, uint8_t* dst
  * No workspace.  Arguments are checked before the launch. */
 int sk_convert_pages_u8(const void* src, int src_dtype, int mode, int C, int X, int Y, int Z, uint8_t* dst,
                         void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Multiscale pyramids: one pooling pass per level (ABI 31)
+ * ------------------------------------------------------------------------ */
+
+#define SK_POOL_MODE 0
+#define SK_POOL_MEAN 1
+#define SK_POOL_MAX 2
+
+/* src: contiguous (X, Y, Z) of dtype, Z innermost; dst: contiguous (ceil(X / fx), ceil(Y / fy), ceil(Z / fz)) of the
+ * same dtype; every factor 1 or 2, not all 1.  The block of an output voxel (xo, yo, zo) is the source voxels
+ * [xo fx, xo fx + fx) x [yo fy, yo fy + fy) x [zo fz, zo fz + fz) that exist: at the far edge of an odd extent it is
+ * clipped, so it holds n = 1, 2, 4 or 8 voxels.
+ *   how = SK_POOL_MODE  dtype SK_I32 / SK_I16 / SK_U8: the value that occurs most often in the block; among values of
+ *                       the same count the smallest in the dtype's order (signed for int32 / int16).  sparse != 0: zeros
+ *                       are not counted unless the whole block is zero.  The result is defined by the counts of the
+ *                       block's values alone, so it does not depend on the order in which a lane visits the block.
+ *   how = SK_POOL_MEAN  dtype SK_U8 / SK_U16: (sum + n / 2) / n in integer arithmetic (round half up); sparse ignored.
+ *   how = SK_POOL_MAX   dtype SK_U8 / SK_U16: the largest value; sparse ignored.
+ * One launch, no workspace, nothing allocated; the same bits on every run.  Every argument is checked before the launch
+ * (SK_ERR_ARG): null pointers, extents < 1, factors, how, the dtype of the reduction, element alignment,
+ * ceil(X / fx) ceil(Y / fy) < 2^31. */
+int sk_pool_volume(const void* src, int dtype, int X, int Y, int Z, int fx, int fy, int fz, int how, int sparse,
+                   void* dst, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Instance measurements: volume, box, moments and face area of every instance

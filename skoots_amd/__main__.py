@@ -2,7 +2,8 @@
 the reference CLI (skoots/__main__.py:19-46, 78-98), and ``--skeletonize-train-data PATH [--mask-filter .labels]
 [--anisotropyXY a] [--anisotropyZ b]`` (skoots/__main__.py:49-68, 101-106), and ``--convert PATH``: eval's zarr stores
 and ``.trch`` tensors under PATH -> TIFF stacks, no eval (skoots/__main__.py:70-74, 84, 108-109).  With it every switch of
-the reference's main command exists here."""
+the reference's main command exists here.  ``--pyramid`` (not in the reference) makes eval also write
+``<base>_skoots.ome.zarr``, the multiscale OME-Zarr group of image, instance mask and skeleton."""
 import argparse
 import glob
 import logging
@@ -23,6 +24,9 @@ def build_parser() -> argparse.ArgumentParser:
     eval_args.add_argument("--output-huffman", choices=("fixed", "dynamic"), default=None,
                            help="Huffman code of the device deflate encoder that writes the zarr chunks and TIFF pages "
                                 "(eval and --convert); default: skoots_amd.lib.eval.OUTPUT_HUFFMAN")
+    eval_args.add_argument("--pyramid", action="store_true",
+                           help="also writes <base>_skoots.ome.zarr: multiscale pyramids of the image, the instance mask "
+                                "and the skeleton as one OME-Zarr group (skoots_amd.utils.pyramid)")
     accessory_args = parser.add_argument_group("scripting arguments")
     accessory_args.add_argument("--skeletonize-train-data",
                                 help="calculate skeletons of training data (a label TIFF or a directory of them)")
@@ -61,7 +65,9 @@ def main(argv=None):
     from skoots_amd.lib.eval import eval as sk_eval
     files = sorted(glob.glob(args.image + "/*.tif")) if os.path.isdir(args.image) else [args.image]
     for f in files:
-        sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached, output_huffman=args.output_huffman)
+        extra = {"pyramid": True} if args.pyramid else {}   # the keyword goes down only when it is set
+        sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached, output_huffman=args.output_huffman,
+                **extra)
 
 
 if __name__ == "__main__":

@@ -211,6 +211,7 @@ _SIGS = {
     "sk_blosc_plan_host": (i32, [vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "sk_blosc_decode_host": (i32, [vp, i64, vp, i64, vp]),
     "sk_convert_pages_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "sk_pool_volume": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "sk_instance_stats_row_values": (i32, [i32]),
     "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "sk_instance_mesh_cells": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp]),

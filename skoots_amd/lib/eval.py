@@ -267,7 +267,7 @@ def _cfg_get(cfg, section: str, key: str, default=None):
 
 @torch.inference_mode()
 def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16",
-         read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None) -> None:
+         read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None, pyramid: bool = False) -> None:
     """Evaluates SKOOTS on an arbitrary image (drop-in for ``skoots.lib.eval.eval``).
 
     ``precision`` (not in the reference's signature; keyword with the reference's behaviour as default): "fp16" = what the
@@ -289,6 +289,14 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     ``output_huffman`` (keyword, not in the reference's signature; ``None`` = the module's ``OUTPUT_HUFFMAN``):
     ``"fixed"`` or ``"dynamic"``, the code of the device deflate encoder that writes the two stores and the TIFF.  The
     files differ in size only: they inflate to the same arrays, and the ``.zarray`` text is the same.
+
+    ``pyramid`` (keyword, not in the reference's signature; off by default, and without it every output is byte for
+    byte what it was): after the mask is written, also writes ``<base>_skoots.ome.zarr``, one OME-Zarr (NGFF 0.4) group
+    of multiscale pyramids made from the tensors still on the device (``utils.pyramid.write_ome_zarr``): the input
+    image (integer samples as read, pooled by the rounded mean), ``labels/instances`` (the instance mask, by the most
+    frequent id, sparse off) and ``labels/skeleton`` (by the maximum).  The voxel spacing is the checkpoint's
+    ``SKOOTS.ANISOTROPY``, (1, 1, 3) without one; ``output_huffman`` applies.  An image that is not uint8 / uint16 (or
+    signed with values in 0 .. 65535) is refused before the model runs.
 
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
     ``SKOOTS.VECTOR_SCALING`` and ``MODEL.*``), ``model_state_dict`` and optionally
@@ -322,6 +330,7 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         c, x, y, z = stack.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {stack.dtype}")
         dev_img = _to_f32(stack[0]).to(torch.float16).contiguous()  # eval.py:80
+        raw_img = stack[0] if pyramid else None
         # the statistics fallback stays the CPU reduction over the same fp16 values: the image comes back for it only
         img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None
     else:
@@ -333,6 +342,20 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {image.dtype}")
         img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16)  # eval.py:80
         dev_img = None
+        raw_img = None
+        if pyramid:     # the samples as read: uint16 through its bit pattern
+            raw = np.ascontiguousarray(image[0])
+            raw_img = (torch.from_numpy(raw.view(np.int16)).view(torch.uint16) if raw.dtype == np.uint16
+                       else torch.from_numpy(raw))
+    if pyramid:
+        from ..utils.pyramid import check_spacing
+        from .morphology import check_pool_volume
+        check_pool_volume(raw_img, "mean", "image")   # refused by name before the model runs
+        try:
+            aniso = _cfg_get(cfg, "SKOOTS", "ANISOTROPY", None)
+        except (KeyError, AttributeError):
+            aniso = None
+        spacing = check_spacing(aniso if aniso is not None else (1.0, 1.0, 3.0))
     mean = checkpoint["dataset_mean"] if "dataset_mean" in checkpoint else img16.mean()  # eval.py:87
     std = checkpoint["dataset_std"] if "dataset_std" in checkpoint else img16.std()  # eval.py:88
     scale = [int(v) for v in _cfg_get(cfg, "SKOOTS", "VECTOR_SCALING")]  # eval.py:99
@@ -379,5 +402,10 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     print("DONE")
     logging.info(f"saving to tif file at {base}_instance_mask.tif")
     tiff.write_label_stack(base + "_instance_mask.tif", inst.permute(2, 0, 1), huffman=output_huffman)
+    if pyramid:
+        from ..utils.pyramid import write_ome_zarr
+        logging.info(f"saving multiscale pyramids to {base}_skoots.ome.zarr")
+        write_ome_zarr(base + "_skoots.ome.zarr", spacing, image=raw_img.to(device),
+                       labels={"instances": inst, "skeleton": (skeleton, "max")}, huffman=output_huffman)
     elapsed = time.time() - start
     logging.info(f"DONE: Process took {elapsed} seconds, {elapsed / 60} minutes, {elapsed / (60 ** 2)}, hours")

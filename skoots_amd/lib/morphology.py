@@ -7,7 +7,8 @@ transform of every instance of a label volume, which the 
 ``label_components`` the connected pieces of every instance at once, which it does not have
 either, nor ``nearest_label``, the nearest instance of every voxel and its distance, nor
 ``local_thickness``, the radius of the largest ball inside the instance that holds the voxel, nor
-``geodesic_assign``, the nearest seed of every voxel along paths inside its instance."""
+``geodesic_assign``, the nearest seed of every voxel along paths inside its instance, nor
+``pool``, one level of a multiscale pyramid by mode, mean or max."""
 from __future__ import annotations
 
 import ctypes as C
@@ -593,3 +594,140 @@ def skeletonize(image: Tensor) -> Tensor:
         p = points.long()
         out[p[:, 0], p[:, 1], p[:, 2]] = True
     return out
+
+
+# ---- one level of a multiscale pyramid ----
+
+POOL_HOW = {"mode": 0, "mean": 1, "max": 2}     # SK_POOL_MODE / _MEAN / _MAX of include/skoots_hip.h
+_SK_U16 = 5                                     # SK_U16: the dtype code only sk_pool_volume takes
+_POOL_SIGNED = (torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def pool_factors(factors) -> Tuple[int, int, int]:
+    """(fx, fy, fz) of ``pool``: three integers, each 1 or 2, not all 1."""
+    try:
+        f = tuple(factors)
+    except TypeError:
+        raise ValueError(f"factors must be three integers (fx, fy, fz), each 1 or 2, got {factors!r}") from None
+    if len(f) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in (1, 2) for v in f):
+        raise ValueError(f"factors must be three integers (fx, fy, fz), each 1 or 2, got {factors!r}")
+    f = tuple(int(v) for v in f)
+    if f == (1, 1, 1):
+        raise ValueError("factors (1, 1, 1) pool nothing: at least one factor must be 2")
+    return f
+
+
+def check_pool_volume(volume, how: str, name: str = "volume") -> Tuple[int, int, int]:
+    """What ``pool`` takes, checked on the tensor's description alone, before any device is touched; the (X, Y, Z) of it.
+    ``how="mode"``: int32, int16 or uint8.  ``how="mean"``: uint8 or uint16, or a signed integer dtype under the
+    convention of ``validate.lib.instance_intensity`` (values in 0 .. 65535, checked when it is pooled).  ``how="max"``:
+    uint8 or uint16.  Float volumes are refused by name."""
+    if how not in POOL_HOW:
+        raise ValueError(f"how = {how!r}, must be 'mode', 'mean' or 'max'")
+    if not isinstance(volume, Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(volume).__name__}")
+    dt = volume.dtype
+    if dt.is_floating_point or dt.is_complex or dt == torch.bool:
+        raise TypeError(f"{name} is {dt}: float, complex and bool volumes are not pooled, the reductions are exact integer "
+                        "work (labels int32 / int16 / uint8, images uint8 / uint16)")
+    u16 = getattr(torch, "uint16", torch.uint8)
+    allowed = {"mode": (torch.int32, torch.int16, torch.uint8), "mean": (torch.uint8, u16) + _POOL_SIGNED,
+               "max": (torch.uint8, u16)}[how]
+    if dt not in allowed:
+        raise TypeError(f"{name} is {dt}: how={how!r} takes " +
+                        {"mode": "int32, int16 or uint8", "mean": "uint8 or uint16 (or a signed integer dtype with values "
+                         "in 0 .. 65535)", "max": "uint8 or uint16"}[how])
+    s = tuple(int(v) for v in volume.shape)
+    s = s[1:] if len(s) == 4 and s[0] == 1 else s
+    if len(s) != 3 or min(s) < 1:
+        raise ValueError(f"{name} has the shape {tuple(volume.shape)}: it must be (X, Y, Z) or (1, X, Y, Z) with every "
+                         "extent at least 1")
+    return s
+
+
+def pool_source(volume: Tensor, how: str, name: str = "volume") -> Tensor:
+    """The (X, Y, Z) contiguous tensor ``pool`` reads: ``volume`` without its leading 1 and, for ``how="mean"`` on a
+    signed dtype, checked to lie in 0 .. 65535 and converted (int8 to uint8, the others to uint16)."""
+    check_pool_volume(volume, how, name)
+    v = volume[0] if volume.ndim == 4 else volume
+    if how == "mean" and v.dtype in _POOL_SIGNED:
+        low, top = int(v.min().item()), int(v.max().item())
+        if low < 0 or top > 65535:
+            raise ValueError(f"{name} is {v.dtype} with values in {low} .. {top}: only 0 .. 65535 can be averaged")
+        v = v.to(torch.uint8 if v.dtype == torch.int8 else torch.uint16)
+    return v.contiguous()
+
+
+def _pool_host(a: np.ndarray, f, how: str, sparse: bool) -> np.ndarray:
+    """The definitions of ``pool`` as numpy statements on whole arrays: the slots of every block side by side, a
+    validity flag for the slots the far edge clips."""
+    shape_o = tuple(-(-n // k) for n, k in zip(a.shape, f))
+    padded = np.zeros(tuple(n * k for n, k in zip(shape_o, f)), dtype=a.dtype)
+    padded[:a.shape[0], :a.shape[1], :a.shape[2]] = a
+    there = np.zeros(padded.shape, dtype=bool)
+    there[:a.shape[0], :a.shape[1], :a.shape[2]] = True
+    vals, valid = [], []
+    for dx in range(f[0]):
+        for dy in range(f[1]):
+            for dz in range(f[2]):
+                vals.append(padded[dx::f[0], dy::f[1], dz::f[2]])
+                valid.append(there[dx::f[0], dy::f[1], dz::f[2]])
+    wide = [v.astype(np.int64) for v in vals]
+    n = sum(v.astype(np.int64) for v in valid)
+    if how == "mean":
+        total = sum(np.where(ok, v, 0) for v, ok in zip(wide, valid))
+        return ((total + n // 2) // n).astype(a.dtype)
+    if how == "max":
+        low = np.iinfo(a.dtype).min
+        return np.max(np.stack([np.where(ok, v, low) for v, ok in zip(wide, valid)]), axis=0).astype(a.dtype)
+    best_count = np.full(shape_o, -1, dtype=np.int64)
+    best = np.zeros(shape_o, dtype=np.int64)
+    for v, ok in zip(wide, valid):
+        count = sum(((w == v) & okw).astype(np.int64) for w, okw in zip(wide, valid))
+        if sparse:
+            count = np.where(v == 0, 0, count)    # a zero never outvotes; an all-zero block still gives 0
+        count = np.where(ok, count, -1)
+        better = (count > best_count) | ((count == best_count) & (v < best))
+        best = np.where(better, v, best)
+        best_count = np.where(better, count, best_count)
+    return best.astype(a.dtype)
+
+
+def pool(volume: Tensor, factors, how: str = "mode", sparse: bool = False) -> Tensor:
+    """One level of a multiscale pyramid: an (X, Y, Z) or (1, X, Y, Z) integer tensor pooled by ``factors`` (fx, fy,
+    fz), each 1 or 2 and not all 1, on the device it lives on (the reference has no counterpart).
+    The result has the extents ``ceil(n / f)``, the input's rank, dtype and device.  The block of an output voxel is
+    clipped at the far edge of an odd extent to the voxels that exist.
+
+    ``how="mode"`` (int32, int16, uint8: label volumes): the value that occurs most often in the block, ties to the
+    smallest value in the dtype's order; with ``sparse`` zeros are not counted unless the whole block is zero, so thin
+    instances survive.  ``how="mean"`` (uint8, uint16; a signed integer image with values in 0 .. 65535 is converted as
+    ``instance_intensity`` converts it): ``(sum + n // 2) // n`` with ``n`` the clipped block's voxel count.
+    ``how="max"`` (uint8, uint16): the largest value.  ``sparse`` belongs to ``"mode"`` alone.
+
+    On a device tensor this is one launch of ``sk_pool_volume`` on the current stream; on a CPU tensor the same
+    definitions run as numpy statements and give the same bits.  Wrong dtypes (``TypeError``), factors, ``how`` and
+    shapes (``ValueError``) are refused by name before any device is touched."""
+    if how not in POOL_HOW:
+        raise ValueError(f"how = {how!r}, must be 'mode', 'mean' or 'max'")
+    f = pool_factors(factors)
+    if sparse and how != "mode":
+        raise ValueError(f"sparse leaves zeros out of the vote of how='mode' and has no meaning for how={how!r}")
+    check_pool_volume(volume, how)
+    v = pool_source(volume, how)
+    X, Y, Z = (int(n) for n in v.shape)
+    if max(X, Y, Z) > 2 ** 31 - 1 or -(-X // f[0]) * -(-Y // f[1]) > 2 ** 31 - 1:
+        raise ValueError(f"volume of shape {(X, Y, Z)} is too large to pool: every extent and ceil(X / fx) * ceil(Y / fy) "
+                         "must stay below 2^31")
+    if not v.is_cuda:
+        if v.dtype == getattr(torch, "uint16", None):
+            out = torch.from_numpy(_pool_host(v.view(torch.int16).numpy().view(np.uint16), f, how, bool(sparse))
+                                   .view(np.int16)).view(torch.uint16)
+        else:
+            out = torch.from_numpy(_pool_host(v.numpy(), f, how, bool(sparse)))
+    else:
+        out = torch.empty(tuple(-(-n // k) for n, k in zip((X, Y, Z), f)), dtype=v.dtype, device=v.device)
+        code = _SK_U16 if v.dtype == getattr(torch, "uint16", None) else _ffi.dtype_code(v)
+        _ffi.check(_ffi.lib.sk_pool_volume(_ffi.ptr(v), code, X, Y, Z, *f, POOL_HOW[how], int(bool(sparse)), _ffi.ptr(out),
+                                           _ffi.stream_ptr(v.device)))
+    return out.unsqueeze(0) if volume.ndim == 4 else out
