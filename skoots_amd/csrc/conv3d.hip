@@ -10,9 +10,9 @@
 //     activated by the fused GroupNorm+SiLU pass; weights are pre-packed on the host
 //     in MFMA A-fragment order (sk_conv3d_pack_weight_host);
 //   * D[cout][voxel] += W[cout][cin,tap] * act[cin,tap][voxel]: rows = 32 output
-//     channels, columns = 32 voxels of a (y,z) patch; conv3_kernel (COUT 64, 128) on
-//     v_mfma_f32_32x32x16_f16 (K = 16 input channels of one tap), conv3_m16_kernel (COUT 32) on
-//     v_mfma_f32_16x16x32_f16 (K = the tap's whole 32-channel chunk, 2 x 2 results per tile);
+//     channels, columns = 32 voxels of a (y,z) patch; conv3_m16_kernel (COUT 32, and since round 8 the plain 16-bit
+//     COUT 64 / 128 layers) on v_mfma_f32_16x16x32_f16 (K = the tap's whole 32-channel chunk, 2 x 2 results per tile),
+//     conv3_kernel (the split and mix8 forms of COUT 64, 128) on v_mfma_f32_32x32x16_f16 (K = 16 input channels of one tap);
 //   * a workgroup (4 waves, one 32-voxel column set each) owns a 128-voxel (y,z)
 //     patch and MARCHES along x, XS output planes per step.  The input planes of a
 //     step (XS+2, with y/z halo) sit in an LDS ring filled by LDS-DMA
@@ -624,9 +624,27 @@ __global__ void __launch_bounds__(256, 2) conv3_kernel(Conv3Args a) {
 // that shape against 1.65 with 32x32x16 on this part, and the COUT-32 variant has the registers for it (a 32 x 32
 // tile becomes 2 x 2 results of 16 x 16; K = 32 = the whole channel chunk per instruction; the 16-byte chunk
 // swizzle of the staged planes and the fragment packing differ, see below).  A/B on one device: -5 % time on each of
-// the three COUT-32 layers (55 % of the conv time).  With this shape the COUT 64 / 128 variants spill, or lose
-// reuse when XS is cut to fit (COUT 64: +22 % with a 76-byte spill at XS 4, +6 % at XS 3; COUT 128: +15 %): they stay
-// on conv3_kernel (32x32x16) above.
+// the three COUT-32 layers (55 % of the conv time).
+//
+// COUT 64 / 128 (kWide, round 8; plain 16-bit only -- the split and mix8 forms stay on conv3_kernel above, whose fp8 phase
+// shares its accumulators with v_mfma_scale_f32_32x32x64).  Rounds 1 and 2 tried these widths on `compute` below, which reads
+// every B fragment once per cout half -- twice conv3_kernel's LDS bytes per flop -- and spilled (+22 % / +13 % / +15 %).
+// The wide form is another schedule on the same tile (one cout tile x P column tiles x XS planes per wave, same ring, same
+// LDS-DMA, same x-chunks, same workgroups):
+//   * one tap row at a time with the A fragments of BOTH cout halves in registers: a B fragment is read once and feeds
+//     3 x taps x 2 halves = 6 MFMAs (XS 4), conv3_kernel's LDS bytes per flop; the next row's six A fragments are requested at
+//     the start of the row (two sets of 24 registers), the next body's B fragments behind the MFMAs that free their registers;
+//   * the A fragments come out of conv3_kernel's 32x32x16 weight image (one packing for all three precisions): see `wlane`;
+//   * what the MFMA loop does not need does not live in registers across it: the 36 tap addresses are formed per phase from
+//     an opaque copy of tile 0's position (hipcc hoisted them all out of the phase loop and spilled), the column tiles'
+//     positions and store voxels are tile 0's plus a wave-uniform step, the bias address and the store offsets are formed
+//     where they are used, and the eight LDS-DMA voxel indices wait in the 8 KiB of LDS that the plan reserves for
+//     conv3_kernel's transpose pads (this kernel transposes with v_permlane16_swap and never touched them).
+// Registers (hipcc -O3, gfx950): <64,4> 241, <64,3> 205, <128,2> 256; no scratch, no VGPR spill, two workgroups per CU.
+// Per launch of 64 production tiles on one device against conv3_kernel: 64 -> 64 2.52 -> 2.50 ms (-0.6 %, a few times the
+// parent's own repeat spread but no more), 128 -> 128 1.311 -> 1.213 ms (-7.5 %).  <64,3> (five-plane ring: z >= 24, the 4 x 32
+// rectangles of the 256^3 training crop) measured 421.5 -> 427.6 us there (+1.4 %): that slot keeps conv3_kernel<64, 3>, and
+// only the tuning builds instantiate the wide <64,3> (SK_CONV_WIDE16=1).  DESIGN.md section 8, round 8.
 //
 // RES: rows (dy,dz) of the 9 whose weight fragments stay in registers for the whole workgroup -- only for
 // single-chunk layers (the same 54 fragments every step) of COUT 32, where the kernel leaves ~80 of its 256
@@ -643,12 +661,24 @@ __global__ void __launch_bounds__(256, 2) conv3_kernel(Conv3Args a) {
 // that carries both cross terms -- K = [x8 | x_lo8] . [w_lo8 | w8] of TWO tap rows per v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3
 // operands at twice the fp16 rate, nine tap rows as five pairs) -- instead of split's three fp16 phases.  The source voxel line is
 // [hi fp16 (32) | x8 (32) | lo8 (32)], 128 bytes as a split line, so staging is unchanged; see sk_conv3d_mix8.
+// the wide form's issue order inside a body: for every staged plane I = 0 .. XS + 1 the MFMAs that read its fragment (two cout
+// halves x the x taps d with 0 <= I - d < XS), then ONE LDS read (the builtin wants literal counts: a recursion, not a loop)
+template <int XS, int I>
+__device__ __forceinline__ void wide_pin_planes() {
+    constexpr int kTaps = (I < 2 ? I : 2) - (I - XS + 1 > 0 ? I - XS + 1 : 0) + 1;
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * kTaps, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    if constexpr (I + 1 < XS + 2) wide_pin_planes<XS, I + 1>();
+}
+
 template <int COUT, int XS, int RES = 0, bool SPLIT = false, int WL = 0, bool MIX8 = false>
 __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
     constexpr int NT = COUT / 32;
     constexpr int P = NT;            // column tiles per wave
     constexpr int R = XS + 2;
     constexpr bool kLateWait = (NT != 2);  // wait for the next phase's DMA after the epilogue (see there)
+    constexpr bool kWide = NT >= 2;        // COUT 64 / 128: the one-row schedule on the 32x32x16 weight image (see above)
+    static_assert(!kWide || (RES == 0 && !SPLIT && WL == 0 && !MIX8), "the wide form is plain 16-bit only");
     extern __shared__ __attribute__((aligned(16))) char lds[];
 
     const int tid = threadIdx.x;
@@ -674,6 +704,7 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
     // per-lane flags of voxel (p, j), bit 2p + j: on the z = 0 face (linear mode) | << 8: on the z = Zt-1 face | << 16:
     // inside the tile.  One VGPR instead of 3 x 2P lane masks (the COUT 128 variant spilled on those).
     unsigned vflags = 0;
+    int sv0 = 0, qstep = 0, sstep = 0;
     auto zlo = [&](int p, int j) { return (vflags >> (2 * p + j)) & 1u; };
     auto zhi = [&](int p, int j) { return (vflags >> (8 + 2 * p + j)) & 1u; };
     auto vvalid = [&](int p, int j) { return (vflags >> (16 + 2 * p + j)) & 1u; };
@@ -701,7 +732,9 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
             }
             const int sv = v0 + 32 * (wm * P + p) + c16 + 16 * (g & 1);
             svox[p] = sv < a.Yt * a.Zt ? sv : -1;
+            if (p == 0) sv0 = sv;
         }
+        qstep = sstep = 32;
     } else {
         const int TY = kPatch / a.TZ;
         int yg = patch / a.nzc, zc = patch - yg * a.nzc;
@@ -723,13 +756,22 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
             const int svl = 32 * (wm * P + p) + c16 + 16 * (g & 1);
             const int syl = svl / a.TZ, sy = y0 + syl, sz = zc0 + svl - syl * a.TZ;
             svox[p] = (sy < a.Yt && sz < a.Zt) ? sy * a.Zt + sz : -1;
+            if (p == 0) sv0 = sy * a.Zt + sz;
         }
+        qstep = pitch;    // (kWide: TZ = 32, a column tile is one row of the rectangle)
+        sstep = a.Zt;
+    }
+    // kWide: the column tiles of a wave lie a wave-uniform step apart, in the region (qstep positions) and in the plane (sstep
+    // voxels), so tile 0's position, its store voxel and one validity bit per tile (vflags bit 24 + p) stand for the arrays
+    if constexpr (kWide) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) vflags |= (unsigned)(svox[p] >= 0) << (24 + p);
     }
 
     // Store box (Conv3Args.has_box, sk_conv3d_box / sk_conv3d_box_split): bit p = the voxel this lane STORES for column tile p
     // (column c16 + 16 (g & 1) after the permlane transpose) lies inside the box in (y, z); the x test is wave-uniform
     unsigned sboxm = ~0u;
-    if (a.has_box) {
+    if (!kWide && a.has_box) {   // (the host passes a box to the COUT-32 kernels only)
         sboxm = 0;
 #pragma unroll
         for (int p = 0; p < P; ++p) {
@@ -854,12 +896,19 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
     // (no 64-bit address arithmetic in the tap loop)
     auto wbase = [&](int ch) { return (unsigned)((ch * (9 * 2 * 3 * NT) + wn) * 1024); };
     const __amdgpu_buffer_rsrc_t wrsrc = sk::make_rsrc(a.wpk, MIX8 ? (unsigned)a.wpk_bytes : (unsigned)(a.nchunks * (9 * 2 * 3 * NT) * 1024));
-    const unsigned wlane = lane * 16;
+    // kWide: the image is conv3_kernel's ([chunk][dy*3+dz][ks(2)][dx][nt], 32x32x16 fragments: old lane 32 h + row holds K
+    // 16 ks + 8 h ..).  This lane's 16 bytes of fragment (nt, cout half i) = K 8 g .. of row 16 i + c16: old fragment ks = g >> 1,
+    // old lane 32 (g & 1) + 16 i + c16 -- one b128 load as before, four 256-byte runs per wave; i adds 256 bytes.
+    const unsigned wlane = kWide ? (unsigned)((g >> 1) * 3 * NT * 1024 + (32 * (g & 1) + c16) * 16) : lane * 16;
     auto wload = [&](unsigned off) {
         return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, __builtin_amdgcn_readfirstlane(off), 0));
     };
 
     half8 a0[3], a1[3];
+    // kWide: the fragments of both cout halves of a tap row, twice: row r multiplies with aw[r & 1] while aw[~r & 1] receives row
+    // r + 1's; every phase starts on set 0 (row 8 leaves it last, the hand-off refills it)
+    half8 aw[kWide ? 2 : 1][2][3];
+    auto wfrag = [&](unsigned rowbase, int i, int d) { return wload(rowbase + (unsigned)(d * NT) * 1024 + (unsigned)i * 256); };
     half8 wres[RES > 0 ? 2 * RES : 1][3];
     if constexpr (RES > 0) {
 #pragma unroll
@@ -874,13 +923,27 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
             *reinterpret_cast<uint4*>(lds + R * plane_bytes + i * 16) =
                 *reinterpret_cast<const uint4*>(a.wpk + RES * 6 * 1024 + i * 16);
     }
+    // kWide: the lane's eight DMA voxel indices wait in LDS between the phases -- in the 8 KiB the plan reserves behind the ring
+    // for conv3_kernel's transpose pads, 32 bytes per lane -- instead of in registers across the MFMAs
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    i32x4* const dma_stash = reinterpret_cast<i32x4*>(lds + R * plane_bytes + tid * 32);
+    static_assert(!kWide || (kMaxDma == 4 && 4 * kPadBytes == 256 * 32), "the stash is the pads' 8 KiB");
+    if constexpr (kWide) {
+        dma_stash[0] = i32x4{d_vox[0], d_vox[1], d_vox[2], d_vox[3]};
+        dma_stash[1] = i32x4{d_up[0], d_up[1], d_up[2], d_up[3]};
+    }
     issue_dma(0, ch0, false, 0);
-    if constexpr (RES == 0) {
+    if constexpr (kWide) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) aw[0][i][d] = wfrag(wbase(ch0), i, d);
+    } else if constexpr (RES == 0) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) a0[d] = wload(wbase(ch0) + (d * NT) * 1024);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!SPLIT) activate(0, ch0, false, 0);
+    if (!SPLIT && !kWide) activate(0, ch0, false, 0);   // (the wide layers take activated sources only: conv3d_route)
     __syncthreads();
 
     int step = 0, k = 0, ch = ch0, rot = 0;   // k: position of the phase in its step's chunk order
@@ -894,13 +957,19 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
         if (MIX8 && ph >= nphases) break;   // an odd number of steps: the last pair of the four does not exist
         const int x0 = xa + step * XS;
         if (k == 0) {
+            const float* bp = biasp;
+            if constexpr (kWide) {   // the lane's bias address is formed here, per step, not held in two registers across the MFMAs
+                int g4 = 4 * g;
+                asm volatile("" : "+v"(g4));
+                bp = a.bias + 32 * wn + g4;
+            }
 #pragma unroll
             for (int p = 0; p < P; ++p)
 #pragma unroll
                 for (int o = 0; o < XS; ++o)
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
-                        acc[p][o][i][0] = acc[p][o][i][1] = *reinterpret_cast<const f32x4*>(biasp + 16 * i);
+                        acc[p][o][i][0] = acc[p][o][i][1] = *reinterpret_cast<const f32x4*>(bp + 16 * i);
         }
         // ---------------- MFMA over the 27 taps of this chunk ---------------------------
         {
@@ -1008,6 +1077,69 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
                         mma8(rp, af);
                     }
                 }
+            } else if constexpr (kWide) {
+                // One tap row at a time, the A fragments of BOTH cout halves in registers: a B fragment (one staged plane of
+                // one 16-voxel half tile) is read once and feeds 3 x taps x 2 cout halves = 6 MFMAs, conv3_px_kernel's ratio
+                // and conv3_kernel's LDS bytes per flop (`compute` below reads every fragment once per cout half: twice those).
+                // (the 36 tap addresses are the same in every phase: formed per row from an opaque copy, or hipcc hoists them all
+                // out of the phase loop and spills)
+                int qr0 = q_row[0];
+                asm volatile("" : "+v"(qr0));
+                // B fragments one body ahead, in the registers the running body frees: a body = (row, column tile p, voxel half
+                // j) = R fragments, one per staged plane, consumed in plane order; the next body's fragment of plane i is requested
+                // right behind the MFMAs that read this body's (the scheduler left to itself asks for a fragment one MFMA
+                // before its use: `ds_read ; s_waitcnt lgkmcnt(1) ; v_mfma` all along the row)
+                half8 bq[2][R];
+                auto bload = [&](int dydz, int p, int j, half8 (&dst)[R]) {
+                    const int dz = dydz % 3 - 1;
+                    const int qj = qr0 + (p * qstep + (dydz / 3 - 1) * pitch + dz + j * a.jstep);
+                    int addr = (qj * 4 + (g ^ (((qj >> 2) & 1) << 1))) * 16;
+                    if (dz < 0) addr = zlo(p, j) ? sk::zero_of(zero_addr, addr) : addr;
+                    if (dz > 0) addr = zhi(p, j) ? sk::zero_of(zero_addr, addr) : addr;
+#pragma unroll
+                    for (int i = 0; i < R; ++i) dst[i] = *reinterpret_cast<const half8*>(lds + pslot[i] + addr);
+                };
+                bload(0, 0, 0, bq[0]);
+#pragma unroll
+                for (int dydz = 0; dydz < 9; ++dydz) {
+                    const int cur = dydz & 1, nxt = cur ^ 1;
+                    if (dydz < 8) {   // the next row's six A fragments: a whole row (12 XS P MFMAs) to land in
+                        const unsigned wnext = wch + (unsigned)((dydz + 1) * 2) * (3 * NT) * 1024;
+#pragma unroll
+                        for (int ih = 0; ih < 2; ++ih)
+#pragma unroll
+                            for (int d = 0; d < 3; ++d) aw[nxt][ih][d] = wfrag(wnext, ih, d);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);   // (see conv3_kernel's kTapUnroll)
+#pragma unroll
+                    for (int p = 0; p < P; ++p)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const int nb = (dydz * P + p) * 2 + j;   // bodies alternate between the two fragment sets
+                            int nd = dydz, np = p, nj = j + 1;
+                            if (nj == 2) {
+                                nj = 0;
+                                ++np;
+                            }
+                            if (np == P) {
+                                np = 0;
+                                ++nd;
+                            }
+                            if (nd < 9) bload(nd, np, nj, bq[(nb + 1) & 1]);
+                            wide_pin_planes<XS, 0>();   // plane i's MFMAs, then the next body's read of plane i
+#pragma unroll
+                            for (int i = 0; i < R; ++i)
+#pragma unroll
+                                for (int d = 0; d < 3; ++d) {
+                                    const int o = i - d;  // x_in = x_out + (d - 1)
+                                    if (o >= 0 && o < XS) {
+                                        acc[p][o][0][j] = SK_MFMA_16x16x32_T16(aw[cur][0][d], bq[nb & 1][i], acc[p][o][0][j], 0, 0, 0);
+                                        acc[p][o][1][j] = SK_MFMA_16x16x32_T16(aw[cur][1][d], bq[nb & 1][i], acc[p][o][1][j], 0, 0, 0);
+                                    }
+                                }
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                }
             } else if constexpr (RES == 0 && NT == 1) {
                 half8 bb[2][2][R];
                 auto load_row = [&](int dydz, half8 (&dst)[2][R]) {
@@ -1114,8 +1246,21 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
         __syncthreads();  // every wave is done reading the planes about to be overwritten
         SK_T(1)           // barrier: waiting for the slowest wave of the workgroup
         if (have_next) {
+            if constexpr (kWide) {   // (the barrier's memory clobber stands between this and the stores: a real read)
+                const i32x4 dv = dma_stash[0], du = dma_stash[1];
+#pragma unroll
+                for (int t = 0; t < kMaxDma; ++t) {
+                    d_vox[t] = dv[t];
+                    d_up[t] = du[t];
+                }
+            }
             if (!(a.chinfo[nch] & 2)) issue_dma(nstep, nch, reuse_n, rot_n);   // bit 1: the next chunk multiplies the SAME staged planes
-            if constexpr (RES == 0) {
+            if constexpr (kWide) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) aw[0][i][d] = wfrag(wbase(nch), i, d);
+            } else if constexpr (RES == 0) {
 #pragma unroll
                 for (int d = 0; d < 3; ++d) a0[d] = wload(wbase(nch) + (d * NT) * 1024);
             }
@@ -1187,10 +1332,16 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
                             // this lane now owns channels 16 i + 8 (g >> 1) .. +7 of voxel c16 + 16 (g & 1)
                             const uint4 line = make_uint4(s0[0], s1[0], s0[1], s1[1]);
                             if (!SK_ABL(a, 4)) {
-                                const bool xbox = !a.has_box || (x >= a.box_lo[0] && x < a.box_hi[0]);   // wave-uniform
-                                const bool sok = x < xb && xbox && ((sboxm >> p) & 1u) && svox[p] >= 0;
+                                const bool xbox = kWide || !a.has_box || (x >= a.box_lo[0] && x < a.box_hi[0]);   // wave-uniform
+                                bool sok = x < xb && xbox && ((sboxm >> p) & 1u) && svox[p] >= 0;
                                 char* dst = outb + (long long)x * out_plane + (long long)svox[p] * kOvs + wn * 64 + part * (COUT * 2) +
                                             32 * i + 16 * (g >> 1);
+                                if constexpr (kWide) {   // the store offset is formed here, from tile 0's voxel (hoisted, the offsets of a step cost registers)
+                                    int svp = sv0;
+                                    asm volatile("" : "+v"(svp));
+                                    sok = x < xb && ((vflags >> (24 + p)) & 1u);
+                                    dst = outb + (long long)x * out_plane + (long long)(svp + p * sstep) * kOvs + wn * 64 + 32 * i + 16 * (g >> 1);
+                                }
                                 // always issued (the counted wait relies on it); a masked lane's offset is out of range: dropped
                                 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                                 const u32x4 lv = {line.x, line.y, line.z, line.w};
@@ -1208,7 +1359,7 @@ __global__ void __launch_bounds__(256, 2) conv3_m16_kernel(Conv3Args a) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kStores) : "memory");
             }
             SK_T(4)       // deferred landing wait
-            if (!SPLIT && !(a.chinfo[nch] & 2)) activate(nstep, nch, reuse_n, rot_n);   // own DMA has landed (waits above)
+            if (!SPLIT && !kWide && !(a.chinfo[nch] & 2)) activate(nstep, nch, reuse_n, rot_n);   // own DMA has landed (waits above)
             SK_T(5)       // in-LDS activation
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             SK_T(6)       // closing barrier
@@ -2779,6 +2930,18 @@ const KernelRow<DownArgs> kDown[2 * 2] = {
 };
 
 // 3x3x3: [precision][slot]; conv3_m16_kernel<32, XS, RES, SPLIT, WL, MIX8>, conv3_kernel<COUT, XS, RES, SPLIT, MIX8>
+// A row's name is the SLOT's (what sk_conv3d_route_name reports and tests/conv16_cases.py spells), not the template's: the plain
+// 16-bit slots conv3<64,4>, conv3<64,3>, conv3<128,2> hold whichever of conv3_kernel<COUT, XS> (32x32x16) and
+// conv3_m16_kernel<COUT, XS> (16x16x32, the wide form) measured faster per launch (a release build
+// instantiates only the form its table holds).
+#ifdef SK_TUNING
+// SK_CONV_WIDE16=0 | 1: all three slots on conv3_kernel | conv3_m16_kernel, so that tools/layer_ab.py and tools/kernel_ab.sh
+// can A/B the two MFMA shapes from one tuning library
+void (*const kWide16AB[2][3])(Conv3Args) = {
+    {conv3_kernel<64, 4>, conv3_kernel<64, 3>, conv3_kernel<128, 2>},
+    {conv3_m16_kernel<64, 4>, conv3_m16_kernel<64, 3>, conv3_m16_kernel<128, 2>},
+};
+#endif
 enum { kSlotPx, kSlotM16W2, kSlotM16W1, kSlotM16W0, kSlotM16x4, kSlotM16x3, kSlotC64x4, kSlotC64x3, kSlotC128, kConv3Slots };
 const KernelRow<Conv3Args> kConv3[kPrecisions * kConv3Slots] = {
     {"px", conv3_px_kernel<kPxResidentHalfRows, kPxPositions>, kPxLds, false},
@@ -2787,9 +2950,9 @@ const KernelRow<Conv3Args> kConv3[kPrecisions * kConv3Slots] = {
     {"m16<4,3,0>", conv3_m16_kernel<32, 4, 3>, 0, true},
     {"m16<4>", conv3_m16_kernel<32, 4>, 0, true},
     {"m16<3>", conv3_m16_kernel<32, 3>, 0, true},
-    {"conv3<64,4>", conv3_kernel<64, 4>, 0, true},
-    {"conv3<64,3>", conv3_kernel<64, 3>, 0, true},
-    {"conv3<128,2>", conv3_kernel<128, 2>, 0, true},
+    {"conv3<64,4>", conv3_m16_kernel<64, 4>, 0, true},     // the wide form since round 8: -0.6 % per launch
+    {"conv3<64,3>", conv3_kernel<64, 3>, 0, true},         // stays: conv3_m16_kernel<64, 3> measured +1.4 % on the 256^3 crop's rectangles
+    {"conv3<128,2>", conv3_m16_kernel<128, 2>, 0, true},   // the wide form since round 8: -7.5 % (production tile), -2.8 % (256^3 crop)
     {}, {}, {}, {},
     {"m16<4,split>", conv3_m16_kernel<32, 4, 0, true>, 0, true},
     {"m16<3,split>", conv3_m16_kernel<32, 3, 0, true>, 0, true},
@@ -3179,7 +3342,14 @@ static int conv3d_impl(const sk_conv_src* srcs, int n_src, const void* weight, c
         a.wpk_bytes = a.w8_off + mix8_fp8_bytes(cout, cin);
         a.w8_scale = 0x01010101 * (127 - w8_scale_exp);
     }
-    return launch(kConv3[r.row].kern, r.grid, r.lds, a, stream);
+    auto kern = kConv3[r.row].kern;
+#ifdef SK_TUNING
+    if (const char* e = getenv("SK_CONV_WIDE16")) {
+        const int slot = r.row - kFp16 * kConv3Slots;   // the plain 16-bit rows only
+        if (slot >= kSlotC64x4 && slot <= kSlotC128) kern = kWide16AB[atoi(e) != 0][slot - kSlotC64x4];
+    }
+#endif
+    return launch(kern, r.grid, r.lds, a, stream);
 }
 
 int sk_conv3d(const sk_conv_src* srcs, int n_src, const void* weight, const float* bias, void* out,
