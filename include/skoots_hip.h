@@ -35,7 +35,7 @@ extern "C" {
 #define SK_I16 2
 #define SK_I32 3
 #define SK_U8 4
-#define SK_U16 5 /* sk_pool_volume only */
+#define SK_U16 5 /* sk_pool_volume and sk_resample_volume */
 
 const char* sk_last_error(void);
 int sk_abi_version(void);
@@ -1020,6 +1020,44 @@ int sk_convert_pages_u8(const void* src, int src_dtype, int mode, int C, int X, 
  * ceil(X / fx) ceil(Y / fy) < 2^31. */
 int sk_pool_volume(const void* src, int dtype, int X, int Y, int Z, int fx, int fy, int fz, int how, int sparse,
                    void* dst, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Exact change of grid by any ratio per axis (ABI 32; no reference counterpart)
+ * ------------------------------------------------------------------------ */
+
+#define SK_RESAMPLE_NEAREST 0
+#define SK_RESAMPLE_LINEAR 1
+#define SK_RESAMPLE_AREA 2
+
+#define SK_RESAMPLE_PATH_GATHER 0 /* nearest on every axis: no arithmetic */
+#define SK_RESAMPLE_PATH_ACC32 1  /* weighted sums in 32 bits: W vmax < 2^32 after the reduction */
+#define SK_RESAMPLE_PATH_ACC64 2  /* weighted sums in 64 bits */
+
+/* src: contiguous (X, Y, Z) of dtype, Z innermost; dst: contiguous (Xo, Yo, Zo) of the same dtype.  Both cover the same
+ * physical extent (pixel-centre convention, no align_corners).  An axis of n source voxels and m output voxels has one
+ * operator: per output index i a list of integer taps (k, w) and a total W.
+ *   SK_RESAMPLE_NEAREST  one tap, k = ((2 i + 1) n) div (2 m), w = 1, W = 1: the source voxel that holds the output
+ *                        voxel's centre; a centre on a boundary takes the upper voxel.
+ *   SK_RESAMPLE_LINEAR   num = (2 i + 1) n - m, den = 2 m, k0 = floor(num / den), r = num - k0 den; taps
+ *                        (clamp(k0), den - r) and (clamp(k0 + 1), r), clamped to 0 .. n - 1; W = den.
+ *   SK_RESAMPLE_AREA     output cell i covers [i n, (i + 1) n) in units of 1 / m of a source voxel; for k from (i n) div m
+ *                        to ceil((i + 1) n / m) - 1 the weight is min((k + 1) m, (i + 1) n) - max(k m, i n); W = n.
+ * The output voxel is floor((2 S + W) / (2 W)), S the sum of wx wy wz v over the product of the three tap lists and
+ * W = Wx Wy Wz: the exact quotient rounded to nearest, halves up.  The weights of an axis are divided by a common factor
+ * first (linear: gcd(2 m, 2 n, |n - m|), area: gcd(n, m)), which changes no result.  Integers only: the same bits on
+ * every run.  dtype: SK_U8 / SK_U16 for every operator; SK_I32 / SK_I16 with SK_RESAMPLE_NEAREST on all three axes.
+ *
+ * workspace: sk_resample_workspace_bytes(...) bytes of device memory, 4-byte aligned, for the three tap tables, which a
+ * prologue launch per axis fills on the same stream; nothing is allocated, nothing comes back to the host.  Limits,
+ * checked before any launch (SK_ERR_ARG; the workspace query then returns 0): null pointers, extents < 1 or > 2^30, a ratio
+ * outside n / 8 <= m <= 8 n (halve with sk_pool_volume first), operator codes, the dtype of the operators, the unreduced
+ * Wx Wy Wz (linear 2 m, area n, nearest 1) times the dtype's largest value >= 2^63, Xo Yo >= 2^31, more than 65535 z chunks
+ * (a chunk is at least 64 output voxels for Zo >= 64), element alignment, a workspace that is too small.
+ * sk_resample_path: HOST, no GPU needed: which kernel the launch runs, SK_RESAMPLE_PATH_*, or SK_ERR_ARG. */
+size_t sk_resample_workspace_bytes(int dtype, int X, int Y, int Z, int Xo, int Yo, int Zo, int op_x, int op_y, int op_z);
+int sk_resample_path(int dtype, int X, int Y, int Z, int Xo, int Yo, int Zo, int op_x, int op_y, int op_z);
+int sk_resample_volume(const void* src, void* dst, int dtype, int X, int Y, int Z, int Xo, int Yo, int Zo, int op_x, int op_y,
+                       int op_z, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Instance measurements: volume, box, moments and face area of every instance

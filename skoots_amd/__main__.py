@@ -3,7 +3,8 @@ the reference CLI (skoots/__main__.py:19-46, 78-98), and ``--skeletonize-train-d
 [--anisotropyXY a] [--anisotropyZ b]`` (skoots/__main__.py:49-68, 101-106), and ``--convert PATH``: eval's zarr stores
 and ``.trch`` tensors under PATH -> TIFF stacks, no eval (skoots/__main__.py:70-74, 84, 108-109).  With it every switch of
 the reference's main command exists here.  ``--pyramid`` (not in the reference) makes eval also write
-``<base>_skoots.ome.zarr``, the multiscale OME-Zarr group of image, instance mask and skeleton."""
+``<base>_skoots.ome.zarr``, the multiscale OME-Zarr group of image, instance mask and skeleton.  ``--rescale FX FY FZ``
+(not in the reference) resamples the image by those factors before the network and writes the mask on the input's grid."""
 import argparse
 import glob
 import logging
@@ -27,6 +28,10 @@ def build_parser() -> argparse.ArgumentParser:
     eval_args.add_argument("--pyramid", action="store_true",
                            help="also writes <base>_skoots.ome.zarr: multiscale pyramids of the image, the instance mask "
                                 "and the skeleton as one OME-Zarr group (skoots_amd.utils.pyramid)")
+    eval_args.add_argument("--rescale", type=float, nargs=3, default=None, metavar=("FX", "FY", "FZ"),
+                           help="output voxels per input voxel along x, y and z: the image is resampled on the device to the "
+                                "voxel size the model was trained at, the instance mask is written on the input's own grid "
+                                "(skoots_amd.lib.morphology.resample)")
     accessory_args = parser.add_argument_group("scripting arguments")
     accessory_args.add_argument("--skeletonize-train-data",
                                 help="calculate skeletons of training data (a label TIFF or a directory of them)")
@@ -43,6 +48,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = parser.parse_args(argv)
     if args.skeletonize_train_data is None and args.convert is None and args.image is None:
         parser.error("the following arguments are required: --image")
+    if args.rescale is not None and not all(0 < v < float("inf") for v in args.rescale):
+        parser.error("--rescale must be three positive finite numbers")
+    if args.rescale is not None and args.pyramid:
+        parser.error("--pyramid together with --rescale is not built: run python -m skoots_amd.utils.pyramid on the outputs")
     return args
 
 
@@ -65,7 +74,9 @@ def main(argv=None):
     from skoots_amd.lib.eval import eval as sk_eval
     files = sorted(glob.glob(args.image + "/*.tif")) if os.path.isdir(args.image) else [args.image]
     for f in files:
-        extra = {"pyramid": True} if args.pyramid else {}   # the keyword goes down only when it is set
+        extra = {"pyramid": True} if args.pyramid else {}   # the keywords go down only when they are set
+        if args.rescale is not None:
+            extra["rescale"] = tuple(args.rescale)
         sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached, output_huffman=args.output_huffman,
                 **extra)
 

@@ -212,6 +212,9 @@ _SIGS = {
     "sk_blosc_decode_host": (i32, [vp, i64, vp, i64, vp]),
     "sk_convert_pages_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "sk_pool_volume": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "sk_resample_workspace_bytes": (sz, [i32] * 10),
+    "sk_resample_path": (i32, [i32] * 10),
+    "sk_resample_volume": (i32, [vp, vp] + [i32] * 10 + [vp, sz, vp]),
     "sk_instance_stats_row_values": (i32, [i32]),
     "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "sk_instance_mesh_cells": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp]),

@@ -267,7 +267,8 @@ def _cfg_get(cfg, section: str, key: str, default=None):
 
 @torch.inference_mode()
 def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16",
-         read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None, pyramid: bool = False) -> None:
+         read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None, pyramid: bool = False,
+         rescale=None) -> None:
     """Evaluates SKOOTS on an arbitrary image (drop-in for ``skoots.lib.eval.eval``).
 
     ``precision`` (not in the reference's signature; keyword with the reference's behaviour as default): "fp16" = what the
@@ -298,6 +299,18 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     ``SKOOTS.ANISOTROPY``, (1, 1, 3) without one; ``output_huffman`` applies.  An image that is not uint8 / uint16 (or
     signed with values in 0 .. 65535) is refused before the model runs.
 
+    ``rescale`` (keyword, not in the reference's signature; ``None`` by default, and without it every output is byte
+    for byte what it was): ``(fx, fy, fz)``, output voxels per input voxel in this function's (X, Y, Z) order, for an
+    image whose voxel size is not the one the model was trained at.  The integer samples as read (uint8 or uint16, or
+    signed with values in 0 .. 65535; anything else is refused by name before the model is built) are resampled on the
+    device to ``resample_shape((X, Y, Z), rescale)`` with ``lib.morphology.resample(how="auto")`` before the fp16
+    conversion, and the statistics fallback is taken from that fp16 image.  The network, labelling, following, the two
+    zarr stores (their ``.zarray`` shapes say so: they are intermediates), ``used_cached_data`` and the benchmark file
+    all live on the resampled grid.  The instance mask is mapped back with ``how="nearest"`` to exactly the input's
+    (X, Y, Z) before it is written.  Its ids are those of the network's grid and are not renumbered, so an instance
+    smaller than an input voxel can be missing from the file.  ``rescale=(1, 1, 1)`` takes this path and gives the same
+    files.  Together with ``pyramid`` it is refused by name: run ``utils.pyramid`` on the outputs.
+
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
     ``SKOOTS.VECTOR_SCALING`` and ``MODEL.*``), ``model_state_dict`` and optionally
     ``dataset_mean`` / ``dataset_std`` (eval.py:51-55, 87-88, 99, 117-118).
@@ -307,6 +320,11 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     if output_huffman is None:
         output_huffman = OUTPUT_HUFFMAN   # looked up now, so that setting the module's switch takes effect
     deflate.huffman_mode(output_huffman)
+    if rescale is not None:
+        if pyramid:
+            raise ValueError("pyramid=True together with rescale is not built: run skoots_amd.utils.pyramid on the outputs")
+        from .morphology import resample_shape
+        resample_shape((1, 1, 1), rescale)   # three positive finite numbers, or a ValueError that says so
     start = time.time()
     logging.info(f"Loading model file: {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -329,10 +347,11 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         stack = stack[[2], ...] if stack.shape[0] > 3 else stack  # eval.py:64 -> [C=1, X, Y, Z]
         c, x, y, z = stack.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {stack.dtype}")
-        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous()  # eval.py:80
-        raw_img = stack[0] if pyramid else None
+        raw_img = stack[0] if pyramid or rescale is not None else None
+        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous() if rescale is None else None  # eval.py:80
         # the statistics fallback stays the CPU reduction over the same fp16 values: the image comes back for it only
-        img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None
+        img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) and \
+            rescale is None else None
     else:
         image = _read_image(image_path)  # [Z, X, Y(, C)]
         image = image[..., np.newaxis] if image.ndim == 3 else image
@@ -340,10 +359,11 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         image = image[[2], ...] if image.shape[0] > 3 else image  # eval.py:64 -> [C=1, X, Y, Z]
         c, x, y, z = image.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {image.dtype}")
-        img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16)  # eval.py:80
+        img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16) \
+            if rescale is None else None  # eval.py:80
         dev_img = None
         raw_img = None
-        if pyramid:     # the samples as read: uint16 through its bit pattern
+        if pyramid or rescale is not None:     # the samples as read: uint16 through its bit pattern
             raw = np.ascontiguousarray(image[0])
             raw_img = (torch.from_numpy(raw.view(np.int16)).view(torch.uint16) if raw.dtype == np.uint16
                        else torch.from_numpy(raw))
@@ -356,6 +376,18 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         except (KeyError, AttributeError):
             aniso = None
         spacing = check_spacing(aniso if aniso is not None else (1.0, 1.0, 3.0))
+    input_shape = (x, y, z)
+    if rescale is not None:
+        # the raw samples go up and are resampled there; everything below lives on the resampled grid
+        from .morphology import check_pool_volume, check_resample, pool_source, resample
+        x, y, z = resample_shape(input_shape, rescale)
+        check_pool_volume(raw_img, "mean", "image")                  # float images are refused by name, as pool refuses them
+        raw_dev = pool_source(raw_img.to(device), "mean", "image")   # signed samples: 0 .. 65535 or a ValueError
+        check_resample(raw_dev, (x, y, z), "auto", "image")
+        logging.info(f"Rescaling the image from {input_shape} to {(x, y, z)}")
+        dev_img = _to_f32(resample(raw_dev, shape=(x, y, z), how="auto")).to(torch.float16).contiguous()
+        del raw_dev
+        img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None
     mean = checkpoint["dataset_mean"] if "dataset_mean" in checkpoint else img16.mean()  # eval.py:87
     std = checkpoint["dataset_std"] if "dataset_std" in checkpoint else img16.std()  # eval.py:88
     scale = [int(v) for v in _cfg_get(cfg, "SKOOTS", "VECTOR_SCALING")]  # eval.py:99
@@ -401,6 +433,8 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
                 f"{torch.cuda.max_memory_allocated(device)})\n\n")
     print("DONE")
     logging.info(f"saving to tif file at {base}_instance_mask.tif")
+    if rescale is not None:   # back onto the input's grid: the ids of the network's grid, not renumbered
+        inst = resample(inst, shape=input_shape, how="nearest")
     tiff.write_label_stack(base + "_instance_mask.tif", inst.permute(2, 0, 1), huffman=output_huffman)
     if pyramid:
         from ..utils.pyramid import write_ome_zarr

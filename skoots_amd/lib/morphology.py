@@ -599,7 +599,7 @@ def skeletonize(image: Tensor) -> Tensor:
 # ---- one level of a multiscale pyramid ----
 
 POOL_HOW = {"mode": 0, "mean": 1, "max": 2}     # SK_POOL_MODE / _MEAN / _MAX of include/skoots_hip.h
-_SK_U16 = 5                                     # SK_U16: the dtype code only sk_pool_volume takes
+_SK_U16 = 5                                     # SK_U16: the dtype code sk_pool_volume and sk_resample_volume take
 _POOL_SIGNED = (torch.int8, torch.int16, torch.int32, torch.int64)
 
 
@@ -731,3 +731,185 @@ def pool(volume: Tensor, factors, how: str = "mode", sparse: bool = False) -> Te
         _ffi.check(_ffi.lib.sk_pool_volume(_ffi.ptr(v), code, X, Y, Z, *f, POOL_HOW[how], int(bool(sparse)), _ffi.ptr(out),
                                            _ffi.stream_ptr(v.device)))
     return out.unsqueeze(0) if volume.ndim == 4 else out
+
+
+# ---- exact change of grid by any ratio per axis ----
+
+RESAMPLE_OP = {"nearest": 0, "linear": 1, "area": 2}    # SK_RESAMPLE_NEAREST / _LINEAR / _AREA of include/skoots_hip.h
+RESAMPLE_HOW = ("auto", "nearest", "linear", "area")
+RESAMPLE_PATHS = ("gather", "acc32", "acc64")           # SK_RESAMPLE_PATH_*: what sk_resample_path answers
+_RESAMPLE_MAX_EXTENT = 2 ** 30
+
+
+def resample_shape(shape, factors) -> Tuple[int, int, int]:
+    """The extents ``resample`` gives an (X, Y, Z) ``shape`` at ``factors`` (fx, fy, fz), output voxels per input voxel:
+    ``max(1, floor(n * f + 0.5))`` per axis."""
+    try:
+        s, f = tuple(int(n) for n in shape), tuple(float(v) for v in factors)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape and factors must be three numbers each, got {shape!r} and {factors!r}") from None
+    if len(s) != 3 or len(f) != 3 or min(s) < 1:
+        raise ValueError(f"shape and factors must be three numbers each, every extent at least 1, got {shape!r} and "
+                         f"{factors!r}")
+    if not all(np.isfinite(v) and v > 0 for v in f):
+        raise ValueError(f"factors must be positive and finite, got {factors!r}")
+    return tuple(max(1, int(np.floor(n * v + 0.5))) for n, v in zip(s, f))
+
+
+def resample_operators(src_shape, dst_shape, how: str) -> Tuple[str, str, str]:
+    """The operator of every axis: ``how`` itself, or under ``"auto"`` linear where ``m >= n`` and area where ``m < n``."""
+    if how not in RESAMPLE_HOW:
+        raise ValueError(f"how = {how!r}, must be 'auto', 'nearest', 'linear' or 'area'")
+    if how != "auto":
+        return (how,) * 3
+    return tuple("linear" if m >= n else "area" for n, m in zip(src_shape, dst_shape))
+
+
+def check_resample(volume, shape, how: str = "auto", name: str = "volume") -> Tuple[Tuple[int, int, int], Tuple[str, str, str]]:
+    """What ``resample`` takes, checked on the tensor's description alone, before any device is touched: the source
+    (X, Y, Z) and the operator of every axis.  ``how="nearest"``: int32, int16, uint8 or uint16.  ``"linear"``,
+    ``"area"`` and ``"auto"``: uint8 or uint16.  Float volumes are refused by name.  Also refused: an axis ratio outside
+    ``n / 8 <= m <= 8 n``, an unreduced weight total ``Wx Wy Wz`` (linear ``2 m``, area ``n``, nearest 1) that reaches
+    2^63 when multiplied by the dtype's largest value, extents beyond 2^30 and more than 2^31 - 1 output rows."""
+    if how not in RESAMPLE_HOW:
+        raise ValueError(f"how = {how!r}, must be 'auto', 'nearest', 'linear' or 'area'")
+    if not isinstance(volume, Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(volume).__name__}")
+    dt = volume.dtype
+    if dt.is_floating_point or dt.is_complex or dt == torch.bool:
+        raise TypeError(f"{name} is {dt}: float, complex and bool volumes are not resampled, the operators are exact "
+                        "integer work (labels int32 / int16 / uint8, images uint8 / uint16)")
+    images = (torch.uint8, torch.uint16)
+    allowed = images + (torch.int32, torch.int16) if how == "nearest" else images
+    if dt not in allowed:
+        raise TypeError(f"{name} is {dt}: how={how!r} takes " +
+                        ("int32, int16, uint8 or uint16" if how == "nearest" else "uint8 or uint16 (labels take 'nearest')"))
+    s = tuple(int(v) for v in volume.shape)
+    s = s[1:] if len(s) == 4 and s[0] == 1 else s
+    if len(s) != 3 or min(s) < 1:
+        raise ValueError(f"{name} has the shape {tuple(volume.shape)}: it must be (X, Y, Z) or (1, X, Y, Z) with every "
+                         "extent at least 1")
+    try:
+        m = tuple(int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape must be three integers (X, Y, Z), got {shape!r}") from None
+    if len(m) != 3 or min(m) < 1 or any(float(a) != float(b) for a, b in zip(m, shape)):
+        raise ValueError(f"shape must be three integers (X, Y, Z), each at least 1, got {shape!r}")
+    if max(s + m) > _RESAMPLE_MAX_EXTENT or m[0] * m[1] > 2 ** 31 - 1:
+        raise ValueError(f"{s} -> {m} is too large to resample: every extent must stay within 2^30 and the output rows "
+                         "X * Y below 2^31")
+    for axis, n, k in zip("XYZ", s, m):
+        if 8 * k < n or k > 8 * n:
+            raise ValueError(f"the ratio of {axis}, {n} -> {k}, is outside n / 8 <= m <= 8 n: halve with pool() first, or "
+                             "resample in two steps")
+    ops = resample_operators(s, m, how)
+    total = 1
+    for n, k, op in zip(s, m, ops):
+        total *= {"nearest": 1, "linear": 2 * k, "area": n}[op]
+    vmax = {torch.uint8: 255, torch.uint16: 65535, torch.int16: 32767, torch.int32: 2 ** 31 - 1}[dt]
+    if total * vmax >= 2 ** 63:
+        raise ValueError(f"{s} -> {m} with {ops}: the weight total {total} times the largest {dt} value reaches 2^63 and "
+                         "cannot be summed exactly; resample in two steps")
+    return s, ops
+
+
+def resample_taps(n: int, m: int, op: str):
+    """The tap table of one axis as numpy arrays: ``start`` (m,), ``count`` (m,), ``weights`` (m, T) int64 with zeros
+    behind ``count``, and the total ``W`` -- weights divided by their common factor, as the kernel's prologue does."""
+    i = np.arange(m, dtype=np.int64)
+    if op == "nearest":
+        return ((2 * i + 1) * n) // (2 * m), np.ones(m, np.int64), np.ones((m, 1), np.int64), 1
+    if op == "linear":
+        den, num = 2 * m, (2 * i + 1) * n - m
+        k0 = num // den                                      # floor: num is negative at i = 0 when m > n
+        r = num - k0 * den
+        one = (k0 < 0) | (k0 + 1 > n - 1) | (r == 0)
+        g = int(np.gcd(np.gcd(2 * m, 2 * n), abs(n - m)))
+        w = np.stack([np.where(one, den, den - r), np.where(one, 0, r)], axis=1) // g
+        return np.clip(k0, 0, n - 1), np.where(one, 1, 2), w, den // g
+    lo, hi = i * n, (i + 1) * n
+    kb, ke = lo // m, -(-hi // m) - 1
+    T = -(-n // m) + 1
+    k = kb[:, None] + np.arange(T, dtype=np.int64)[None, :]
+    w = np.minimum((k + 1) * m, hi[:, None]) - np.maximum(k * m, lo[:, None])
+    g = int(np.gcd(n, m))
+    return kb, ke - kb + 1, np.where(k <= ke[:, None], w, 0) // g, n // g
+
+
+def _resample_host(a: np.ndarray, shape, ops) -> np.ndarray:
+    """The definition of ``resample`` as numpy statements: one axis after the other in exact int64 sums (the product of
+    the three tap lists factorises), then the one rounded division."""
+    if all(op == "nearest" for op in ops):
+        for axis, (n, m) in enumerate(zip(a.shape, shape)):
+            a = np.take(a, resample_taps(n, m, "nearest")[0], axis=axis)
+        return np.ascontiguousarray(a)
+    s, W = a.astype(np.int64), 1
+    for axis, (n, m, op) in enumerate(zip(a.shape, shape, ops)):
+        start, count, w, total = resample_taps(n, m, op)
+        acc = 0
+        for t in range(w.shape[1]):
+            wt = w[:, t].reshape([-1 if d == axis else 1 for d in range(3)])
+            acc = acc + wt * np.take(s, np.minimum(start + t, n - 1), axis=axis)     # weight 0 behind count
+        s, W = acc, W * total
+    q = s // W
+    return (q + (2 * (s - q * W) >= W)).astype(a.dtype)
+
+
+def resample(volume: Tensor, shape=None, factors=None, how: str = "auto") -> Tensor:
+    """An exactly defined change of grid by any ratio per axis: an (X, Y, Z) or (1, X, Y, Z) integer tensor brought to
+    ``shape`` (three extents) or to ``resample_shape(its shape, factors)`` -- exactly one of the two is given -- on the
+    device it lives on (the reference has no counterpart).  Source and result cover the same
+    physical extent (pixel centres, no ``align_corners``).  The result has the input's rank, dtype and device.
+
+    Per axis of ``n`` source and ``m`` output voxels one operator, a list of integer taps ``(k, w)`` per output index
+    ``i`` with the total ``W``: ``"nearest"`` the voxel ``((2i+1) n) // (2m)`` that holds the output voxel's centre (the
+    upper one for a centre on a boundary); ``"linear"`` the two voxels around the centre, ``num = (2i+1) n - m``,
+    ``k0 = num // (2m)``, ``r = num - 2m k0``, taps ``(clamp(k0), 2m - r)`` and ``(clamp(k0 + 1), r)``, ``W = 2m``;
+    ``"area"`` every voxel the output cell covers, weighted by the covered length in units of ``1 / m``, ``W = n``.
+    ``"auto"`` (the default) is linear where ``m >= n`` and area where ``m < n``.  The output voxel is the exact quotient
+    ``S / W`` of the weighted sum over the product of the three tap lists and ``W = Wx Wy Wz``, rounded to nearest,
+    halves up -- ``pool(..., "mean")``'s rule, which area at even extents and factors of two reproduces.
+
+    ``"nearest"`` takes int32, int16, uint8 and uint16 (labels keep their ids; an instance smaller than an output voxel
+    can vanish), the others uint8 and uint16.  On a device tensor this is ``sk_resample_volume`` on the current stream;
+    on a CPU tensor the same definition runs as numpy statements and gives the same bits.  ``check_resample`` lists what
+    is refused by name (``TypeError`` for dtypes, ``ValueError`` otherwise) before any device is touched."""
+    if (shape is None) == (factors is None):
+        raise ValueError("resample takes exactly one of shape and factors")
+    if how not in RESAMPLE_HOW:
+        raise ValueError(f"how = {how!r}, must be 'auto', 'nearest', 'linear' or 'area'")
+    if shape is None:
+        if not isinstance(volume, Tensor):
+            raise TypeError(f"volume must be a tensor, got {type(volume).__name__}")
+        s = tuple(int(v) for v in volume.shape)
+        shape = resample_shape(s[1:] if len(s) == 4 and s[0] == 1 else s, factors) if len(s) in (3, 4) else (0, 0, 0)
+    (X, Y, Z), ops = check_resample(volume, shape, how)
+    m = tuple(int(v) for v in shape)
+    v = (volume[0] if volume.ndim == 4 else volume).contiguous()
+    if not v.is_cuda:
+        if v.dtype == torch.uint16:
+            out = torch.from_numpy(_resample_host(v.view(torch.int16).numpy().view(np.uint16), m, ops)
+                                   .view(np.int16)).view(torch.uint16)
+        else:
+            out = torch.from_numpy(_resample_host(v.numpy(), m, ops))
+    else:
+        code = _SK_U16 if v.dtype == torch.uint16 else _ffi.dtype_code(v)
+        geometry = (code, X, Y, Z, *m, *(RESAMPLE_OP[op] for op in ops))
+        nbytes = int(_ffi.lib.sk_resample_workspace_bytes(*geometry))
+        if nbytes == 0:
+            raise ValueError(_ffi.last_error())
+        out = torch.empty(m, dtype=v.dtype, device=v.device)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+        _ffi.check(_ffi.lib.sk_resample_volume(_ffi.ptr(v), _ffi.ptr(out), *geometry, _ffi.ptr(workspace), nbytes,
+                                               _ffi.stream_ptr(v.device)))
+    return out.unsqueeze(0) if volume.ndim == 4 else out
+
+
+def resample_path(dtype, src_shape, dst_shape, ops) -> str:
+    """Which kernel ``resample`` runs for this geometry, answered on the host: ``"gather"`` (nearest on every axis),
+    ``"acc32"`` (weighted sums in 32 bits) or ``"acc64"``."""
+    code = {torch.uint8: 4, torch.uint16: _SK_U16, torch.int16: 2, torch.int32: 3}[dtype]
+    rc = int(_ffi.lib.sk_resample_path(code, *(int(n) for n in src_shape), *(int(n) for n in dst_shape),
+                                       *(RESAMPLE_OP[op] for op in ops)))
+    _ffi.check(rc if rc < 0 else 0)
+    return RESAMPLE_PATHS[rc]
