@@ -467,7 +467,12 @@ int sk_baked_embed_to_prob(const float* embedding, const float* baked, float* ou
                            int64_t voxels, const float* sigma_host, float eps, void* stream);
 
 /* Stand-alone Tversky value (train/loss.py:95-212): predicted, ground_truth (B, voxels) fp32
- * (ground_truth != 0 = foreground); loss = batch mean of 1 - (TP+eps)/(TP+alpha(FP+1e-10)+beta FN+eps).
+ * (ground_truth != 0 = foreground); loss = batch mean of 1 - (TP+eps)/(TP+alpha(FP+1e-10)+beta FN+eps),
+ * a sample without foreground contributing the constant 1 - eps/(alpha 1e-10 + eps).
+ * Every non-zero value of ground_truth, whatever its sign or id, counts as ONE foreground.  The reference
+ * expands a ground truth with several ids into one mask per id (train/loss.py:175-182), so this equals the
+ * reference for binary ground truth only -- what its callers pass (masks.gt(0), engine.py:468).  sk_train_loss
+ * and sk_train_cldice_term_field count `> 0` instead: a negative value is background there, foreground here.
  * workspace: sk_train_loss_workspace_floats(B, voxels) floats. */
 int sk_train_tversky(const float* predicted, const float* ground_truth, int B, int64_t voxels,
                      float alpha, float beta, float eps, float* loss, float* workspace,

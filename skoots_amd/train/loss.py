@@ -21,6 +21,12 @@ class tversky:
     predicted (B, 1, X, Y, Z) probabilities; ground_truth (B, 1, X, Y, Z), 0 = background (the
     reference's callers pass ``masks.gt(0).float()``, engine.py:468).  Per sample
     1 - (TP + eps) / (TP + alpha (FP + 1e-10) + beta FN + eps), then the batch mean.  Value only.
+
+    Every non-zero value of ground_truth counts as one foreground (sk_train_tversky, ``!= 0``).  The reference
+    expands a ground truth that holds several ids into one mask per id (train/loss.py:175-182), so the two agree
+    for binary ground truth only -- pass ``masks.gt(0)`` as the reference's callers do.  The fused step
+    (``fused_loss``, sk_train_loss) counts ``> 0``: a negative value is background there and foreground here.
+    tests/test_hip_train_loss.py pins both rules.
     """
 
     def __init__(self, alpha: float, beta: float, eps: float):
