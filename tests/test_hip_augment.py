@@ -7,88 +7,23 @@ round either way depending on the order torch's kernels happen to use.  The test
 float64 itself; a voxel may differ from the fixture only if some coordinate lies within 1e-4 voxel of a boundary,
 only if both the port's and the fixture's value are samples the other rounding would give, and at most 1e-4 of all
 voxels (at least one) may do so."""
-import math
-from itertools import product
-
 import numpy as np
 import pytest
 import torch
 
+from tests.augment_cases import EPS, params_from_plan
+from tests.augment_cases import voxel_candidates as _voxel_candidates
 from tests.test_augment_plan import assert_points_match, case_cfg, case_inputs, case_plan
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-EPS = 1e-4
-
-
-def _cands(c):
-    f = math.floor(c)
-    if abs(c - f - 0.5) < EPS:
-        return [f, f + 1]
-    return [int(np.rint(c))]
-
-
-def _rss(angle, shear, scale):
-    rot, sx = math.radians(angle), math.radians(shear)
-    a = math.cos(rot)
-    b = -math.cos(rot) * math.tan(sx) - math.sin(rot)
-    c = math.sin(rot)
-    d = -math.sin(rot) * math.tan(sx) + math.cos(rot)
-    return [d / scale, -b / scale, 0.0, -c / scale, a / scale, 0.0]
-
-
-def _lin64(dst, n_in, n_out):
-    src = max(n_in / n_out * (dst + 0.5) - 0.5, 0.0)
-    i0 = int(src)
-    return i0, (1 if i0 < n_in - 1 else 0), src - i0
 
 
 def voxel_candidates(image, masks, g, plan, t, x, y, z):
     """Every (image, mask) value the output voxel (x, y, z) can take when each stage's float64 coordinate that lies
-    within EPS of a rounding boundary may round either way."""
-    (w1, h1, d1), (w2, h2, d2) = t.crop_extents(image.shape)
-    x0, y0, z0 = g["crop1"]
-    cx0, cy0, cz0 = g["crop2"]
-    xa = (w2 - 1 - x if plan.flip_x else x) + cx0
-    ya = (h2 - 1 - y if plan.flip_y else y) + cy0
-    za = (d2 - 1 - z if plan.flip_z else z) + cz0
-    pos = [(xa, ya, za)]
-    if plan.affine:
-        m = _rss(plan.angle, plan.shear, plan.scale)
-        bx, by = ya - 0.5 * h1 + 0.5, xa - 0.5 * w1 + 0.5
-        gx = (bx * m[0] + by * m[1]) / (0.5 * h1)
-        gy = (bx * m[3] + by * m[4]) / (0.5 * w1)
-        pos = [(sx, sy, za) for sx in _cands(((gy + 1) * w1 - 1) / 2) for sy in _cands(((gx + 1) * h1 - 1) / 2)]
-    if plan.elastic:
-        f = plan.elastic_field.double().cpu().numpy()[0]
-        mag = (0.01, 0.05, 0.05)
-        out = []
-        for (xe, ye, ze) in pos:
-            if not (0 <= xe < w1 and 0 <= ye < h1):
-                out.append(None)
-                continue
-            (a0, ap, la), (b0, bp, lb), (c0, cp, lc) = _lin64(xe, 2, w1), _lin64(ye, 6, h1), _lin64(ze, 6, d1)
-            off = []
-            for c in range(3):
-                v = 0.0
-                for da, wa in ((0, 1 - la), (ap, la)):
-                    for db, wb in ((0, 1 - lb), (bp, lb)):
-                        for dc, wc in ((0, 1 - lc), (cp, lc)):
-                            v += wa * wb * wc * f[c, a0 + da, b0 + db, c0 + dc]
-                off.append(v * mag[c])
-            lin = lambda i, n: -1.0 if n == 1 else -1.0 + 2.0 * i / (n - 1)  # noqa: E731
-            gz, gy, gx = lin(ze, d1) + off[0], lin(ye, h1) + off[1], lin(xe, w1) + off[2]
-            out += list(product(_cands((gx + 1) / 2 * (w1 - 1)), _cands((gy + 1) / 2 * (h1 - 1)),
-                                _cands((gz + 1) / 2 * (d1 - 1))))
-        pos = out
-    vals = set()
-    for p in pos:
-        if p is None or not (0 <= p[0] < w1 and 0 <= p[1] < h1 and 0 <= p[2] < d1):
-            vals.add((0.0, 0))
-        else:
-            s = (0, p[0] + x0, p[1] + y0, p[2] + z0)
-            vals.add((float(image[s]), int(masks[s])))
-    return vals
+    within EPS of a rounding boundary may round either way (tests/augment_cases.py)."""
+    p = params_from_plan(t, image.shape, g, plan)
+    return _voxel_candidates(p, image[0].numpy(), masks[0].numpy(), int(x), int(y), int(z))
 
 
 def _transform(d, i):
