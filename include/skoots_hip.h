@@ -1065,6 +1065,53 @@ int sk_resample_volume(const void* src, void* dst, int dtype, int X, int Y, int 
                        int op_z, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Exact rank and tap filters (ABI 33; the reference declares median_filter, mean_filter, dilate,
+ * binary_erosion and gauss_filter in skoots/lib/morphology.py, and the first three cannot run)
+ * ------------------------------------------------------------------------ */
+
+#define SK_FILTER_BORDER_ZERO 0   /* a sample outside 0 <= i < n is 0 */
+#define SK_FILTER_BORDER_EDGE 1   /* clamp(i, 0, n - 1) */
+#define SK_FILTER_BORDER_MIRROR 2 /* j = i mod 2 n (non-negative); j < n ? j : 2 n - 1 - j: numpy's symmetric */
+
+#define SK_FILTER_PATH_EXTREME 0     /* rank 0 or n - 1: one min / max pass over the window */
+#define SK_FILTER_PATH_RADIX 1       /* any other rank: bitwise radix descent over the key bits */
+#define SK_FILTER_PATH_ACC32 2       /* taps, sums in 32 bits: W vmax < 2^32 */
+#define SK_FILTER_PATH_ACC64 3       /* taps, sums in 64 bits */
+#define SK_FILTER_PATH_NETWORK 4     /* the median of radius (1, 1, 0) and (1, 1, 1): a min / max exchange network */
+#define SK_FILTER_PATH_VECTOR_ROWS 8 /* or-ed in: rows are dword multiples on dword-aligned bases, 16-byte loads and stores */
+
+#define SK_FILTER_METHOD_AUTO 0    /* what sk_filter_path names */
+#define SK_FILTER_METHOD_RADIX 1   /* the radix descent for every rank and window, the ends included */
+#define SK_FILTER_METHOD_NETWORK 2 /* the exchange network; refused where it is not built */
+
+/* in: contiguous (X, Y, Z) of dtype, Z innermost; out: the same shape and dtype, another buffer.  The border rule gives
+ * the source index of any integer i on an axis of extent n, windows wider than the volume included.
+ * sk_filter_rank: radii rx, ry, rz in 0 .. 2; the window of an output voxel holds n = (2 rx + 1)(2 ry + 1)(2 rz + 1)
+ * bordered samples and the output is the rank-th smallest of them, rank in 0 .. n - 1 counted from 0.  dtype SK_U8,
+ * SK_U16 or SK_F32; float32 is ordered by value (-0.0 and 0.0 are equal and either may come back, infinities are
+ * ordinary values, a NaN anywhere is outside the definition).  method chooses the selection, SK_FILTER_METHOD_*: every
+ * method gives the same bits, and the forced ones exist so that they can be timed and tested against each other.
+ * sk_filter_taps: per axis an odd number 1 .. 17 of integer taps >= 0 whose sum W_axis is in 1 .. 4096 (HOST arrays,
+ * read before the call returns).  The output is (S + W / 2) / W in integers, S the sum of wx wy wz v over the product
+ * of the three lists applied to the bordered samples, W = Wx Wy Wz: the exact weighted mean rounded to nearest, halves
+ * up, rounded once.  dtype SK_U8 or SK_U16.  Sums are 32-bit where W vmax < 2^32 and 64-bit otherwise; both are exact.
+ * One launch on the caller's stream, no workspace, nothing allocated; the same bits on every run.  Checked before the
+ * launch (SK_ERR_ARG): null pointers, in == out, element alignment, dtype, extents < 1 or > 2^30, border, radius, rank,
+ * method,
+ * tap counts, negative taps, tap sums, more than 2^31 - 1 workgroups.
+ * sk_filter_path: HOST, no GPU needed: the kernel a geometry takes, SK_FILTER_PATH_* (or SK_ERR_ARG).  With any tap
+ * list not NULL it answers for sk_filter_taps (rx, ry, rz and rank are ignored), else for sk_filter_rank.  aligned:
+ * whether in and out are dword aligned.  sk_filter_tile(0 / 1 / 2): the rank kernels' tile, rows in x, rows in y and
+ * bytes along z (4, 8, 128), for tests that place their sizes around it. */
+int sk_filter_tile(int axis);
+int sk_filter_path(int dtype, int X, int Y, int Z, int rx, int ry, int rz, int rank, const int* taps_x, int nx,
+                   const int* taps_y, int ny, const int* taps_z, int nz, int aligned);
+int sk_filter_rank(const void* in, void* out, int dtype, int X, int Y, int Z, int rx, int ry, int rz, int rank, int border,
+                   int method, void* stream);
+int sk_filter_taps(const void* in, void* out, int dtype, int X, int Y, int Z, const int* taps_x, int nx, const int* taps_y,
+                   int ny, const int* taps_z, int nz, int border, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Instance measurements: volume, box, moments and face area of every instance
  * ------------------------------------------------------------------------ */
 

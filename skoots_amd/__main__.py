@@ -4,7 +4,9 @@ the reference CLI (skoots/__main__.py:19-46, 78-98), and ``--skeletonize-train-d
 and ``.trch`` tensors under PATH -> TIFF stacks, no eval (skoots/__main__.py:70-74, 84, 108-109).  With it every switch of
 the reference's main command exists here.  ``--pyramid`` (not in the reference) makes eval also write
 ``<base>_skoots.ome.zarr``, the multiscale OME-Zarr group of image, instance mask and skeleton.  ``--rescale FX FY FZ``
-(not in the reference) resamples the image by those factors before the network and writes the mask on the input's grid."""
+(not in the reference) resamples the image by those factors before the network and writes the mask on the input's grid.
+``--denoise HOW A B C`` (not in the reference) filters the integer image on the device before that: ``HOW`` one of
+``median | mean | min | max`` with three integer radii, or ``gauss`` with three sigmas in voxels."""
 import argparse
 import glob
 import logging
@@ -28,6 +30,10 @@ def build_parser() -> argparse.ArgumentParser:
     eval_args.add_argument("--pyramid", action="store_true",
                            help="also writes <base>_skoots.ome.zarr: multiscale pyramids of the image, the instance mask "
                                 "and the skeleton as one OME-Zarr group (skoots_amd.utils.pyramid)")
+    eval_args.add_argument("--denoise", type=str, nargs=4, default=None, metavar=("HOW", "A", "B", "C"),
+                           help="filters the integer image on the device before the network (and before --rescale), mirror "
+                                "borders: HOW is median, mean, min or max with three integer radii along x, y and z, or gauss "
+                                "with three sigmas in voxels (skoots_amd.lib.morphology.filter_volume)")
     eval_args.add_argument("--rescale", type=float, nargs=3, default=None, metavar=("FX", "FY", "FZ"),
                            help="output voxels per input voxel along x, y and z: the image is resampled on the device to the "
                                 "voxel size the model was trained at, the instance mask is written on the input's own grid "
@@ -46,6 +52,15 @@ def build_parser() -> argparse.ArgumentParser:
 def parse_args(argv=None) -> argparse.Namespace:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.denoise is not None:
+        from skoots_amd.lib.eval import denoise_arguments
+        how, numbers = args.denoise[0], args.denoise[1:]
+        try:
+            numbers = tuple(float(v) if how == "gauss" else int(v) for v in numbers)
+            denoise_arguments((how, numbers))
+        except ValueError as e:
+            parser.error(f"--denoise: {e}")
+        args.denoise = (how, numbers)
     if args.skeletonize_train_data is None and args.convert is None and args.image is None:
         parser.error("the following arguments are required: --image")
     if args.rescale is not None and not all(0 < v < float("inf") for v in args.rescale):
@@ -77,6 +92,8 @@ def main(argv=None):
         extra = {"pyramid": True} if args.pyramid else {}   # the keywords go down only when they are set
         if args.rescale is not None:
             extra["rescale"] = tuple(args.rescale)
+        if args.denoise is not None:
+            extra["denoise"] = args.denoise
         sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached, output_huffman=args.output_huffman,
                 **extra)
 

@@ -215,6 +215,10 @@ _SIGS = {
     "sk_resample_workspace_bytes": (sz, [i32] * 10),
     "sk_resample_path": (i32, [i32] * 10),
     "sk_resample_volume": (i32, [vp, vp] + [i32] * 10 + [vp, sz, vp]),
+    "sk_filter_tile": (i32, [i32]),
+    "sk_filter_path": (i32, [i32] * 8 + [ip, i32, ip, i32, ip, i32, i32]),
+    "sk_filter_rank": (i32, [vp, vp] + [i32] * 10 + [vp]),
+    "sk_filter_taps": (i32, [vp, vp] + [i32] * 4 + [ip, i32, ip, i32, ip, i32, i32, vp]),
     "sk_instance_stats_row_values": (i32, [i32]),
     "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "sk_instance_mesh_cells": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp]),

@@ -265,10 +265,34 @@ def _cfg_get(cfg, section: str, key: str, default=None):
     return sec.get(key, default) if isinstance(sec, dict) else getattr(sec, key, default)
 
 
+DENOISE_HOW = ("median", "mean", "min", "max", "gauss")
+
+
+def denoise_arguments(denoise) -> dict:
+    """``eval``'s ``denoise=(how, (a, b, c))`` as the keywords of ``lib.morphology.filter_volume``: ``how`` one of
+    ``DENOISE_HOW``, the three numbers integer radii, or sigmas for ``"gauss"``; checked by ``filter_plan``."""
+    from .morphology import filter_plan
+    try:
+        how, numbers = denoise
+        numbers = tuple(numbers)
+    except (TypeError, ValueError):
+        raise ValueError(f"denoise must be (how, (a, b, c)), got {denoise!r}") from None
+    if how not in DENOISE_HOW:
+        raise ValueError(f"denoise how = {how!r}, must be one of {DENOISE_HOW}")
+    if how == "gauss":
+        kwargs = dict(how=how, sigma=numbers)
+    else:
+        if len(numbers) == 3 and all(isinstance(v, float) and float(v).is_integer() for v in numbers):
+            numbers = tuple(int(v) for v in numbers)
+        kwargs = dict(how=how, radius=numbers)
+    filter_plan(**kwargs)
+    return kwargs
+
+
 @torch.inference_mode()
 def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16",
          read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None, pyramid: bool = False,
-         rescale=None) -> None:
+         rescale=None, denoise=None) -> None:
     """Evaluates SKOOTS on an arbitrary image (drop-in for ``skoots.lib.eval.eval``).
 
     ``precision`` (not in the reference's signature; keyword with the reference's behaviour as default): "fp16" = what the
@@ -311,6 +335,14 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     smaller than an input voxel can be missing from the file.  ``rescale=(1, 1, 1)`` takes this path and gives the same
     files.  Together with ``pyramid`` it is refused by name: run ``utils.pyramid`` on the outputs.
 
+    ``denoise`` (keyword, not in the reference's signature; ``None`` by default, and without it every output is byte
+    for byte what it was): ``(how, (a, b, c))`` with ``how`` one of ``"median"``, ``"mean"``, ``"min"``, ``"max"`` --
+    ``(a, b, c)`` the integer radii along x, y, z -- or ``"gauss"`` -- the three sigmas in voxels.  The integer samples as
+    read (uint8 or uint16, or signed with values in 0 .. 65535) are filtered on the device in their own dtype with
+    ``lib.morphology.filter_volume(..., border="mirror")``, before ``rescale`` if both are given and before the fp16
+    conversion: ``("median", (1, 1, 0))`` is the 3x3x1 median that removes shot noise and hot pixels.  A float image is
+    refused by name before the model is built.  ``pyramid=True`` still writes the image as read.
+
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
     ``SKOOTS.VECTOR_SCALING`` and ``MODEL.*``), ``model_state_dict`` and optionally
     ``dataset_mean`` / ``dataset_std`` (eval.py:51-55, 87-88, 99, 117-118).
@@ -325,6 +357,8 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
             raise ValueError("pyramid=True together with rescale is not built: run skoots_amd.utils.pyramid on the outputs")
         from .morphology import resample_shape
         resample_shape((1, 1, 1), rescale)   # three positive finite numbers, or a ValueError that says so
+    if denoise is not None:
+        denoise = denoise_arguments(denoise)   # how and its three numbers, or a ValueError that says so
     start = time.time()
     logging.info(f"Loading model file: {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -347,11 +381,12 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         stack = stack[[2], ...] if stack.shape[0] > 3 else stack  # eval.py:64 -> [C=1, X, Y, Z]
         c, x, y, z = stack.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {stack.dtype}")
-        raw_img = stack[0] if pyramid or rescale is not None else None
-        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous() if rescale is None else None  # eval.py:80
+        raw_img = stack[0] if pyramid or rescale is not None or denoise is not None else None
+        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous() if rescale is None and denoise is None \
+            else None  # eval.py:80
         # the statistics fallback stays the CPU reduction over the same fp16 values: the image comes back for it only
         img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) and \
-            rescale is None else None
+            rescale is None and denoise is None else None
     else:
         image = _read_image(image_path)  # [Z, X, Y(, C)]
         image = image[..., np.newaxis] if image.ndim == 3 else image
@@ -360,10 +395,10 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         c, x, y, z = image.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {image.dtype}")
         img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16) \
-            if rescale is None else None  # eval.py:80
+            if rescale is None and denoise is None else None  # eval.py:80
         dev_img = None
         raw_img = None
-        if pyramid or rescale is not None:     # the samples as read: uint16 through its bit pattern
+        if pyramid or rescale is not None or denoise is not None:     # the samples as read: uint16 through its bit pattern
             raw = np.ascontiguousarray(image[0])
             raw_img = (torch.from_numpy(raw.view(np.int16)).view(torch.uint16) if raw.dtype == np.uint16
                        else torch.from_numpy(raw))
@@ -377,16 +412,33 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
             aniso = None
         spacing = check_spacing(aniso if aniso is not None else (1.0, 1.0, 3.0))
     input_shape = (x, y, z)
+    denoised = None
+    if denoise is not None:
+        # the raw samples go up and are filtered there, in their own dtype; raw_img stays the image as read
+        from .morphology import check_filter, check_pool_volume, filter_volume, pool_source
+        if raw_img.dtype.is_floating_point:
+            raise TypeError(f"image is {raw_img.dtype}: denoise filters the integer samples as read (uint8 / uint16), a float "
+                            "image is not denoised")
+        check_pool_volume(raw_img, "mean", "image")
+        denoised = pool_source(raw_img.to(device), "mean", "image")   # signed samples: 0 .. 65535 or a ValueError
+        check_filter(denoised, border="mirror", name="image", **denoise)
+        logging.info(f"Denoising the image: {denoise}")
+        denoised = filter_volume(denoised, border="mirror", **denoise)
+        if rescale is None:
+            dev_img = _to_f32(denoised).to(torch.float16).contiguous()
+            img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None
+            denoised = None
     if rescale is not None:
         # the raw samples go up and are resampled there; everything below lives on the resampled grid
         from .morphology import check_pool_volume, check_resample, pool_source, resample
         x, y, z = resample_shape(input_shape, rescale)
         check_pool_volume(raw_img, "mean", "image")                  # float images are refused by name, as pool refuses them
-        raw_dev = pool_source(raw_img.to(device), "mean", "image")   # signed samples: 0 .. 65535 or a ValueError
+        raw_dev = denoised if denoised is not None else \
+            pool_source(raw_img.to(device), "mean", "image")         # signed samples: 0 .. 65535 or a ValueError
         check_resample(raw_dev, (x, y, z), "auto", "image")
         logging.info(f"Rescaling the image from {input_shape} to {(x, y, z)}")
         dev_img = _to_f32(resample(raw_dev, shape=(x, y, z), how="auto")).to(torch.float16).contiguous()
-        del raw_dev
+        del raw_dev, denoised
         img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None
     mean = checkpoint["dataset_mean"] if "dataset_mean" in checkpoint else img16.mean()  # eval.py:87
     std = checkpoint["dataset_std"] if "dataset_std" in checkpoint else img16.std()  # eval.py:88

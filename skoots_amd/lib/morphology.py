@@ -8,7 +8,13 @@ transform of every instance of a label volume, which the 
 either, nor ``nearest_label``, the nearest instance of every voxel and its distance, nor
 ``local_thickness``, the radius of the largest ball inside the instance that holds the voxel, nor
 ``geodesic_assign``, the nearest seed of every voxel along paths inside its instance, nor
-``pool``, one level of a multiscale pyramid by mode, mean or max."""
+``pool``, one level of a multiscale pyramid by mode, mean or max, nor ``resample`` (section 37).
+
+``filter_volume`` is the exact rank filter (median, min, max, any rank) and the exact integer tap
+filter (box mean, Gaussian) in front of the network, and under the reference's names ``median_filter``, ``dilate`` and
+``binary_erosion`` (skoots/lib/morphology.py:131-152, 202-232) run on float32 tensors with zero padding.  The
+reference's ``mean_filter`` and ``gauss_filter`` on float tensors are not built: a float sum has no defined order, so
+nothing exact could be promised; use ``filter_volume(..., "mean" | "gauss")`` on the integer image."""
 from __future__ import annotations
 
 import ctypes as C
@@ -913,3 +919,298 @@ def resample_path(dtype, src_shape, dst_shape, ops) -> str:
                                        *(RESAMPLE_OP[op] for op in ops)))
     _ffi.check(rc if rc < 0 else 0)
     return RESAMPLE_PATHS[rc]
+
+
+# ---- exact rank and tap filters ----
+
+FILTER_HOW = ("median", "min", "max", "rank", "mean", "gauss", "taps")
+FILTER_BORDER = {"zero": 0, "edge": 1, "mirror": 2}     # SK_FILTER_BORDER_* of include/skoots_hip.h
+FILTER_KERNELS = ("extreme", "radix", "acc32", "acc64", "network")   # SK_FILTER_PATH_*: sk_filter_path's low three bits
+FILTER_METHOD = {"auto": 0, "radix": 1, "network": 2}    # SK_FILTER_METHOD_*: the selection of a rank filter
+FILTER_TILE = (4, 8, 128)                                # the rank kernels' tile: rows in x, rows in y, bytes along z
+FILTER_MAX_RANK_RADIUS, FILTER_MAX_TAP_RADIUS, FILTER_MAX_TAP_SUM = 2, 8, 4096
+_FILTER_MAX_EXTENT = 2 ** 30
+_FILTER_CODE = {torch.uint8: 4, torch.uint16: _SK_U16, torch.float32: 1}
+
+
+def border_index(i: int, n: int, border: str) -> int:
+    """The source index of any integer ``i`` on an axis of extent ``n``: ``"zero"`` -1 outside ``0 <= i < n`` (the sample
+    is 0), ``"edge"`` ``clamp(i, 0, n - 1)``, ``"mirror"`` ``j = i mod 2n``, ``j`` if ``j < n`` else ``2n - 1 - j``
+    (numpy's ``symmetric``: the edge sample repeats, reflection repeats as often as needed)."""
+    if border not in FILTER_BORDER:
+        raise ValueError(f"border = {border!r}, must be 'zero', 'edge' or 'mirror'")
+    i, n = int(i), int(n)
+    if n < 1:
+        raise ValueError(f"an axis has at least one sample, got n = {n}")
+    if 0 <= i < n:
+        return i
+    if border == "zero":
+        return -1
+    if border == "edge":
+        return min(max(i, 0), n - 1)
+    j = i % (2 * n)
+    return j if j < n else 2 * n - 1 - j
+
+
+def gaussian_taps(sigma: float, radius=None, total: int = 256):
+    """Integer taps of a Gaussian of ``sigma`` voxels that sum to ``total``: the only place of the filters a float
+    enters.  ``sigma == 0`` gives ``[total]``.  Otherwise ``r = radius`` if given, else ``min(8, ceil(3 sigma))``;
+    ``g_i = exp(-i^2 / (2 sigma^2))`` in float64 for ``i = -r .. r``, normalised to sum 1; ``w_i = floor(total g_i + 0.5)``
+    for ``i != 0`` and the centre tap is ``total`` minus the others; zero taps at both ends are trimmed symmetrically."""
+    sigma = float(sigma)
+    if isinstance(total, bool) or not isinstance(total, (int, np.integer)) or not 1 <= total <= FILTER_MAX_TAP_SUM:
+        raise ValueError(f"total must be an integer in 1 .. {FILTER_MAX_TAP_SUM}, got {total!r}")
+    if not 0 <= sigma < float("inf"):
+        raise ValueError(f"sigma must be a non-negative finite number, got {sigma!r}")
+    total = int(total)
+    if sigma == 0:
+        return [total]
+    if radius is None:
+        r = min(FILTER_MAX_TAP_RADIUS, int(np.ceil(3 * sigma)))
+    else:
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= FILTER_MAX_TAP_RADIUS:
+            raise ValueError(f"radius must be an integer in 0 .. {FILTER_MAX_TAP_RADIUS}, got {radius!r}")
+        r = int(radius)
+    i = np.arange(-r, r + 1, dtype=np.float64)
+    g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    g = g / g.sum()
+    w = [int(v) for v in np.floor(total * g + 0.5)]
+    w[r] = total - (sum(w) - w[r])
+    while len(w) > 1 and w[0] == 0 and w[-1] == 0:
+        w = w[1:-1]
+    if min(w) < 0:
+        raise ValueError(f"sigma = {sigma} at radius {r} leaves a negative centre tap of total {total}")
+    return w
+
+
+def _three(values, what: str, kind=int):
+    try:
+        v = tuple(values.detach().cpu().tolist() if isinstance(values, Tensor) else values)
+    except TypeError:
+        v = ()
+    if len(v) != 3:
+        raise ValueError(f"{what} must be three numbers (x, y, z), got {values!r}")
+    if kind is int and not all(isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_)) for k in v):
+        raise ValueError(f"{what} must be three integers (x, y, z), got {values!r}")
+    return tuple(kind(k) for k in v)
+
+
+def filter_plan(how: str, radius=None, rank=None, sigma=None, taps=None):
+    """What ``how`` and its arguments ask for, checked by name: ``("rank", (rx, ry, rz), rank)`` or ``("taps", (tx, ty,
+    tz))`` with three lists of integers."""
+    if how not in FILTER_HOW:
+        raise ValueError(f"how = {how!r}, must be one of {FILTER_HOW}")
+    takes = {"median": ("radius",), "min": ("radius",), "max": ("radius",), "rank": ("radius", "rank"), "mean": ("radius",),
+             "gauss": ("sigma",), "taps": ("taps",)}[how]
+    given = {"radius": radius, "rank": rank, "sigma": sigma, "taps": taps}
+    for key, value in given.items():
+        if (value is not None) != (key in takes):
+            raise ValueError(f"how={how!r} takes {' and '.join(takes)}" + (f", not {key}" if value is not None else
+                                                                         f": {key} is missing"))
+    if how in ("median", "min", "max", "rank"):
+        r = _three(radius, "radius")
+        if not all(0 <= k <= FILTER_MAX_RANK_RADIUS for k in r):
+            raise ValueError(f"radius = {r}: a rank filter takes radii in 0 .. {FILTER_MAX_RANK_RADIUS} per axis")
+        n = (2 * r[0] + 1) * (2 * r[1] + 1) * (2 * r[2] + 1)
+        if how == "rank":
+            rank = {"min": 0, "median": n // 2, "max": n - 1}.get(rank, rank) if isinstance(rank, str) else rank
+            if isinstance(rank, (bool, np.bool_)) or not isinstance(rank, (int, np.integer)) or not 0 <= rank < n:
+                raise ValueError(f"rank = {rank!r}: the window of radius {r} has the ranks 0 .. {n - 1}, or 'min', 'median', "
+                                 "'max'")
+            return "rank", r, int(rank)
+        return "rank", r, {"min": 0, "median": n // 2, "max": n - 1}[how]
+    if how == "mean":
+        r = _three(radius, "radius")
+        if not all(0 <= k <= FILTER_MAX_TAP_RADIUS for k in r):
+            raise ValueError(f"radius = {r}: a mean takes radii in 0 .. {FILTER_MAX_TAP_RADIUS} per axis")
+        return "taps", tuple([1] * (2 * k + 1) for k in r)
+    if how == "gauss":
+        return "taps", tuple(gaussian_taps(s) for s in _three(sigma, "sigma", float))
+    try:
+        lists = tuple([k for k in (t.tolist() if isinstance(t, (Tensor, np.ndarray)) else t)] for t in taps)
+    except TypeError:
+        lists = ()
+    if len(lists) != 3:
+        raise ValueError(f"taps must be three lists of integers (x, y, z), got {taps!r}")
+    for axis, t in zip("xyz", lists):
+        if not all(isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_)) and k >= 0 for k in t):
+            raise ValueError(f"the taps of {axis} must be non-negative integers, got {t!r}")
+        if len(t) % 2 == 0 or not 1 <= len(t) <= 2 * FILTER_MAX_TAP_RADIUS + 1:
+            raise ValueError(f"{len(t)} taps on {axis}: the count must be odd and in 1 .. {2 * FILTER_MAX_TAP_RADIUS + 1}")
+        if not 1 <= sum(t) <= FILTER_MAX_TAP_SUM:
+            raise ValueError(f"the tap sum of {axis} is {sum(t)}, it must be in 1 .. {FILTER_MAX_TAP_SUM}")
+    return "taps", tuple([int(k) for k in t] for t in lists)
+
+
+def check_filter(volume, how: str, radius=None, rank=None, sigma=None, taps=None, border: str = "mirror",
+                 name: str = "volume"):
+    """What ``filter_volume`` takes, checked on the tensor's description alone, before any device is touched: the
+    (X, Y, Z) of it and ``filter_plan``'s answer.  Refused by name: a ``how`` or ``border`` that is not one, arguments
+    that do not belong to ``how`` or are missing, rank radii beyond 2, mean radii beyond 8, a rank outside the window,
+    tap lists that are not three odd-length lists of non-negative integers with sums in 1 .. 4096 (``ValueError``); a
+    volume that is not a tensor, float volumes under a tap filter, and every dtype but uint8, uint16 and -- rank filters
+    only -- float32 (``TypeError``); shapes that are not (X, Y, Z) or (1, X, Y, Z), extents beyond 2^30."""
+    if border not in FILTER_BORDER:
+        raise ValueError(f"border = {border!r}, must be 'zero', 'edge' or 'mirror'")
+    plan = filter_plan(how, radius, rank, sigma, taps)
+    if not isinstance(volume, Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(volume).__name__}")
+    dt = volume.dtype
+    if plan[0] == "taps" and (dt.is_floating_point or dt.is_complex or dt == torch.bool):
+        raise TypeError(f"{name} is {dt}: float, complex and bool volumes take no tap filter, a float sum has no defined "
+                        "order; filter the integer image (uint8 / uint16)")
+    allowed = (torch.uint8, torch.uint16) + ((torch.float32,) if plan[0] == "rank" else ())
+    if dt not in allowed:
+        raise TypeError(f"{name} is {dt}: how={how!r} takes " + ("uint8, uint16 or float32" if plan[0] == "rank" else
+                                                                "uint8 or uint16"))
+    s = tuple(int(v) for v in volume.shape)
+    s = s[1:] if len(s) == 4 and s[0] == 1 else s
+    if len(s) != 3 or min(s) < 1:
+        raise ValueError(f"{name} has the shape {tuple(volume.shape)}: it must be (X, Y, Z) or (1, X, Y, Z) with every "
+                         "extent at least 1")
+    if max(s) > _FILTER_MAX_EXTENT:
+        raise ValueError(f"{name} of shape {s} is too large to filter: every extent must stay within 2^30")
+    return s, plan
+
+
+def _bordered(a: np.ndarray, axis: int, r: int, border: str) -> np.ndarray:
+    """``a`` with ``r`` bordered samples on both sides of ``axis``, by ``border_index``"""
+    n = a.shape[axis]
+    idx = np.array([border_index(i, n, border) for i in range(-r, n + r)], dtype=np.int64)
+    out = np.take(a, np.maximum(idx, 0), axis=axis)
+    if (idx < 0).any():
+        out = np.where((idx >= 0).reshape([-1 if d == axis else 1 for d in range(a.ndim)]), out, np.zeros((), a.dtype))
+    return out
+
+
+def _filter_host(a: np.ndarray, plan, border: str) -> np.ndarray:
+    """The definitions of ``filter_volume`` as numpy statements: the bordered volume, then the sorted window or the
+    three exact int64 sums and the one rounded division."""
+    if plan[0] == "rank":
+        _, r, rank = plan
+        p = a
+        for axis in range(3):
+            p = _bordered(p, axis, r[axis], border)
+        X, Y, Z = a.shape
+        window = np.stack([p[dx:dx + X, dy:dy + Y, dz:dz + Z] for dx in range(2 * r[0] + 1) for dy in range(2 * r[1] + 1)
+                           for dz in range(2 * r[2] + 1)])
+        return np.ascontiguousarray(np.partition(window, rank, axis=0)[rank])
+    s, W = a.astype(np.int64), 1
+    for axis, t in enumerate(plan[1]):
+        n = a.shape[axis]
+        p = _bordered(s, axis, len(t) // 2, border)
+        s = sum(int(w) * np.take(p, np.arange(k, k + n), axis=axis) for k, w in enumerate(t))
+        W *= sum(t)
+    return ((s + W // 2) // W).astype(a.dtype)
+
+
+def _int_array(values):
+    return (C.c_int32 * len(values))(*values)
+
+
+def filter_rank_device(v: Tensor, radius, rank: int, border: str = "mirror", method: str = "auto") -> Tensor:
+    """One launch of ``sk_filter_rank`` on a contiguous (X, Y, Z) device tensor that ``check_filter`` has passed.
+    ``method`` forces a selection (``FILTER_METHOD``); every method gives the same bits, and the forced ones exist for
+    tests and for tools/bench_filter.py."""
+    X, Y, Z = (int(n) for n in v.shape)
+    out = torch.empty_like(v)
+    _ffi.check(_ffi.lib.sk_filter_rank(_ffi.ptr(v), _ffi.ptr(out), _FILTER_CODE[v.dtype], X, Y, Z, *radius, int(rank),
+                                       FILTER_BORDER[border], FILTER_METHOD[method], _ffi.stream_ptr(v.device)))
+    return out
+
+
+def filter_volume(volume: Tensor, how: str, radius=None, rank=None, sigma=None, taps=None, border: str = "mirror") -> Tensor:
+    """An exactly defined neighbourhood filter of an (X, Y, Z) or (1, X, Y, Z) tensor on the device it lives on
+    (DESIGN.md section 38).  The result has the input's rank, dtype, shape and device.
+
+    ``border`` gives the sample at any source index ``i`` of an axis of extent ``n``, windows wider than the volume
+    included: ``"zero"`` 0 outside the volume (the reference's padding), ``"edge"`` ``clamp(i, 0, n - 1)``, ``"mirror"``
+    (the default) ``j = i mod 2n``, ``j`` if ``j < n`` else ``2n - 1 - j``.
+
+    Rank filters -- ``how="median" | "min" | "max"`` with ``radius=(rx, ry, rz)``, each 0 .. 2, and ``how="rank"`` with
+    ``rank`` as well, an integer in ``0 .. n - 1`` or one of those three names: the ``rank``-th smallest, counted from 0,
+    of the ``n = (2rx+1)(2ry+1)(2rz+1)`` bordered samples of the window; the median is rank ``n // 2``.  uint8, uint16 and
+    float32.  float32 is ordered by value: ``-0.0`` and ``0.0`` are equal and either may be returned, infinities are
+    ordinary values.  A volume with a NaN in it is outside the definition: what comes back is unspecified.
+
+    Tap filters -- ``how="mean"`` with ``radius`` up to 8 per axis (the taps ``[1] * (2r + 1)``), ``how="gauss"`` with
+    ``sigma=(sx, sy, sz)`` in voxels (``gaussian_taps`` of each), ``how="taps"`` with ``taps=(tx, ty, tz)``, three odd-length
+    lists of 1 .. 17 non-negative integers with sums in 1 .. 4096: ``(S + W // 2) // W`` with ``S`` the sum of
+    ``wx wy wz v`` over the product of the three lists applied to the bordered samples and ``W = Wx Wy Wz`` -- the exact
+    weighted mean rounded to nearest, halves up, rounded once; the rule of ``pool(..., "mean")`` and ``resample``.  uint8
+    and uint16.
+
+    On a device tensor this is one launch of ``sk_filter_rank`` or ``sk_filter_taps`` on the current stream; on a CPU
+    tensor the same definitions run as numpy statements and give the same bits.  ``check_filter`` lists what is refused
+    by name (``TypeError`` for dtypes, ``ValueError`` otherwise) before any device is touched."""
+    (X, Y, Z), plan = check_filter(volume, how, radius, rank, sigma, taps, border)
+    v = (volume[0] if volume.ndim == 4 else volume).contiguous()
+    if not v.is_cuda:
+        if v.dtype == torch.uint16:
+            out = torch.from_numpy(_filter_host(v.view(torch.int16).numpy().view(np.uint16), plan, border)
+                                   .view(np.int16)).view(torch.uint16)
+        else:
+            out = torch.from_numpy(_filter_host(v.numpy(), plan, border))
+    elif plan[0] == "rank":
+        out = filter_rank_device(v, plan[1], plan[2], border)
+    else:
+        out = torch.empty_like(v)
+        arrays = [_int_array(t) for t in plan[1]]
+        lists = [arg for a in arrays for arg in (a, len(a))]
+        _ffi.check(_ffi.lib.sk_filter_taps(_ffi.ptr(v), _ffi.ptr(out), _FILTER_CODE[v.dtype], X, Y, Z, *lists,
+                                           FILTER_BORDER[border], _ffi.stream_ptr(v.device)))
+    return out.unsqueeze(0) if volume.ndim == 4 else out
+
+
+def filter_path(dtype, shape, how: str, radius=None, rank=None, sigma=None, taps=None, aligned: bool = True):
+    """Which kernel ``filter_volume`` runs for this geometry, answered on the host: ``(kernel, rows)`` with ``kernel``
+    one of ``FILTER_KERNELS`` -- ``"extreme"`` (min and max: one pass over the window), ``"network"`` (the median of
+    radius (1, 1, 0) and (1, 1, 1)), ``"radix"`` (every other rank), ``"acc32"`` / ``"acc64"`` (taps, by the width of the
+    sums) -- and ``rows`` ``"vector"`` (16-byte loads and stores:
+    rows are dword multiples and the bases ``aligned``) or ``"scalar"``."""
+    assert tuple(int(_ffi.lib.sk_filter_tile(k)) for k in range(3)) == FILTER_TILE
+    plan = filter_plan(how, radius, rank, sigma, taps)
+    X, Y, Z = (int(n) for n in shape)
+    if plan[0] == "rank":
+        rc = int(_ffi.lib.sk_filter_path(_FILTER_CODE[dtype], X, Y, Z, *plan[1], plan[2], None, 0, None, 0, None, 0,
+                                         int(bool(aligned))))
+    else:
+        arrays = [_int_array(t) for t in plan[1]]
+        rc = int(_ffi.lib.sk_filter_path(_FILTER_CODE[dtype], X, Y, Z, 0, 0, 0, 0, *[arg for a in arrays for arg in (a, len(a))],
+                                         int(bool(aligned))))
+    _ffi.check(rc if rc < 0 else 0)
+    return FILTER_KERNELS[rc & 7], "vector" if rc & 8 else "scalar"
+
+
+def _reference_rank(image: Tensor, rank: int, name: str) -> Tensor:
+    """(B C, X, Y, Z): the rank-th smallest of the 27 zero-padded samples around every voxel of every channel"""
+    if not isinstance(image, Tensor) or image.ndim != 5:
+        raise ValueError(f"{name} must be a (B, C, X, Y, Z) tensor")
+    _ffi.require_gpu(image, name)
+    if image.dtype != torch.float32:
+        raise TypeError(f"{name} is {image.dtype}: the reference's filters take float32; integer images go through "
+                        "filter_volume")
+    b, c, w, h, d = image.shape
+    x = image.view(b * c, w, h, d)
+    if x.numel() == 0:
+        return torch.empty_like(x)
+    return torch.stack([filter_rank_device(x[i], (1, 1, 1), rank, "zero") for i in range(b * c)])
+
+
+def median_filter(input: Tensor) -> Tensor:
+    """The reference's ``median_filter`` (skoots/lib/morphology.py:202-210, which cannot run as written): the lower
+    median -- ``torch.median``'s, rank 13 of 27 -- of the 3x3x3 window with zero padding on a (B, C, X, Y, Z) float32
+    device tensor.  NaNs are outside the definition."""
+    return _reference_rank(input, 13, "input").view(input.shape)
+
+
+def dilate(input: Tensor) -> Tensor:
+    """The reference's ``dilate`` (skoots/lib/morphology.py:224-232, which cannot run as written): the maximum of the
+    3x3x3 window with zero padding on a (B, C, X, Y, Z) float32 device tensor."""
+    return _reference_rank(input, 26, "input").view(input.shape)
+
+
+def binary_erosion(image: Tensor) -> Tensor:
+    """The reference's ``binary_erosion`` (skoots/lib/morphology.py:131-152): the minimum of the 3x3x3 window with zero
+    padding on a (B, C, X, Y, Z) float32 device tensor, with the reference's result shape (1, B C, X, Y, Z)."""
+    return _reference_rank(image, 0, "image").unsqueeze(0)
