@@ -1112,6 +1112,55 @@ int sk_filter_taps(const void* in, void* out, int dtype, int X, int Y, int Z, co
                    int ny, const int* taps_z, int nz, int border, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Tile histograms and look-up-table transforms (ABI 34; not in the reference)
+ * ------------------------------------------------------------------------ */
+
+#define SK_EQUALIZE_HIST_ONE 0    /* a workgroup counts one tile in LDS, several copies of the table */
+#define SK_EQUALIZE_HIST_PLANES 1 /* tz == 1: a table per z-plane, a chunk of planes per workgroup */
+#define SK_EQUALIZE_HIST_ZTILES 2 /* tz >= 2: several z-tiles per workgroup */
+#define SK_EQUALIZE_HIST_GLOBAL 3 /* tile columns of fewer than 16 rows: 64-bit global atomics, no LDS */
+
+#define SK_EQUALIZE_APPLY_Z_ONE 0    /* bits 0 .. 1: one table along z */
+#define SK_EQUALIZE_APPLY_Z_TILE 1   /*   the table of the voxel's own z-tile */
+#define SK_EQUALIZE_APPLY_Z_INTERP 2 /*   two z-tiles, weighted */
+#define SK_EQUALIZE_APPLY_XY 4       /* or-ed in: x or y interpolates, four corner columns */
+#define SK_EQUALIZE_APPLY_ACC32 8    /* or-ed in: weighted sums in 32 bits; neither ACC bit: a plain look-up */
+#define SK_EQUALIZE_APPLY_ACC64 16   /* or-ed in: weighted sums in 64 bits */
+#define SK_EQUALIZE_APPLY_GATHER 32  /* or-ed in: cells of fewer than 16 rows, tables read from global memory, not staged */
+
+/* in: contiguous (X, Y, Z) of dtype SK_U8 or SK_U16, Z innermost.  bin(v) = min(v >> shift, bins - 1); SK_U8 takes
+ * bins = 256 and shift = 0, SK_U16 bins in {256, 1024, 4096} and shift in 0 .. 8.
+ * Tiles: tx, ty, tz >= 1, 0 = the whole axis, a side larger than the extent = the extent; with the side t so replaced,
+ * tile k of an axis of extent n covers [k t, min((k + 1) t, n)) and there are ceil(n / t) of them.
+ * sk_tile_histograms: out_counts is an int64 device table (nx, ny, nz, bins), zeroed by the call on the stream;
+ * [kx, ky, kz, b] counts the voxels of that tile with bin(v) == b.  Exact for every volume the extents admit (a
+ * workgroup counts fewer than 2^32 voxels in its 32-bit LDS counters and adds them to the table with 64-bit integer
+ * atomics) and the same on every run.
+ * sk_apply_tile_luts: luts is an int32 device table (nx, ny, nz, bins) with values in 0 .. the dtype's maximum (the
+ * CALLER's promise: values are used modulo 2^16).  interpolate == 0: out = luts[tile of the voxel][bin(v)].
+ * interpolate == 1: per axis, for index i, side t and n tiles, p = 2 i + 1 - t, k0 = floor(p / (2 t)), w1 = p - 2 t k0,
+ * w0 = 2 t - w1; the two tiles are clamp(k0, 0, n - 1) with weight w0 and clamp(k0 + 1, 0, n - 1) with weight w1 (tile
+ * centres at their nominal places, clipped tiles included; beyond the first and the last centre the nearest tile
+ * alone).  out = (S + W / 2) / W in integers, S the sum over the 8 corner tiles of wx wy wz luts[corner][bin(v)],
+ * W = 8 tx ty tz: the exact weighted mean rounded to nearest, halves up, rounded once.
+ * An axis with one tile, or with t == 1, has both weights on one tile: S = 2 t S' and W = 2 t W' with S', W' the sums
+ * without that axis, and (2 t S' + t W') / (2 t W') = floor((2 S' + W') / (2 W')) = (S' + W' / 2) / W' (for odd W',
+ * 2 S' + W' is odd and no multiple of 2 W', so the missing half does not matter).  The kernels therefore sum over the
+ * axes that do interpolate only, in 32 bits where that W' times the dtype's maximum is below 2^32 and in 64 bits
+ * otherwise; both are exact.  W' times the maximum must stay below 2^62.
+ * One launch each on the caller's stream (the histograms after a memset of the table), no workspace, nothing
+ * allocated.  Checked before any launch (SK_ERR_ARG): null pointers, in == out, element alignment (8 bytes for
+ * out_counts, 4 for luts), dtype, extents < 1 or > 2^30, negative tile sides, bins, shift, interpolate, more than
+ * 2^31 - 1 workgroups.
+ * sk_equalize_path: HOST, no GPU needed: the kernel a geometry takes, which = 0 SK_EQUALIZE_HIST_* of the histograms,
+ * which = 1 the SK_EQUALIZE_APPLY_* bits of the apply pass (or SK_ERR_ARG). */
+int sk_equalize_path(int which, int dtype, int X, int Y, int Z, int tx, int ty, int tz, int bins, int shift, int interpolate);
+int sk_tile_histograms(const void* in, int dtype, int X, int Y, int Z, int tx, int ty, int tz, int bins, int shift,
+                       long long* out_counts, void* stream);
+int sk_apply_tile_luts(const void* in, void* out, int dtype, int X, int Y, int Z, int tx, int ty, int tz, const int* luts, int bins,
+                       int shift, int interpolate, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Instance measurements: volume, box, moments and face area of every instance
  * ------------------------------------------------------------------------ */
 

@@ -6,7 +6,10 @@ the reference's main command exists here.  ``--pyramid`` (not in the reference) 
 ``<base>_skoots.ome.zarr``, the multiscale OME-Zarr group of image, instance mask and skeleton.  ``--rescale FX FY FZ``
 (not in the reference) resamples the image by those factors before the network and writes the mask on the input's grid.
 ``--denoise HOW A B C`` (not in the reference) filters the integer image on the device before that: ``HOW`` one of
-``median | mean | min | max`` with three integer radii, or ``gauss`` with three sigmas in voxels."""
+``median | mean | min | max`` with three integer radii, or ``gauss`` with three sigmas in voxels.  ``--equalize`` (not in
+the reference) transforms the grey values of the integer image after that: ``stretch LOW HIGH`` (percentiles), ``clahe TX
+TY TZ CLIP`` (contrast-limited adaptive equalisation in tiles), ``match REF.tif`` (the histogram of another image) or
+``slices`` (every z-plane matched to the whole stack)."""
 import argparse
 import glob
 import logging
@@ -34,6 +37,12 @@ def build_parser() -> argparse.ArgumentParser:
                            help="filters the integer image on the device before the network (and before --rescale), mirror "
                                 "borders: HOW is median, mean, min or max with three integer radii along x, y and z, or gauss "
                                 "with three sigmas in voxels (skoots_amd.lib.morphology.filter_volume)")
+    eval_args.add_argument("--equalize", type=str, nargs="+", default=None, metavar="HOW",
+                           help="transforms the grey values of the integer image on the device before the network (after "
+                                "--denoise, before --rescale): 'stretch LOW HIGH' sends those percentiles to 0 and the maximum, "
+                                "'clahe TX TY TZ CLIP' equalises in tiles of that size with the histogram clipped at CLIP times "
+                                "its mean, 'match REF.tif' matches the histogram of that image, 'slices' matches every z-plane "
+                                "to the whole stack (skoots_amd.lib.morphology.equalize)")
     eval_args.add_argument("--rescale", type=float, nargs=3, default=None, metavar=("FX", "FY", "FZ"),
                            help="output voxels per input voxel along x, y and z: the image is resampled on the device to the "
                                 "voxel size the model was trained at, the instance mask is written on the input's own grid "
@@ -49,6 +58,26 @@ def build_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def equalize_option(words) -> dict:
+    """``--equalize``'s words as ``eval``'s ``equalize`` dict: ``stretch LOW HIGH``, ``clahe TX TY TZ CLIP``, ``match
+    REF.tif`` or ``slices``"""
+    from skoots_amd.lib.eval import equalize_arguments
+    how, rest = words[0], list(words[1:])
+    forms = {"stretch": 2, "clahe": 4, "match": 1, "slices": 0}
+    if how not in forms or len(rest) != forms[how]:
+        raise ValueError(f"takes 'stretch LOW HIGH', 'clahe TX TY TZ CLIP', 'match REF.tif' or 'slices', got {' '.join(words)!r}")
+    if how == "stretch":
+        option = {"how": "stretch", "low": float(rest[0]), "high": float(rest[1])}
+    elif how == "clahe":
+        option = {"how": "equalize", "tile": tuple(int(v) for v in rest[:3]), "clip": float(rest[3])}
+    elif how == "match":
+        option = {"how": "match", "target": rest[0]}
+    else:
+        option = {"how": "match", "tile": "slices"}
+    equalize_arguments(option)
+    return option
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -61,6 +90,11 @@ def parse_args(argv=None) -> argparse.Namespace:
         except ValueError as e:
             parser.error(f"--denoise: {e}")
         args.denoise = (how, numbers)
+    if args.equalize is not None:
+        try:
+            args.equalize = equalize_option(args.equalize)
+        except (ValueError, FileNotFoundError) as e:
+            parser.error(f"--equalize: {e}")
     if args.skeletonize_train_data is None and args.convert is None and args.image is None:
         parser.error("the following arguments are required: --image")
     if args.rescale is not None and not all(0 < v < float("inf") for v in args.rescale):
@@ -94,6 +128,8 @@ def main(argv=None):
             extra["rescale"] = tuple(args.rescale)
         if args.denoise is not None:
             extra["denoise"] = args.denoise
+        if args.equalize is not None:
+            extra["equalize"] = args.equalize
         sk_eval(f, args.pretrained_checkpoint, used_cached_data=args.use_cached, output_huffman=args.output_huffman,
                 **extra)
 

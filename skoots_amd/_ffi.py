@@ -219,6 +219,9 @@ _SIGS = {
     "sk_filter_path": (i32, [i32] * 8 + [ip, i32, ip, i32, ip, i32, i32]),
     "sk_filter_rank": (i32, [vp, vp] + [i32] * 10 + [vp]),
     "sk_filter_taps": (i32, [vp, vp] + [i32] * 4 + [ip, i32, ip, i32, ip, i32, i32, vp]),
+    "sk_equalize_path": (i32, [i32] * 11),
+    "sk_tile_histograms": (i32, [vp] + [i32] * 9 + [vp, vp]),
+    "sk_apply_tile_luts": (i32, [vp, vp] + [i32] * 7 + [vp, i32, i32, i32, vp]),
     "sk_instance_stats_row_values": (i32, [i32]),
     "sk_instance_stats": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "sk_instance_mesh_cells": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp]),

@@ -289,10 +289,48 @@ def denoise_arguments(denoise) -> dict:
     return kwargs
 
 
+EQUALIZE_KEYS = ("how", "tile", "bins", "low", "high", "clip", "target", "top", "interpolate")
+
+
+def equalize_arguments(equalize) -> dict:
+    """``eval``'s ``equalize={"how": ..., ...}`` as the keywords of ``lib.morphology.equalize``, checked by
+    ``equalize_plan`` as far as that goes without the image: ``how`` and the keywords that belong to it.  A ``target``
+    given as a path must exist; it is read when the image is."""
+    from .morphology import equalize_plan
+    if not isinstance(equalize, dict) or "how" not in equalize:
+        raise ValueError(f"equalize must be a dict of lib.morphology.equalize's keywords with 'how' among them, got {equalize!r}")
+    unknown = [k for k in equalize if k not in EQUALIZE_KEYS]
+    if unknown:
+        raise ValueError(f"equalize takes {EQUALIZE_KEYS}, not {unknown}")
+    kwargs = dict(equalize)
+    if isinstance(kwargs.get("tile"), list):
+        kwargs["tile"] = tuple(kwargs["tile"])
+    target = kwargs.get("target")
+    if isinstance(target, (str, os.PathLike)):
+        if kwargs["how"] != "match":
+            raise ValueError(f"how={kwargs['how']!r} takes no target")
+        if not os.path.exists(target):
+            raise FileNotFoundError(f"equalize target {target} does not exist")
+        equalize_plan(**{k: v for k, v in kwargs.items() if k != "target"})
+    else:
+        equalize_plan(**kwargs)
+    return kwargs
+
+
+def _image_volume(path: str) -> Tensor:
+    """The (X, Y, Z) samples of an image file, the channel ``eval`` evaluates: uint16 through its bit pattern"""
+    image = _read_image(path)  # [Z, X, Y(, C)]
+    image = image[..., np.newaxis] if image.ndim == 3 else image
+    image = image.transpose(-1, 1, 2, 0)
+    image = image[[2], ...] if image.shape[0] > 3 else image
+    raw = np.ascontiguousarray(image[0])
+    return torch.from_numpy(raw.view(np.int16)).view(torch.uint16) if raw.dtype == np.uint16 else torch.from_numpy(raw)
+
+
 @torch.inference_mode()
 def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, precision: str = "fp16",
          read_on_device: Optional[bool] = None, output_huffman: Optional[str] = None, pyramid: bool = False,
-         rescale=None, denoise=None) -> None:
+         rescale=None, denoise=None, equalize=None) -> None:
     """Evaluates SKOOTS on an arbitrary image (drop-in for ``skoots.lib.eval.eval``).
 
     ``precision`` (not in the reference's signature; keyword with the reference's behaviour as default): "fp16" = what the
@@ -343,6 +381,14 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
     conversion: ``("median", (1, 1, 0))`` is the 3x3x1 median that removes shot noise and hot pixels.  A float image is
     refused by name before the model is built.  ``pyramid=True`` still writes the image as read.
 
+    ``equalize`` (keyword, not in the reference's signature; ``None`` by default, and without it every output is byte
+    for byte what it was): a dict of the keywords of ``lib.morphology.equalize`` -- ``{"how": "stretch", "low": 0.5,
+    "high": 99.5}``, ``{"how": "equalize", "tile": (64, 64, 16), "clip": 3.0}``, ``{"how": "match", "tile": "slices"}``,
+    ``{"how": "match", "target": "train_volume.tif"}`` (a path is read as the image is) -- that brings the grey values of
+    the integer image to what ``dataset_mean`` / ``dataset_std`` expect.  It runs on the device in the image's own dtype,
+    after ``denoise`` and before ``rescale`` and the fp16 conversion.  A float image is refused by name before the model is
+    built.  ``pyramid=True`` still writes the image as read.
+
     ``checkpoint_path``: ``torch.save``d dict with ``cfg`` (dict/attribute config holding
     ``SKOOTS.VECTOR_SCALING`` and ``MODEL.*``), ``model_state_dict`` and optionally
     ``dataset_mean`` / ``dataset_std`` (eval.py:51-55, 87-88, 99, 117-118).
@@ -359,6 +405,9 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         resample_shape((1, 1, 1), rescale)   # three positive finite numbers, or a ValueError that says so
     if denoise is not None:
         denoise = denoise_arguments(denoise)   # how and its three numbers, or a ValueError that says so
+    if equalize is not None:
+        equalize = equalize_arguments(equalize)   # how and its keywords, or a ValueError that says so
+    before = denoise is not None or equalize is not None   # the integer image is worked on before the network sees it
     start = time.time()
     logging.info(f"Loading model file: {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -381,12 +430,12 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         stack = stack[[2], ...] if stack.shape[0] > 3 else stack  # eval.py:64 -> [C=1, X, Y, Z]
         c, x, y, z = stack.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {stack.dtype}")
-        raw_img = stack[0] if pyramid or rescale is not None or denoise is not None else None
-        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous() if rescale is None and denoise is None \
+        raw_img = stack[0] if pyramid or rescale is not None or before else None
+        dev_img = _to_f32(stack[0]).to(torch.float16).contiguous() if rescale is None and not before \
             else None  # eval.py:80
         # the statistics fallback stays the CPU reduction over the same fp16 values: the image comes back for it only
         img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) and \
-            rescale is None and denoise is None else None
+            rescale is None and not before else None
     else:
         image = _read_image(image_path)  # [Z, X, Y(, C)]
         image = image[..., np.newaxis] if image.ndim == 3 else image
@@ -395,10 +444,10 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         c, x, y, z = image.shape
         logging.info(f"Loaded an image with shape: {(c, x, y, z)}, dtype: {image.dtype}")
         img16 = torch.from_numpy(np.ascontiguousarray(image[0]).astype(np.float32)).to(torch.float16) \
-            if rescale is None and denoise is None else None  # eval.py:80
+            if rescale is None and not before else None  # eval.py:80
         dev_img = None
         raw_img = None
-        if pyramid or rescale is not None or denoise is not None:     # the samples as read: uint16 through its bit pattern
+        if pyramid or rescale is not None or before:     # the samples as read: uint16 through its bit pattern
             raw = np.ascontiguousarray(image[0])
             raw_img = (torch.from_numpy(raw.view(np.int16)).view(torch.uint16) if raw.dtype == np.uint16
                        else torch.from_numpy(raw))
@@ -413,17 +462,31 @@ def eval(image_path: str, checkpoint_path: str, used_cached_data: bool = False, 
         spacing = check_spacing(aniso if aniso is not None else (1.0, 1.0, 3.0))
     input_shape = (x, y, z)
     denoised = None
-    if denoise is not None:
-        # the raw samples go up and are filtered there, in their own dtype; raw_img stays the image as read
-        from .morphology import check_filter, check_pool_volume, filter_volume, pool_source
+    if before:
+        # the raw samples go up and are worked on there, in their own dtype; raw_img stays the image as read
+        from .morphology import check_pool_volume, pool_source
         if raw_img.dtype.is_floating_point:
-            raise TypeError(f"image is {raw_img.dtype}: denoise filters the integer samples as read (uint8 / uint16), a float "
-                            "image is not denoised")
+            if denoise is not None:
+                raise TypeError(f"image is {raw_img.dtype}: denoise filters the integer samples as read (uint8 / uint16), a float "
+                                "image is not denoised")
+            raise TypeError(f"image is {raw_img.dtype}: equalize transforms the integer samples as read (uint8 / uint16), a "
+                            "float image is not equalized")
         check_pool_volume(raw_img, "mean", "image")
         denoised = pool_source(raw_img.to(device), "mean", "image")   # signed samples: 0 .. 65535 or a ValueError
-        check_filter(denoised, border="mirror", name="image", **denoise)
-        logging.info(f"Denoising the image: {denoise}")
-        denoised = filter_volume(denoised, border="mirror", **denoise)
+        if denoise is not None:
+            from .morphology import check_filter, filter_volume
+            check_filter(denoised, border="mirror", name="image", **denoise)
+            logging.info(f"Denoising the image: {denoise}")
+            denoised = filter_volume(denoised, border="mirror", **denoise)
+        if equalize is not None:
+            from .morphology import check_equalize, equalize as equalize_volume
+            if isinstance(equalize.get("target"), (str, os.PathLike)):
+                target = _image_volume(equalize["target"])
+                check_pool_volume(target, "mean", "equalize target")
+                equalize = dict(equalize, target=pool_source(target.to(device), "mean", "equalize target"))
+            check_equalize(denoised, name="image", **equalize)
+            logging.info("Equalizing the image: " + ", ".join(f"{k}={v!r}" for k, v in equalize.items() if k != "target"))
+            denoised = equalize_volume(denoised, **equalize)
         if rescale is None:
             dev_img = _to_f32(denoised).to(torch.float16).contiguous()
             img16 = dev_img.cpu() if not ("dataset_mean" in checkpoint and "dataset_std" in checkpoint) else None

@@ -14,7 +14,11 @@ either, nor ``nearest_label``, the nearest instance of every voxel and its dista
 filter (box mean, Gaussian) in front of the network, and under the reference's names ``median_filter``, ``dilate`` and
 ``binary_erosion`` (skoots/lib/morphology.py:131-152, 202-232) run on float32 tensors with zero padding.  The
 reference's ``mean_filter`` and ``gauss_filter`` on float tensors are not built: a float sum has no defined order, so
-nothing exact could be promised; use ``filter_volume(..., "mean" | "gauss")`` on the integer image."""
+nothing exact could be promised; use ``filter_volume(..., "mean" | "gauss")`` on the integer image.
+
+``equalize`` transforms the grey values themselves, driven by histograms: percentile stretch,
+histogram equalisation (global, and contrast-limited in tiles) and histogram matching, made of ``tile_histograms``, the
+pure table builders ``stretch_lut`` / ``equalize_lut`` / ``match_lut`` and ``apply_tile_luts``.  Not in the reference."""
 from __future__ import annotations
 
 import ctypes as C
@@ -1214,3 +1218,453 @@ def binary_erosion(image: Tensor) -> Tensor:
     """The reference's ``binary_erosion`` (skoots/lib/morphology.py:131-152): the minimum of the 3x3x3 window with zero
     padding on a (B, C, X, Y, Z) float32 device tensor, with the reference's result shape (1, B C, X, Y, Z)."""
     return _reference_rank(image, 0, "image").unsqueeze(0)
+
+
+# ---- tile histograms and look-up-table transforms (DESIGN.md section 39) ----
+
+EQUALIZE_HOW = ("stretch", "equalize", "match")
+EQUALIZE_BINS = {torch.uint8: (256,), torch.uint16: (256, 1024, 4096)}
+EQUALIZE_DEFAULT_BINS = {torch.uint8: 256, torch.uint16: 1024}
+EQUALIZE_MAX_SHIFT = 8
+EQUALIZE_HIST_PATHS = ("one", "planes", "ztiles", "global")            # SK_EQUALIZE_HIST_*
+EQUALIZE_Z_MODES = ("one", "tile", "interp")                           # SK_EQUALIZE_APPLY_Z_*
+_EQUALIZE_MAX_EXTENT = 2 ** 30
+_EQUALIZE_MAX_TOTAL = 2 ** 31
+_EQUALIZE_DEFAULTS = {"low": 0.5, "high": 99.5, "clip": 3.0, "target": None}
+_EQUALIZE_TAKES = {"stretch": ("low", "high"), "equalize": ("clip",), "match": ("target",)}
+
+
+def _dtype_top(dtype) -> int:
+    return 255 if dtype == torch.uint8 else 65535
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def histogram_shift(vmax: int, bins: int) -> int:
+    """The smallest ``s`` with ``vmax >> s < bins``"""
+    if not _is_int(vmax) or vmax < 0 or not _is_int(bins) or bins < 1:
+        raise ValueError(f"histogram_shift takes a maximum >= 0 and bins >= 1, got {vmax!r} and {bins!r}")
+    s = 0
+    while (int(vmax) >> s) >= bins:
+        s += 1
+    return s
+
+
+def equalize_tile(tile) -> Tuple[int, int, int]:
+    """``tile`` as ``(tx, ty, tz)``: ``None`` is ``(0, 0, 0)``, ``"slices"`` is ``(0, 0, 1)``, ``0`` the whole axis"""
+    if tile is None:
+        return 0, 0, 0
+    if isinstance(tile, str):
+        if tile != "slices":
+            raise ValueError(f"tile = {tile!r}: the only name is 'slices'")
+        return 0, 0, 1
+    try:
+        t = tuple(tile.tolist() if isinstance(tile, (Tensor, np.ndarray)) else tile)
+    except TypeError:
+        t = ()
+    if len(t) != 3 or not all(_is_int(k) for k in t):
+        raise ValueError(f"tile must be None, 'slices' or three integers (tx, ty, tz), got {tile!r}")
+    if not all(0 <= k <= _EQUALIZE_MAX_EXTENT for k in t):
+        raise ValueError(f"tile = {t}: every side must be >= 1 (or 0: the whole axis) and within 2^30")
+    return tuple(int(k) for k in t)
+
+
+def tile_grid(shape, tile) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """``(sides, counts)`` of ``tile`` on a volume of ``shape``: a side of 0, or larger than the extent, is the extent;
+    there are ``ceil(n / t)`` tiles per axis and the last may be clipped"""
+    t = equalize_tile(tile)
+    sides = tuple(int(n) if k == 0 or k > n else k for k, n in zip(t, shape))
+    return sides, tuple(-(-int(n) // k) for k, n in zip(sides, shape))
+
+
+def equalize_plan(how: str, tile=None, bins=None, low=0.5, high=99.5, clip=3.0, target=None, top=None,
+                  interpolate=True) -> dict:
+    """The arguments of ``equalize`` that can be judged without the volume, checked by name; returns them as keywords"""
+    if how not in EQUALIZE_HOW:
+        raise ValueError(f"how = {how!r}, must be one of {EQUALIZE_HOW}")
+    given = {"low": low, "high": high, "clip": clip, "target": target}
+    for key, value in given.items():
+        default = _EQUALIZE_DEFAULTS[key]
+        if key not in _EQUALIZE_TAKES[how] and not (value is default or (default is not None and value == default)):
+            raise ValueError(f"how={how!r} takes {' and '.join(_EQUALIZE_TAKES[how])}, not {key}")
+    t = equalize_tile(tile)
+    if bins is not None and bins not in EQUALIZE_BINS[torch.uint16]:
+        raise ValueError(f"bins = {bins!r}, must be 256, 1024 or 4096 (uint8: 256)")
+    if how == "stretch":
+        try:
+            low, high = float(low), float(high)
+        except (TypeError, ValueError):
+            raise ValueError(f"low and high must be numbers, got {low!r} and {high!r}") from None
+        if not (0 <= low <= 100 and 0 <= high <= 100):
+            raise ValueError(f"low = {low} and high = {high} must lie in 0 .. 100")
+        if not low < high:
+            raise ValueError(f"low = {low} must be below high = {high}")
+    if how == "equalize" and clip is not None:
+        if isinstance(clip, (bool, str)) or not isinstance(clip, (int, float, np.integer, np.floating)) or \
+                not 0 < float(clip) < float("inf"):
+            raise ValueError(f"clip = {clip!r}: a multiple of the mean bin height > 0, or None for no clipping")
+        clip = float(clip)
+    if top is not None and (not _is_int(top) or not 1 <= top <= 65535):
+        raise ValueError(f"top = {top!r}: the output maximum must be an integer in 1 .. the dtype's maximum")
+    if not isinstance(interpolate, (bool, np.bool_)):
+        raise ValueError(f"interpolate = {interpolate!r}, must be True or False")
+    return dict(how=how, tile=t, bins=bins, low=low, high=high, clip=clip, target=target, top=top,
+                interpolate=bool(interpolate))
+
+
+def _equalize_volume(volume, name: str):
+    """dtype and (X, Y, Z) of a volume the histogram kernels take, from its description"""
+    if not isinstance(volume, Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(volume).__name__}")
+    dt = volume.dtype
+    if dt not in EQUALIZE_BINS:
+        raise TypeError(f"{name} is {dt}: grey-value transforms take uint8 or uint16; float, signed, bool and complex volumes "
+                        "are refused")
+    s = tuple(int(v) for v in volume.shape)
+    s = s[1:] if len(s) == 4 and s[0] == 1 else s
+    if len(s) != 3 or min(s) < 1:
+        raise ValueError(f"{name} has the shape {tuple(volume.shape)}: it must be (X, Y, Z) or (1, X, Y, Z) with every "
+                         "extent at least 1")
+    if max(s) > _EQUALIZE_MAX_EXTENT:
+        raise ValueError(f"{name} of shape {s} is too large: every extent must stay within 2^30")
+    return dt, s
+
+
+def _equalize_bins(dt, bins, name: str) -> int:
+    if bins is None:
+        return EQUALIZE_DEFAULT_BINS[dt]
+    if bins not in EQUALIZE_BINS[dt]:
+        raise ValueError(f"bins = {bins!r}: {name} is {dt} and takes {' or '.join(str(b) for b in EQUALIZE_BINS[dt])}")
+    return int(bins)
+
+
+def check_equalize(volume, how: str, *, tile=None, bins=None, low=0.5, high=99.5, clip=3.0, target=None, top=None,
+                   interpolate=True, name: str = "volume"):
+    """What ``equalize`` takes, checked on the tensors' descriptions alone, before any device is touched.  Returns
+    ``((X, Y, Z), plan)`` with ``plan`` the checked keywords, ``bins`` and ``top`` filled in.  Refused by name: a ``how``
+    that is not one, arguments that belong to another ``how``, a tile that is not ``None``, ``"slices"`` or three sides
+    >= 0, a tile of 2^31 voxels or more, ``bins`` the dtype does not take, ``low`` / ``high`` outside 0 .. 100 or not in
+    order, a ``clip`` that is not positive, a ``top`` beyond the dtype's maximum, a target that is neither a volume of
+    the same dtype with fewer than 2^31 voxels nor a 1-D int64 histogram of ``bins`` entries (``ValueError``); a volume
+    that is not a tensor or not uint8 / uint16 (``TypeError``); shapes that are not (X, Y, Z) or (1, X, Y, Z), extents
+    beyond 2^30."""
+    plan = equalize_plan(how, tile, bins, low, high, clip, target, top, interpolate)
+    dt, s = _equalize_volume(volume, name)
+    plan["bins"] = _equalize_bins(dt, bins, name)
+    if plan["top"] is None:
+        plan["top"] = _dtype_top(dt)
+    elif plan["top"] > _dtype_top(dt):
+        raise ValueError(f"top = {plan['top']} is beyond the maximum of {dt}")
+    sides, _ = tile_grid(s, plan["tile"])
+    if sides[0] * sides[1] * sides[2] >= _EQUALIZE_MAX_TOTAL:
+        raise ValueError(f"a tile of {sides} has 2^31 voxels or more: the tables are built from totals below 2^31")
+    if target is not None:
+        if isinstance(target, np.ndarray):
+            target = torch.from_numpy(target)
+        if not isinstance(target, Tensor):
+            raise TypeError(f"target must be a volume, a 1-D int64 histogram or None, got {type(target).__name__}")
+        if target.ndim == 1:
+            if target.dtype != torch.int64 or target.numel() != plan["bins"]:
+                raise ValueError(f"a target histogram must be int64 with bins = {plan['bins']} entries, got {target.dtype} "
+                                 f"with {target.numel()}")
+        else:
+            tdt, ts = _equalize_volume(target, "target")
+            if tdt != dt:
+                raise TypeError(f"target is {tdt} and {name} is {dt}: a target volume has the volume's dtype")
+            if ts[0] * ts[1] * ts[2] >= _EQUALIZE_MAX_TOTAL:
+                raise ValueError(f"target of shape {ts} has 2^31 voxels or more")
+        plan["target"] = target
+    return s, plan
+
+
+def _as_numpy(t: Tensor) -> np.ndarray:
+    t = t.detach().cpu().contiguous()
+    return t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.uint16 else t.numpy()
+
+
+def _from_numpy(a: np.ndarray) -> Tensor:
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.int16)).view(torch.uint16) if a.dtype == np.uint16 else torch.from_numpy(a)
+
+
+def volume_max(v: Tensor) -> int:
+    """The largest sample of a uint8 / uint16 tensor, where it lives"""
+    if v.dtype == torch.uint16:
+        s = v.view(torch.int16)
+        return (int(torch.bitwise_xor(s, -32768).max()) ^ -32768) & 0xFFFF    # unsigned order through the sign bit
+    return int(v.max())
+
+
+def _hist_shift(dt, bins: int, shift, vmax) -> int:
+    if dt == torch.uint8:
+        if shift not in (None, 0):
+            raise ValueError(f"shift = {shift!r}: uint8 takes shift 0")
+        return 0
+    if shift is None:
+        return histogram_shift(vmax(), bins)
+    if not _is_int(shift) or not 0 <= shift <= EQUALIZE_MAX_SHIFT:
+        raise ValueError(f"shift = {shift!r}, must be an integer in 0 .. {EQUALIZE_MAX_SHIFT}")
+    return int(shift)
+
+
+def _axis_tiles(n: int, t: int) -> np.ndarray:
+    return np.arange(n, dtype=np.int64) // t
+
+
+def _axis_pairs(n: int, t: int, count: int, interpolate: bool):
+    """per index of an axis: the two tiles and their weights"""
+    i = np.arange(n, dtype=np.int64)
+    if not interpolate:
+        k = i // t
+        return k, k, np.ones(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    p = 2 * i + 1 - t
+    k0 = p // (2 * t)
+    w1 = p - 2 * t * k0
+    return np.clip(k0, 0, count - 1), np.clip(k0 + 1, 0, count - 1), 2 * t - w1, w1
+
+
+def _histograms_host(a: np.ndarray, sides, counts, bins: int, shift: int) -> np.ndarray:
+    b = np.minimum(a.astype(np.int64) >> shift, bins - 1)
+    kx, ky, kz = (_axis_tiles(n, t) for n, t in zip(a.shape, sides))
+    tile = (kx[:, None, None] * counts[1] + ky[None, :, None]) * counts[2] + kz[None, None, :]
+    flat = np.bincount((tile * bins + b).ravel(), minlength=counts[0] * counts[1] * counts[2] * bins)
+    return flat.astype(np.int64).reshape(*counts, bins)
+
+
+def _apply_host(a: np.ndarray, luts: np.ndarray, sides, counts, bins: int, shift: int, interpolate: bool) -> np.ndarray:
+    b = np.minimum(a.astype(np.int64) >> shift, bins - 1)
+    luts = luts.astype(np.int64)
+    ax = [_axis_pairs(n, t, c, interpolate) for n, t, c in zip(a.shape, sides, counts)]
+    if not interpolate:
+        return luts[ax[0][0][:, None, None], ax[1][0][None, :, None], ax[2][0][None, None, :], b].astype(a.dtype)
+    W = 8 * sides[0] * sides[1] * sides[2]
+    if W * 65535 >= 2 ** 63:
+        raise ValueError(f"tile sides {sides} are too large for the host path")
+    S = np.zeros(a.shape, dtype=np.int64)
+    for cx in (0, 1):
+        for cy in (0, 1):
+            for cz in (0, 1):
+                w = ax[0][2 + cx][:, None, None] * ax[1][2 + cy][None, :, None] * ax[2][2 + cz][None, None, :]
+                S += w * luts[ax[0][cx][:, None, None], ax[1][cy][None, :, None], ax[2][cz][None, None, :], b]
+    return ((S + W // 2) // W).astype(a.dtype)
+
+
+def tile_histograms(volume: Tensor, tile=None, bins=None, shift=None) -> Tensor:
+    """int64 ``(nx, ny, nz, bins)`` on the volume's device: entry ``[kx, ky, kz, b]`` counts the voxels of that tile with
+    ``min(v >> shift, bins - 1) == b``.  ``shift=None`` is ``histogram_shift`` of the volume's maximum.  Exact, and the
+    same on every run; one launch of ``sk_tile_histograms`` on a device tensor, numpy statements on a CPU tensor."""
+    dt, s = _equalize_volume(volume, "volume")
+    bins = _equalize_bins(dt, bins, "volume")
+    sides, counts = tile_grid(s, tile)
+    v = (volume[0] if volume.ndim == 4 else volume).contiguous()
+    shift = _hist_shift(dt, bins, shift, lambda: volume_max(v))
+    if not v.is_cuda:
+        return torch.from_numpy(_histograms_host(_as_numpy(v), sides, counts, bins, shift))
+    out = torch.empty(counts + (bins,), dtype=torch.int64, device=v.device)
+    _ffi.check(_ffi.lib.sk_tile_histograms(_ffi.ptr(v), _FILTER_CODE[dt], *s, *sides, bins, shift, _ffi.ptr(out),
+                                           _ffi.stream_ptr(v.device)))
+    return out
+
+
+def apply_tile_luts(volume: Tensor, luts: Tensor, tile=None, shift: int = 0, interpolate: bool = True, out=None) -> Tensor:
+    """Every voxel through the tables of the tiles around it: ``luts`` is int32 ``(nx, ny, nz, bins)`` with values in
+    ``0 .. dtype max``.  ``interpolate=False``: ``luts[tile of the voxel][bin(v)]``.  ``interpolate=True``: the weighted
+    mean of the 8 surrounding tiles' entries, weights linear between the tile centres, ``(S + W // 2) // W`` with
+    ``W = 8 tx ty tz``, rounded once (include/skoots_hip.h has the formulas).  One launch of ``sk_apply_tile_luts`` on a
+    device tensor; a CPU tensor gives the same bits through numpy.  ``out``, device tensors only: a contiguous (X, Y, Z)
+    tensor of the volume's dtype and device to write into, another buffer than the volume."""
+    dt, s = _equalize_volume(volume, "volume")
+    sides, counts = tile_grid(s, tile)
+    if isinstance(luts, np.ndarray):
+        luts = torch.from_numpy(luts)
+    if not isinstance(luts, Tensor) or luts.dtype != torch.int32 or luts.ndim != 4 or tuple(luts.shape[:3]) != counts \
+            or luts.shape[3] not in EQUALIZE_BINS[dt]:
+        raise ValueError(f"luts must be an int32 tensor {counts + ('bins',)} with bins one of {EQUALIZE_BINS[dt]}, got "
+                         f"{getattr(luts, 'dtype', type(luts).__name__)} {tuple(getattr(luts, 'shape', ()))}")
+    bins = int(luts.shape[3])
+    shift = _hist_shift(dt, bins, int(shift) if _is_int(shift) else shift, None)
+    if not isinstance(interpolate, (bool, np.bool_)):
+        raise ValueError(f"interpolate = {interpolate!r}, must be True or False")
+    v = (volume[0] if volume.ndim == 4 else volume).contiguous()
+    luts = luts.to(v.device).contiguous()
+    if int(luts.min()) < 0 or int(luts.max()) > _dtype_top(dt):
+        raise ValueError(f"luts holds values outside 0 .. {_dtype_top(dt)}, the range of {dt}")
+    if not v.is_cuda:
+        if out is not None:
+            raise ValueError("out is for device tensors")
+        out = _from_numpy(_apply_host(_as_numpy(v), luts.numpy(), sides, counts, bins, shift, bool(interpolate)))
+    else:
+        if out is None:
+            out = torch.empty_like(v)
+        elif not isinstance(out, Tensor) or out.dtype != dt or out.device != v.device or tuple(out.shape) != s or \
+                not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dt} tensor of shape {s} on {v.device}")
+        _ffi.check(_ffi.lib.sk_apply_tile_luts(_ffi.ptr(v), _ffi.ptr(out), _FILTER_CODE[dt], *s, *sides, _ffi.ptr(luts), bins,
+                                               shift, int(bool(interpolate)), _ffi.stream_ptr(v.device)))
+    return out.unsqueeze(0) if volume.ndim == 4 else out
+
+
+def _hist_array(h, what: str = "h"):
+    h = np.asarray(h.detach().cpu().numpy() if isinstance(h, Tensor) else h)
+    if h.ndim < 1 or h.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be an integer array (..., bins)")
+    h = h.astype(np.int64)
+    n = h.sum(axis=-1)
+    if h.min() < 0 or n.min() < 1 or n.max() >= _EQUALIZE_MAX_TOTAL:
+        raise ValueError(f"{what}: every histogram needs counts >= 0 and a total in 1 .. 2^31 - 1")
+    return h, n
+
+
+def _lut_top(top, bins: int) -> int:
+    if top is None:
+        return 255 if bins == 256 else 65535
+    if not _is_int(top) or not 1 <= top <= 65535:
+        raise ValueError(f"top = {top!r}: the output maximum must be an integer in 1 .. 65535")
+    return int(top)
+
+
+def _first_reaching(H: np.ndarray, k: np.ndarray) -> np.ndarray:
+    """per leading index the first bin whose inclusive cumulative sum reaches k"""
+    return (H >= k[..., None]).argmax(axis=-1)
+
+
+def stretch_bounds(h, low: float = 0.5, high: float = 99.5):
+    """``(lo, hi)``: the nearest-rank percentile bins of ``(..., bins)`` histograms -- for ``q`` percent the first bin
+    whose cumulative sum reaches ``clamp(ceil(q / 100 * n), 1, n)``, numpy's ``method="inverted_cdf"`` on the bins"""
+    h, n = _hist_array(h)
+    equalize_plan("stretch", low=low, high=high)
+    H = np.cumsum(h, axis=-1)
+    ks = [np.clip(np.ceil(float(q) / 100 * n.astype(np.float64)).astype(np.int64), 1, n) for q in (low, high)]
+    return _first_reaching(H, ks[0]), _first_reaching(H, ks[1])
+
+
+def stretch_lut(h, low: float = 0.5, high: float = 99.5, top=None, shift: int = 0) -> np.ndarray:
+    """Percentile stretch: ``lut[b] = clamp(((b - lo) * top + (hi - lo) // 2) // (hi - lo), 0, top)`` with ``lo``, ``hi``
+    of ``stretch_bounds``; where ``hi == lo`` the identity ``b << shift`` clamped to ``top``.  ``h`` is ``(..., bins)``
+    int64, the result int32 of the same shape; ``top=None`` is 255 for 256 bins and 65535 otherwise."""
+    lo, hi = stretch_bounds(h, low, high)
+    bins = np.shape(h)[-1]
+    top = _lut_top(top, bins)
+    b = np.arange(bins, dtype=np.int64)
+    d = (hi - lo)[..., None]
+    lut = np.clip(((b - lo[..., None]) * top + d // 2) // np.maximum(d, 1), 0, top)
+    return np.where(d > 0, lut, np.minimum(b << shift, top)).astype(np.int32)
+
+
+def equalize_lut(h, clip=None, top=None) -> np.ndarray:
+    """Histogram equalisation: ``lut[b] = (H'[b] * top + n // 2) // n`` with ``H'`` the cumulative sum of the clipped
+    histogram.  ``clip`` (a multiple of the mean bin height, > 0): ``c = max(1, ceil(clip * n / bins))``, the excess
+    ``E = sum(max(h - c, 0))`` is cut off and handed back, ``E // bins`` to every bin and one more to the ``E % bins``
+    lowest-numbered bins, once.  ``clip=None`` is plain equalisation."""
+    h, n = _hist_array(h)
+    bins = h.shape[-1]
+    top = _lut_top(top, bins)
+    if clip is not None:
+        clip = equalize_plan("equalize", clip=clip)["clip"]
+        c = np.maximum(1, np.ceil(clip * n.astype(np.float64) / bins).astype(np.int64))[..., None]
+        E = np.maximum(h - c, 0).sum(axis=-1)
+        q, r = np.divmod(E, bins)
+        h = np.minimum(h, c) + q[..., None] + (np.arange(bins, dtype=np.int64) < r[..., None])
+    H = np.cumsum(h, axis=-1)
+    return ((H * top + (n // 2)[..., None]) // n[..., None]).astype(np.int32)
+
+
+def match_lut(h, g, shift: int = 0, top=None) -> np.ndarray:
+    """Histogram matching to the target histogram ``g`` (``(bins,)`` or of ``h``'s shape): ``t[b]`` is the smallest ``t``
+    with ``G[t] * n >= H[b] * m`` (``G``, ``m`` the target's cumulative sum and total) and ``lut[b] = min(t[b] << shift,
+    top)``."""
+    h, n = _hist_array(h)
+    g, m = _hist_array(g, "g")
+    bins = h.shape[-1]
+    if g.shape[-1] != bins:
+        raise ValueError(f"the target has {g.shape[-1]} bins and h has {bins}")
+    top = _lut_top(top, bins)
+    H, G = np.cumsum(h, axis=-1), np.cumsum(g, axis=-1)
+    need = (H * np.broadcast_to(m, n.shape)[..., None] + n[..., None] - 1) // n[..., None]   # G[t] n >= H m <=> G[t] >= ceil(H m / n)
+    if g.ndim == 1:
+        t = np.searchsorted(G, need, side="left")
+    else:                                         # one sorted array of all targets: target k lives in k M .. k M + m_k
+        G = np.broadcast_to(G, h.shape).reshape(-1, bins)
+        M = int(m.max()) + 1
+        off = np.arange(G.shape[0], dtype=np.int64)[:, None] * M
+        t = np.searchsorted((G + off).ravel(), (need.reshape(-1, bins) + off).ravel(), side="left").reshape(-1, bins)
+        t = (t - np.arange(G.shape[0], dtype=np.int64)[:, None] * bins).reshape(h.shape)
+    return np.minimum(t.astype(np.int64) << shift, top).astype(np.int32)
+
+
+def equalize(volume: Tensor, how: str, *, tile=None, bins=None, low=0.5, high=99.5, clip=3.0, target=None, top=None,
+             interpolate=True, report=None) -> Tensor:
+    """A histogram-driven transform of the grey values of a uint8 / uint16 (X, Y, Z) or (1, X, Y, Z) tensor on the device
+    it lives on: ``tile_histograms``, then a table per tile, then ``apply_tile_luts``.
+
+    ``how="stretch"``: the ``low`` and ``high`` percentiles (nearest rank, on the bins) go to 0 and ``top``
+    (``stretch_lut``).  ``how="equalize"``: histogram equalisation with the histogram clipped at ``clip`` times the mean bin
+    height (``equalize_lut``); ``clip=None`` with ``tile=None`` is global equalisation, with tiles it is CLAHE in 3-D, with
+    ``(tx, ty, 0)`` CLAHE per column of planes.  ``how="match"``: histogram matching (``match_lut``) to ``target`` -- a
+    volume of the same dtype (its global histogram at the same bins and shift), a 1-D int64 histogram of ``bins`` entries,
+    or ``None``, the volume's own global histogram, which with ``tile="slices"`` removes slice flicker.
+
+    ``tile``: ``(tx, ty, tz)``, 0 = the whole axis; ``None`` = one tile; ``"slices"`` = one per z-plane.  ``bins``: 256 for
+    uint8; 256, 1024 (default) or 4096 for uint16, with ``bin(v) = min(v >> shift, bins - 1)`` and the shift
+    ``histogram_shift`` of the volume's maximum (for a target volume: of the larger of the two).  ``top``: the output
+    maximum, the dtype's by default.  ``interpolate``: tables are interpolated between tile centres so that no tile edge
+    shows.  ``report``, a dict, receives ``shift``, ``bins``, ``grid``, ``paths`` and for ``"stretch"`` ``lo`` / ``hi``.
+    Everything is integer arithmetic: a CPU tensor gives the same bits through numpy.  ``check_equalize`` lists what is
+    refused."""
+    s, plan = check_equalize(volume, how, tile=tile, bins=bins, low=low, high=high, clip=clip, target=target, top=top,
+                             interpolate=interpolate)
+    v = (volume[0] if volume.ndim == 4 else volume).contiguous()
+    dt, nbins, out_top, t = v.dtype, plan["bins"], plan["top"], plan["tile"]
+    goal = plan["target"]
+    goal_volume = None
+    if goal is not None and goal.ndim != 1:
+        goal_volume = (goal[0] if goal.ndim == 4 else goal).contiguous()
+    shift = 0
+    if dt == torch.uint16:
+        vmax = volume_max(v)
+        if goal_volume is not None:
+            vmax = max(vmax, volume_max(goal_volume))
+        shift = histogram_shift(vmax, nbins)
+    h = tile_histograms(v, t, nbins, shift).cpu().numpy()
+    if how == "stretch":
+        luts = stretch_lut(h, plan["low"], plan["high"], out_top, shift)
+    elif how == "equalize":
+        luts = equalize_lut(h, plan["clip"], out_top)
+    else:
+        if goal_volume is not None:
+            g = tile_histograms(goal_volume, None, nbins, shift)[0, 0, 0].cpu().numpy()
+        elif goal is not None:
+            g = goal.cpu().numpy()
+        else:
+            g = h.reshape(-1, nbins).sum(axis=0)
+        luts = match_lut(h, g, shift, out_top)
+    if report is not None:
+        sides, counts = tile_grid(s, t)
+        report.update(shift=shift, bins=nbins, grid=counts, sides=sides,
+                      paths=equalize_path(dt, s, t, nbins, shift, plan["interpolate"]) if v.is_cuda else ("numpy", "numpy"))
+        if how == "stretch":
+            lo, hi = stretch_bounds(h, plan["low"], plan["high"])
+            report.update(lo=lo, hi=hi)
+    out = apply_tile_luts(v, torch.from_numpy(luts), t, shift, plan["interpolate"])
+    return out.unsqueeze(0) if volume.ndim == 4 else out
+
+
+def equalize_path(dtype, shape, tile=None, bins=None, shift: int = 0, interpolate: bool = True) -> Tuple[str, str]:
+    """Which kernels ``tile_histograms`` and ``apply_tile_luts`` run for this geometry, answered on the host:
+    ``(histograms, apply)``.  ``histograms`` is one of ``EQUALIZE_HIST_PATHS`` -- ``"one"`` (a workgroup counts one tile in
+    LDS), ``"planes"`` (``tz == 1``: a table per z-plane), ``"ztiles"`` (several z-tiles per workgroup), ``"global"`` (tile
+    columns of fewer than 16 rows).  ``apply`` is ``"<lds|gather>/<xy|-><z-mode>/<lookup|acc32|acc64>"``: tables staged in
+    LDS or gathered from global memory; whether x or y interpolates and how z picks its table (``one``, ``tile``,
+    ``interp``); a plain look-up or weighted sums of that width."""
+    bins = _equalize_bins(dtype, bins, "the volume")
+    X, Y, Z = (int(n) for n in shape)
+    t = equalize_tile(tile)
+    rc = [int(_ffi.lib.sk_equalize_path(which, _FILTER_CODE[dtype], X, Y, Z, *t, bins, int(shift), int(bool(interpolate))))
+          for which in (0, 1)]
+    for r in rc:
+        _ffi.check(r if r < 0 else 0)
+    a = rc[1]
+    return EQUALIZE_HIST_PATHS[rc[0]], "/".join(("gather" if a & 32 else "lds", ("xy+" if a & 4 else "-+") + EQUALIZE_Z_MODES[a & 3],
+                                                 "acc64" if a & 16 else "acc32" if a & 8 else "lookup"))
